@@ -21,7 +21,14 @@ mfx_render_rgba8(ctx, 1, buf) with the 8 MB RGBA8 readback, the config's spp cal
 Rays counted = primary + extension (closest-hit queries actually traced) + shadow rays, read
 from the kernel's own counters. Inputs (scene, BVH) are resident in HBM before timing starts.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times --steps steps (back to back, no host read between them), writes
+the last step's outputs if --dump-outputs DIR is given (dump_outputs) and prints the line: metric,
+value, ms_per_step (wall milliseconds of one timed step), rays_per_step, config. Everything else is
+measured only with --full, after the timed steps or in processes of their own; without it these
+objects are null. At N > 1 --full also times the other scaling's job and checks the merged frame
+against one GPU (`verify`, merged_equals_1gpu).
+
+Extra objects on the JSON line (--full):
   roofline      the dominant kernel of the wavefront pipeline (k_extend<false>: path start +
                 closest-hit traversal; k_shadow<false>: shading + shadow-ray traversal; whichever
                 takes the larger share of the step, the other in `other_kernel`) — algorithmic
@@ -122,7 +129,16 @@ def parse():
     ap.add_argument("--sample-base", type=int, default=0,
                     help="global sample index of the first warmup step's first sample (steps follow on)")
     ap.add_argument("--no-verify", action="store_true",
-                    help="N > 1: skip the merged-frame check against one GPU (merged_equals_1gpu)")
+                    help="--full, N > 1: skip the merged-frame check against one GPU (merged_equals_1gpu)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: per-stage times and traversal counters (roofline), render_api, "
+                         "sample_api, strong_share, cpu_baseline, and at N > 1 the other scaling and the merged-frame "
+                         "check (the --no-* options switch single ones off); off: set up, warm up, time the steps, "
+                         "print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0): the FP64 "
+                         "accumulator [3][w*h] of the frame (accum.npy), or with --api render the last call's RGBA8 "
+                         "frame as float32 (rgba8.npy)")
     # internal: measure strong_share in this (fresh) process for the parent run's VALUE_1GPU, MS_1GPU
     ap.add_argument("--strong-share-child", nargs=2, type=float, default=None, help=argparse.SUPPRESS)
     return ap.parse_args()
@@ -543,6 +559,33 @@ def verify_merge(arrays, ctx, ctxs, pr, accs, gathers, rank, world, local, backe
                     "compared bit for bit (digest: blake2b-64 of their bytes)"}
 
 
+def dump_outputs(out_dir, ctx, pr, rbuf):
+    """--dump-outputs: what the last timed step left its caller, as DIR/<name>.npy. Called after the
+    final barrier, so every step and exchange has finished.
+      accum.npy  float64 [3][w*h]: the step's FP64 accumulator (sums over its samples, one plane per
+                 channel, as mfx_accum_device_ptr exposes it; 50 MB at 1080p). One process per GPU:
+                 rank 0's merged buffer of the last frame.
+      rgba8.npy  (--api render) float32 [w*h][4]: the RGBA8 frame the last render call wrote.
+    The scene, seed and sample range are functions of the arguments alone, so two builds run with the
+    same arguments write comparable files."""
+    import ctypes as C
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if rbuf is not None:
+        np.save(os.path.join(out_dir, "rgba8.npy"), rbuf.reshape(-1, 4).astype(np.float32))
+        return
+    if pr is not None:
+        acc = pr.buffer(pr.k - 1).cpu().numpy()
+    else:
+        src, nbytes = ctx.accum_device_ptr()
+        acc = np.empty(nbytes // 8, dtype=np.float64)
+        hip = C.CDLL("libamdhip64.so")
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        if hip.hipMemcpy(acc.ctypes.data, src, nbytes, 2) != 0:  # hipMemcpyDeviceToHost
+            raise RuntimeError("--dump-outputs: hipMemcpy of the accumulator failed")
+    np.save(os.path.join(out_dir, "accum.npy"), acc.reshape(3, -1))
+
+
 def main():
     args = parse()
     # the JSON line is the only thing on stdout: libraries that print banners there (RCCL prints
@@ -574,8 +617,8 @@ def main():
     # Never from a profiled process (the profiler initialised the GPU before this one started).
     share_runs = []
     # (the metric's configuration only: C3's 1024 spp in three fresh processes would take minutes)
-    if (int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and args.api == "batch" and not args.no_render_api
-            and not args.megakernel and not _under_profiler() and args.config == "C2"):
+    if (args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and args.api == "batch"
+            and not args.no_render_api and not args.megakernel and not _under_profiler() and args.config == "C2"):
         cmd = [sys.executable, os.path.abspath(__file__), "--config", args.config, "--scene", args.scene,
                "--steps", str(args.steps), "--strong-share-child", "0", "0"] + \
               (["--spp", str(args.spp)] if args.spp is not None else [])
@@ -722,6 +765,9 @@ def main():
     else:
         c = totals()  # every timed step's counters, summed on the device
         rays, closest_rays, primary_rays = c[0] + c[1] + c[2], c[0] + c[1], c[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, pr, rbuf if args.api == "render" else None)
+    if args.full and args.api != "render":
         # per-stage device times (HIP events around each launch) from two more steps of the same
         # workload, each read after it (the timed steps above carry no per-step host read)
         for k in range(2):
@@ -741,7 +787,7 @@ def main():
     elapsed, rays_all = job_max_sum(elapsed, rays)
 
     other = None
-    if ngpu > 1 and args.api == "batch":
+    if args.full and ngpu > 1 and args.api == "batch":
         # the same job under the other scaling, in the same run (barriers, max over ranks): strong
         # lines carry the weak job (the config's spp of a whole film per GPU), weak lines the strong
         # one (the config's spp split over the GPUs)
@@ -788,12 +834,12 @@ def main():
     verify = topo = None
     if ngpu > 1 or use_dist:
         topo = topology(ctx, use_dist, dist, backend, local, world, args.single_process)
-        if args.api == "batch" and not args.no_verify:
+        if args.full and args.api == "batch" and not args.no_verify:
             verify = verify_merge(arrays, ctx, ctxs, pr, accs if use_dist else None, gathers if use_dist else None,
                                   rank, world, local, backend, spp_step, mode, rows, args.single_process, devices, npix)
     stage_ms = {k: float(np.mean([t[k] for t in timings]))
                 for k in ("total_ms", "camera_ms", "extend_ms", "camera_launches", "shadow_ms", "iterations", "launches",
-                          "generations")}
+                          "generations")} if timings else None
 
     result = None
     # launches per timed unit: a step, or (--api render) one 1-spp call
@@ -801,7 +847,7 @@ def main():
     if rank == 0:
         # traversal counters (separate, untimed pass at 1 spp of the same frame)
         stats = None
-        if not args.no_stats:
+        if args.full and not args.no_stats:
             # per-ray counters: the camera rays' packet walk (k_camera) would count its union of
             # visits for every lane, so this pass traces them one ray per lane
             old = os.environ.get("MFX_CAMERA_PACKETS")
@@ -1043,7 +1089,7 @@ def main():
                                         else round(d, 4)) for g, d in stats.items()}
         value = rays_all / elapsed / 1e6
         rapi = sapi = share = None
-        if ngpu == 1 and args.api == "batch" and not args.no_render_api and not args.megakernel:
+        if args.full and ngpu == 1 and args.api == "batch" and not args.no_render_api and not args.megakernel:
             # the shipped binding's default (fsharp/Native.fs DefaultRenderAhead, native.Scene): Scene.Render
             # served from batches of DEFAULT_RENDER_AHEAD samples
             cf = CONFIG_FLAGS.get(args.config, 0)
@@ -1062,7 +1108,7 @@ def main():
             share = combine_shares(share_runs, value, elapsed / args.steps * 1e3) if share_runs else \
                 {"skipped": "under a profiler" if _under_profiler() else "measured on the metric's configuration (C2)"}
         cpu = None
-        if ngpu == 1 and not args.no_cpu_baseline:
+        if args.full and ngpu == 1 and not args.no_cpu_baseline:
             progress("cpu_baseline")
             cpu = cpu_baseline(arrays, args.spp, DEFAULT_SEED, args.cpu_seconds)
         if ngpu == 1 and use_dist:
@@ -1087,7 +1133,7 @@ def main():
                if args.api == "render" else "mfx_trace_accumulate of the step's spp (inputs resident in HBM)")
         result = {
             "metric": METRIC, "value": round(value, 2), "unit": "Mrays/s", "n_gpus": ngpu,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "steps": args.steps, "warmup": args.warmup, "full": args.full, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "rays_per_step": rays_all / args.steps,
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f64",
             "data": "synthetic",

@@ -10,7 +10,7 @@ TAG=${1:-r01}
 OUT=$R/gpurun_out/configs_$TAG
 mkdir -p $OUT
 for c in C2 C3 C4 C5; do
-  timeout -k 10 300 python3 $R/bench.py --config $c --steps 2 --warmup 1 > $OUT/bench_$c.json 2> $OUT/bench_$c.err
+  timeout -k 10 300 python3 $R/bench.py --full --config $c --steps 2 --warmup 1 > $OUT/bench_$c.json 2> $OUT/bench_$c.err
   cat $OUT/bench_$c.json
 done
 MFX_DIAG_ITER=1 timeout -k 10 120 python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-stats \

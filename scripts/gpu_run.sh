@@ -4,8 +4,8 @@
 # each under its own time limit; the first failing step ends the run (set -e).
 #   tests[:PATTERN]      pytest -m gpu (optionally -k PATTERN), verbose log
 #   smoke                __graft_entry__.smoke()
-#   bench:CFG[:ARGS]     bench.py --config CFG (ARGS: extra bench args, comma-separated) -> bench_CFG.json
-#   default              bench.py with no arguments (the driver's N = 1 line) -> bench_default.json
+#   bench:CFG[:ARGS]     bench.py --full --config CFG (ARGS: extra bench args, comma-separated) -> bench_CFG.json
+#   default              bench.py --full (the N = 1 line with every extra object) -> bench_default.json
 #   prof:CFG             rocprofv3 kernel trace/stats + FETCH_SIZE / WRITE_SIZE passes (profile_traffic.sh)
 #   td:CFG               TD roof PMC pass of the bench step and the td_gather peak (pmc_td_roof.sh)
 #   pmc:CFG              the TD / TCP / SQ counter groups (pmc_td.sh)
@@ -55,10 +55,10 @@ for step in "$@"; do
       cat $O/smoke.log ;;
     bench)
       X=(); [ -n "$a2" ] && IFS=, read -ra X <<< "$a2"
-      timeout -k 10 420 python3 bench.py --config $a1 "${X[@]}" > $O/bench_$a1.json 2> $O/bench_$a1.err
+      timeout -k 10 420 python3 bench.py --full --config $a1 "${X[@]}" > $O/bench_$a1.json 2> $O/bench_$a1.err
       python3 -c "import json; d=json.load(open('$O/bench_$a1.json')); print('$a1', d['value'], d['ms_per_step'])" ;;
     default)
-      timeout -k 10 420 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+      timeout -k 10 420 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
       python3 -c "import json; d=json.load(open('$O/bench_default.json')); print('default', d['value'], d['ms_per_step'])" ;;
     prof)
       bash scripts/profile_traffic.sh ${TAG}_$(echo $a1 | tr A-Z a-z) --config $a1 > $O/prof_$a1.log 2>&1 ;;
@@ -78,7 +78,7 @@ for step in "$@"; do
       # the driver's N-rank launch on this one GPU: every rank on device 0, gloo (RCCL refuses two
       # ranks on one device); a rehearsal of the code path, not a scaling figure
       MFX_BENCH_DEVICE=0 MFX_BENCH_BACKEND=gloo timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 \
-        --nproc-per-node=$a1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus $a1 --no-cpu-baseline \
+        --nproc-per-node=$a1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus $a1 --no-cpu-baseline \
         --no-stats --steps 5 --warmup 1 > $O/rehearse_$a1.json 2> $O/rehearse_$a1.err
       python3 -c "import json; d=json.load(open('$O/rehearse_$a1.json')); print('rehearse', d['n_gpus'], d['scaling'], d['value'], d['config']['global_spp_per_step'], d['config']['frames_in_flight'])" ;;
     inflight)

@@ -12,7 +12,7 @@ i=0
 for grp in "$@"; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc $grp --output-format csv -d $OUT/p$i -o run -- \
-      python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-stats > $OUT/p$i.log 2>&1 || { echo "pass $i failed" >> $OUT/errors.txt; exit 1; }
+      python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-stats > $OUT/p$i.log 2>&1 || { echo "pass $i failed" >> $OUT/errors.txt; exit 1; }
 done
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections

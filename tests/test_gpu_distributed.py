@@ -214,7 +214,7 @@ def test_bench_multiprocess_path_under_torchrun(gpu, tmp_path):
     env = dict(os.environ, MFX_BENCH_FORCE_DIST="1")
     common = ["--steps", "2", "--warmup", "1", "--spp", "2", "--no-cpu-baseline", "--no-stats", "--no-render-api"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr",
-           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py")] + common
+           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full"] + common
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -251,7 +251,7 @@ def test_bench_two_ranks_rehearsal_under_torchrun(gpu):
     larger sample set."""
     common = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-stats", "--no-render-api"]
     env = dict(os.environ, MFX_BENCH_DEVICE="0", MFX_BENCH_BACKEND="gloo")
-    line = _bench(["--spp", "2"] + common, env=env, torchrun=2)
+    line = _bench(["--full", "--spp", "2"] + common, env=env, torchrun=2)
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"
     assert line["config"]["global_spp_per_step"] == 2 and line["config"]["film_share_per_gpu"] == 0.5
     assert "image partition" in line["config"]["parallelism"]
@@ -278,7 +278,7 @@ def test_bench_merge_check_catches_a_wrong_partition(gpu):
     (MFX_BENCH_FAULT=partition), the 2-rank line reports merged_equals_1gpu false."""
     common = ["--steps", "1", "--warmup", "1", "--spp", "2", "--no-cpu-baseline", "--no-stats", "--no-render-api"]
     env = dict(os.environ, MFX_BENCH_DEVICE="0", MFX_BENCH_BACKEND="gloo", MFX_BENCH_FAULT="partition")
-    line = _bench(common, env=env, torchrun=2)
+    line = _bench(["--full"] + common, env=env, torchrun=2)
     assert line["merged_equals_1gpu"] is False and line["verify"]["max_abs_diff"] > 0
     assert line["verify"]["digest_merged"] != line["verify"]["digest_1gpu"]
 
@@ -290,7 +290,7 @@ def test_bench_single_process_device_list_rehearsal(gpu):
     one-GPU run of the same job."""
     common = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-stats", "--no-render-api"]
     env = dict(os.environ, MFX_BENCH_DEVICE="0")
-    line = _bench(["--spp", "4", "--single-process", "--gpus", "2"] + common, env=env)
+    line = _bench(["--full", "--spp", "4", "--single-process", "--gpus", "2"] + common, env=env)
     one = _bench(["--spp", "4"] + common)
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["rays_per_step"] == one["rays_per_step"]
     assert line["merged_equals_1gpu"] is True
@@ -314,7 +314,7 @@ def test_bench_two_ranks_on_two_devices_over_rccl(gpu):
         pytest.skip("needs 2 GPUs")
     common = ["--steps", "2", "--warmup", "1", "--spp", "2", "--no-cpu-baseline", "--no-stats", "--no-render-api"]
     env = {k: v for k, v in os.environ.items() if k not in ("MFX_BENCH_DEVICE", "MFX_BENCH_BACKEND")}
-    line = _bench(common, env=env, torchrun=2)
+    line = _bench(["--full"] + common, env=env, torchrun=2)
     topo = line["topology"]
     assert topo["backend"] == "nccl" and topo["rccl_world"] == 2 and topo["distinct_devices"] is True
     assert line["merged_equals_1gpu"] is True and line["verify"]["exact_expected"] is True
@@ -330,7 +330,7 @@ def test_bench_single_process_two_devices(gpu):
         pytest.skip("needs 2 GPUs")
     common = ["--steps", "2", "--warmup", "1", "--spp", "4", "--no-cpu-baseline", "--no-stats", "--no-render-api"]
     env = {k: v for k, v in os.environ.items() if k != "MFX_BENCH_DEVICE"}
-    line = _bench(common + ["--single-process", "--gpus", "2"], env=env)
+    line = _bench(["--full"] + common + ["--single-process", "--gpus", "2"], env=env)
     topo = line["topology"]
     assert topo["single_process_devices"] == [0, 1] and topo["communicators"] == 2
     assert topo["library_context"]["merge"] == "rccl_reduce"
