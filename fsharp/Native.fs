@@ -116,6 +116,17 @@ type MfxOptions =
     val mutable renderAhead : int32
     val mutable devices : nativeint
 
+/// mfx_adaptive (32 B): the schedule (2 <= minSpp <= maxSpp, stepSpp >= 1, reserved 0) and the
+/// threshold of mfx_sample_adaptive (relError, absFloor: finite, >= 0)
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type MfxAdaptive =
+    val mutable minSpp : int32
+    val mutable maxSpp : int32
+    val mutable stepSpp : int32
+    val mutable reserved : int32
+    val mutable relError : float
+    val mutable absFloor : float
+
 // ---- entry points --------------------------------------------------------------------------------
 
 module Api =
@@ -125,6 +136,8 @@ module Api =
     extern void mfx_destroy(nativeint ctx)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
     extern int mfx_sample(nativeint ctx, int spp, nativeint frameXmajorRgba)
+    [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
+    extern int mfx_sample_adaptive(nativeint ctx, MfxAdaptive& cfg, nativeint frameXmajorRgba, int[] tileSpp, byte[] rgbaYmajor)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
     extern int mfx_render_rgba8(nativeint ctx, int spp, byte[] rgbaYmajor)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
@@ -298,6 +311,27 @@ type NativePixelIntegrator(shapes : IHitable[], light : INewLight, camera : ICam
     /// (Film.fs:32-34, Scene.fs:315-333) into buffer = byte[w*h*4], y-major RGBA8.
     member this.RenderRgba8(spp : int, buffer : byte[]) =
         check (Api.mfx_render_rgba8(ctx, spp, buffer)) "mfx_render_rgba8"
+    /// Sample with a per-tile early stop (mfx_sample_adaptive; the rule is stated in
+    /// include/mafrix_rt.h): every 8x8 tile gets minSpp samples, then stepSpp more at a time while the
+    /// RMS standard error of its pixels exceeds relError x (|mean luminance| + absFloor), up to maxSpp.
+    /// Returns the integrator's texture (every pixel the mean over its own tile's count) and the
+    /// tiles' sample counts, row-major by tile row (ceil(h/8) rows of ceil(w/8)). The film is untouched;
+    /// the sample counter advances by maxSpp. One device only (a device list is refused).
+    member this.SampleAdaptive(minSpp : int, maxSpp : int, stepSpp : int, relError : float, absFloor : float) =
+        let counts : int[] = Array.zeroCreate (((width + 7) / 8) * ((height + 7) / 8))
+        let mutable cfg = MfxAdaptive()
+        cfg.minSpp <- minSpp
+        cfg.maxSpp <- maxSpp
+        cfg.stepSpp <- stepSpp
+        cfg.reserved <- 0
+        cfg.relError <- relError
+        cfg.absFloor <- absFloor
+        let h = GCHandle.Alloc(data, GCHandleType.Pinned)
+        try
+            check (Api.mfx_sample_adaptive(ctx, &cfg, h.AddrOfPinnedObject(), counts, null)) "mfx_sample_adaptive"
+        finally
+            h.Free()
+        texture, counts
     /// Film.Reset (Film.fs:26-30) of the GPU film.
     member this.Reset() = check (Api.mfx_reset ctx) "mfx_reset"
     /// Rays traced (primary + extension + shadow) and device seconds of the last call.

@@ -201,6 +201,52 @@ int mfx_build_instanced_info(const mfx_scene_desc* scene, const mfx_instance* in
  * running between calls).                                                                  */
 int mfx_sample(mfx_ctx* ctx, int32_t spp, double* frame_xmajor_rgba);
 
+/* ---- adaptive sampling (an extension: the reference gives every pixel the same budget) ------
+ * mfx_sample with a per-tile early stop. Additive in ABI 6.
+ *
+ * Tiles are the film's 8x8 pixel tiles: tiles_x = ceil(w/8), tiles_y = ceil(h/8), tile
+ * T = ty * tiles_x + tx; a tile's valid pixels are those inside the film, m of them (1 <= m <= 64).
+ * For one sample of pixel p let (fx, fy, fz) be the path's radiance (0 for a path with no lit
+ * vertex) and Y = (fx + fy) + fz. Beside the accumulator the call keeps two FP64 planes,
+ * S1_p = sum Y and S2_p = sum Y*Y, summed in sample order, FP64, no contraction. After n samples
+ * of every pixel of a tile:
+ *     v_p = max(0, S2_p - S1_p*S1_p/n) / (n*(n-1))        (variance of the pixel's mean)
+ *     E = sum over valid p of v_p,   M = sum over valid p of S1_p/n
+ *     converged  <=>  E*m <= rel_error^2 * (|M| + abs_floor*m)^2
+ * i.e. the RMS standard error of the tile's pixels is at most rel_error x (the magnitude of the
+ * tile's mean luminance + abs_floor); |M| because the reference's cosine is unclamped and radiance
+ * can be negative. A black tile has E = 0 and converges at the first check.
+ * Schedule: every tile gets min_spp samples and is checked; an unconverged tile gets step_spp more
+ * (clipped so that it never exceeds max_spp) and is checked again; a tile stops at the first check
+ * it passes, or at max_spp. All tiles still active have had the same number of samples: one pass
+ * is one sample range over the list of active tiles.
+ * Samples: a tile that stops at n uses global samples [next_sample, next_sample + n), next_sample
+ * being the running counter mfx_sample advances; the call then advances it by max_spp whatever
+ * the tiles did, so later calls draw samples no pixel has used. A pixel's value is, bit for bit,
+ * the sum in sample order of its samples 0..n-1 divided by n (color / float n).
+ * (E and M are summed across a wave: a decision whose two sides agree to ~1e-9 relative may fall
+ * either way; every pixel is exact for the count its tile got.)                                  */
+typedef struct mfx_adaptive {
+    int32_t min_spp, max_spp, step_spp, reserved; /* 2 <= min <= max, step >= 1, reserved 0 */
+    double rel_error;                             /* >= 0, finite */
+    double abs_floor;                             /* >= 0, finite */
+} mfx_adaptive; /* 32 bytes */
+
+/* frame_xmajor_rgba: per-pixel mean over its tile's count, alpha 1 (layout of mfx_sample);
+ * tile_spp: [tiles_y * tiles_x] the tiles' sample counts, row-major by tile row; rgba_ymajor: the
+ * same mean through ACES -> sqrt -> RGBA8 (layout of mfx_render_rgba8). Each may be NULL.
+ * The call clears and uses the context's accumulator and the two moment planes (allocated at the
+ * first call: a context that never calls this pays nothing); the film (mfx_render_rgba8's state)
+ * is left untouched. Afterwards the accumulator holds per-pixel sums over differing counts, so
+ * mfx_accum_read_mean is meaningless until the next clear. mfx_ray_counts, mfx_stats,
+ * mfx_last_trace_ms, mfx_trace_timing and mfx_ray_counts_total report the sum over the call's passes
+ * (device time: the passes' traces and checks and the final mean). Always the wavefront pipeline.
+ * MFX_E_INVALID: a bad struct or a NULL ctx. MFX_E_STATE: a context with part_count > 1,
+ * MFX_F_ROW_PARTITION, a device list (ndevices > 0) or MFX_F_MEGAKERNEL (adaptive sampling over
+ * several GPUs needs the tiles re-balanced between passes and is not provided).                */
+int mfx_sample_adaptive(mfx_ctx* ctx, const mfx_adaptive* cfg, double* frame_xmajor_rgba, int32_t* tile_spp,
+                        uint8_t* rgba_ymajor);
+
 /* == Film.GetFrame(integrator, spp) + Scene.PostProcessAndToScreenBuffer
  * (Film.fs:18-34, Scene.fs:315-333): adds spp samples per pixel to the film, then writes the
  * progressive mean through ACES -> sqrt -> int(255.99 c) as RGBA8, y-major:

@@ -67,8 +67,15 @@ class MfxInstance(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MfxAdaptive(C.Structure):
+    """mfx_adaptive: the schedule and threshold of mfx_sample_adaptive."""
+    _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("step_spp", C.c_int32), ("reserved", C.c_int32),
+                ("rel_error", C.c_double), ("abs_floor", C.c_double)]
+
+
 assert C.sizeof(MfxPrim) == 104
 assert C.sizeof(MfxInstance) == 48
+assert C.sizeof(MfxAdaptive) == 32
 
 # numpy structured dtype with the same layout as mfx_prim (for building big prim arrays fast)
 PRIM_DTYPE = np.dtype([("kind", "<i4"), ("material", "<i4"), ("p", "<f8", (4, 3))], align=True)
@@ -150,6 +157,7 @@ def _bind(lib, strict: bool = True):
         "mfx_build_instanced_info": (C.c_int, [_P(MfxSceneDesc), _P(MfxInstance), C.c_int32, C.c_int32, _dp, _ip]),
         "mfx_destroy": (None, [C.c_void_p]),
         "mfx_sample": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+        "mfx_sample_adaptive": (C.c_int, [C.c_void_p, _P(MfxAdaptive), _dp, _ip, _P(C.c_uint8)]),
         "mfx_render_rgba8": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint8)]),
         "mfx_accumulate_render_rgba8": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint8)]),
         "mfx_stats": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -189,7 +197,7 @@ def _bind(lib, strict: bool = True):
 
 
 EXPORTED_SYMBOLS = [
-    "mfx_create", "mfx_create_instanced", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
+    "mfx_create", "mfx_create_instanced", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
     "mfx_film_mean", "mfx_stats",
     "mfx_trace_accumulate", "mfx_accum_clear", "mfx_accum_reduce", "mfx_accum_device_ptr", "mfx_accum_attach", "mfx_accum_read_mean",
     "mfx_sync", "mfx_stream", "mfx_ray_counts", "mfx_last_trace_ms", "mfx_trace_timing", "mfx_ray_counts_total", "mfx_closest_hit", "mfx_any_hit", "mfx_ref_leaves",
@@ -206,6 +214,8 @@ def load_library(path: str | None = None, strict: bool = True):
     if _lib is not None and path is None:
         return _lib
     p = path or LIB_PATH
+    if path is None and os.environ.get("MFX_LIB_PATH"):
+        strict = False  # another build under A/B (an older commit's: bench.py against it as the baseline)
     if not os.path.exists(p):
         raise RuntimeError(f"mafrix_rt native library not built: {p} (run __graft_entry__.build())")
     lib = _bind(C.CDLL(p, mode=C.RTLD_GLOBAL), strict)

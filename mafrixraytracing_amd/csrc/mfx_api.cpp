@@ -141,6 +141,14 @@ struct AheadBuf {
     bool reported = false;              // a call has reported the batch's rays and time
 };
 
+// A listed wavefront trace (mfx_sample_adaptive's passes; WfParams tiles / ntiles / mom)
+struct TileList {
+    const int32_t* tiles;  // device: film tile indices, ascending
+    int32_t ntiles;
+    double* mom;           // device: [2][npix] the luminance moments k_resolve adds to
+    int64_t gen_paths;     // paths per generation at most (a multiple of 4096)
+};
+
 // k_resolve's frames mode for a wavefront trace (WfParams film / frames / count0)
 struct FrameMode {
     double* film;     // the film state: read before the first sample, written after the last
@@ -268,14 +276,26 @@ struct mfx_ctx {
     hipEvent_t stage_ev[kStageChunks] = {};  // host_readback: piece i is in h_stage
     hipEvent_t band_ev[kStageChunks] = {};   // mfx_sample's banded readback: band i's mean is computed
     size_t h_stage_bytes = 0;
-    bool rep_valid = false;          // the last call was served from held frames: its stats are rep_*
+    bool rep_valid = false;          // the last call was served from held frames, or was mfx_sample_adaptive
+                                     // (several traces): its stats are rep_*
     double rep_counts[16] = {0};
+    double rep_timing[8] = {0};      // mfx_trace_timing's stage split (mfx_sample_adaptive: summed over its passes; else 0)
     double rep_ms = 0.0;
     bool diag_iter = false;
     bool pooled_stream = false;  // `stream` belongs to the process's pool (process_stream), not to this context
     bool iter_events = true;  // per-iteration HIP events around each launch (mfx_trace_timing's stage split)
 
+    // ---- adaptive sampling (mfx_sample_adaptive); allocated at its first call ----
+    double* d_mom = nullptr;             // [2][npix] per-pixel luminance moments S1, S2
+    int32_t* d_tiles[2] = {nullptr, nullptr};  // [tiles] the active tile list of a pass and the next one's
+    int32_t* d_tile_flags = nullptr;     // [tiles] the check's verdicts (1: the tile goes on)
+    int32_t* d_tile_spp = nullptr;       // [tiles] sample count of every tile
+    int32_t* d_tile_count = nullptr;     // [1] tiles that go on
+    hipEvent_t adp_ev0 = nullptr, adp_ev1 = nullptr;  // around a pass (trace, check) and the mean
+    bool adaptive_check = false;         // MFX_ADAPTIVE_CHECK=1: the host validates every pass's tile list
+
     // ---- multi-device (primary context only) ----
+    bool device_list = false;            // created with a device list (mfx_options.ndevices > 0)
     int api_part_count = 1;              // the caller's partition count (mfx_options.part_count)
     std::vector<mfx_ctx*> peers;         // devices[1..G) of the device list, same host scene
     std::vector<ncclComm_t> comms;       // [G] one RCCL communicator per device, rank g = device g
@@ -336,6 +356,11 @@ static void free_ctx(mfx_ctx* c) {
                     c->d_film, c->d_frame, c->d_rgba, c->d_work, c->d_counters, c->d_counters_total, c->wf_mem, c->d_wfctl, c->d_spill, c->d_vscratch, c->d_albedo, c->d_light, c->d_cam, (void*)c->d_refs, c->d_nodes_h};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
+    for (void* b : {(void*)c->d_mom, (void*)c->d_tiles[0], (void*)c->d_tiles[1], (void*)c->d_tile_flags,
+                    (void*)c->d_tile_spp, (void*)c->d_tile_count})
+        if (b) (void)hipFree(b);
+    for (hipEvent_t e : {c->adp_ev0, c->adp_ev1})
+        if (e) (void)hipEventDestroy(e);
     ahead_free(c);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->sample_copy2) (void)hipStreamDestroy(c->sample_copy2);
@@ -463,6 +488,7 @@ static int ctx_setup(mfx_ctx* c) {
     c->pool_fail_once = getenv("MFX_POOL_FAIL_ONCE") && atoi(getenv("MFX_POOL_FAIL_ONCE")) != 0;
     if (const char* pm = getenv("MFX_POOL")) c->wf_pool_max = std::max<int64_t>(2048, std::min<int64_t>(1 << 28, atoll(pm)));
     c->diag_iter = getenv("MFX_DIAG_ITER") != nullptr;
+    c->adaptive_check = getenv("MFX_ADAPTIVE_CHECK") && atoi(getenv("MFX_ADAPTIVE_CHECK")) != 0;
     if (const char* e = getenv("MFX_ITER_EVENTS")) c->iter_events = atoi(e) != 0 || c->diag_iter;
     if (const char* qf = getenv("MFX_QUEUE_FROM")) c->wf_queue_from = MFX_RAY_QUEUE ? std::max(-2, atoi(qf)) : -1;
     if (const char* qc = getenv("MFX_QCHUNK")) c->wf_qchunk = std::max(64, std::min(WF_CHUNK_MAX, atoi(qc) / 64 * 64));
@@ -673,6 +699,7 @@ static int create_impl(const mfx_scene_desc* scene, const mfx_instance* instance
     };
     init(c, 0);
     c->render_ahead = opt->render_ahead;
+    c->device_list = opt->ndevices > 0;
     int rc = ctx_setup(c);
     if (rc) {
         free_ctx(c);
@@ -948,12 +975,17 @@ static void note_live(mfx_ctx* c, const unsigned long long* h);
 // events e0 / e1 instead of the context's (no per-iteration events), so a batch traced in the
 // background leaves the last call's timing records alone.
 // split != null (mfx_sample, one device): the last generation's resolve in column bands (ResolveSplit).
+// list != null (mfx_sample_adaptive's passes): the trace covers the film tiles list->tiles instead of
+// the device's band, and k_resolve also adds the luminance moments (TileList).
 static int wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, const FrameMode* fm = nullptr,
                     unsigned long long* counters = nullptr, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
-                    ResolveSplit* split = nullptr) {
+                    ResolveSplit* split = nullptr, const TileList* list = nullptr) {
     const int W = c->host.width, H = c->host.height;
     const int brows = band_rows(c);
-    const int64_t per_sample = (int64_t)((W + 7) / 8) * brows * 64;  // the device's band of the film
+    if (list && (fm || split || list->ntiles < 1 || !list->tiles || !list->mom))
+        return fail(MFX_E_INVALID, "wf_trace: bad tile list");
+    // the device's band of the film, or the listed tiles
+    const int64_t per_sample = list ? (int64_t)list->ntiles * 64 : (int64_t)((W + 7) / 8) * brows * 64;
     const int64_t total = per_sample * ns;
     if (total == 0) return fail(MFX_E_STATE, "wf_trace: empty band");
     // generations of whole 64-path windows (one 8x8 tile of one sample each: the camera-ray packets)
@@ -976,7 +1008,9 @@ static int wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, const FrameMode
             cap = c->wf_pool_max;
     }
     while (true) {
-        gen_max = std::min<int64_t>(total, std::max<int64_t>(4096, cap / 4096 * 4096));
+        // (a listed trace: at most the call's first pass per generation, so no later pass grows the pool)
+        const int64_t gcap = list ? std::min(cap, list->gen_paths) : cap;
+        gen_max = std::min<int64_t>(total, std::max<int64_t>(4096, gcap / 4096 * 4096));
         pool = (int32_t)((gen_max + 4095) / 4096 * 4096);  // 64 shards of whole windows
         rc = wf_ensure_pool(c, pool, qf >= 0);
         if (rc != MFX_E_NOMEM || cap <= (1 << 20)) break;
@@ -1021,6 +1055,9 @@ static int wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, const FrameMode
     P.film = fm ? fm->film : nullptr;
     P.frames = fm ? fm->frames : nullptr;
     P.count0 = fm ? fm->count0 : 0.0;
+    P.tiles = list ? list->tiles : nullptr;
+    P.ntiles = list ? list->ntiles : 0;
+    P.mom = list ? list->mom : nullptr;
     const bool stats = (c->flags & MFX_F_COUNT_STATS) != 0;
     P.cam_grid = c->host.inst.empty() ? c->wf_cam_grid : 0;
     if (own_events) c->cam_last = P.cam_grid > 0;
@@ -1280,10 +1317,35 @@ int mfx_accum_reduce(mfx_ctx* c) {
     return rc;
 }
 
+// The stage split of the last wavefront trace, added to out[1..7] from its per-iteration events (which
+// have completed): [2] the closest-hit kernels (k_camera + k_extend), [4] k_shadow (+ memset), summed
+// over iterations; [1] of [2] the k_camera launches (each generation's first iteration when camera
+// rays run as packets), [3] their count; [5], [6] iterations, [7] generations
+static int add_stage_times(mfx_ctx* c, double out[8]) {
+    const int per_gen = std::max(1, c->it_per_gen);
+    for (int it = 0; it < c->it_recorded; ++it) {
+        const hipEvent_t* ev = c->it_ev.data() + 3 * it;
+        float fe = 0.f, fs = 0.f;
+        HIPCHECK(hipEventElapsedTime(&fe, ev[0], ev[1]));
+        HIPCHECK(hipEventElapsedTime(&fs, ev[1], ev[2]));
+        out[2] += fe;
+        out[4] += fs;
+        if (c->cam_last && it % per_gen == 0) {
+            out[1] += fe;
+            out[3] += 1;
+        }
+    }
+    out[5] += c->it_recorded;
+    out[6] += c->it_recorded;
+    out[7] += c->generations;
+    return MFX_OK;
+}
+
 int mfx_trace_timing(mfx_ctx* c, double out[8]) {
     if (!c || !out) return fail(MFX_E_INVALID, "null argument");
-    if (c->rep_valid) {  // a call served from held frames: its batch's device time, no stage split
-        for (int k = 0; k < 8; ++k) out[k] = 0.0;
+    if (c->rep_valid) {  // a call served from held frames: its batch's device time, no stage split;
+                         // mfx_sample_adaptive: the sums over its passes
+        for (int k = 0; k < 8; ++k) out[k] = c->rep_timing[k];
         out[0] = c->rep_ms;
         return MFX_OK;
     }
@@ -1297,25 +1359,9 @@ int mfx_trace_timing(mfx_ctx* c, double out[8]) {
         out[5] = 1;
         out[6] = 1;
     } else {
-        // [2] the closest-hit kernels (k_camera + k_extend), [4] k_shadow (+ memset), summed over
-        // iterations; [1] of [2] the k_camera launches (each generation's first iteration when
-        // camera rays run as packets), [3] their count; the resolve launches make up the rest of [0]
-        const int per_gen = std::max(1, c->it_per_gen);
-        for (int it = 0; it < c->it_recorded; ++it) {
-            const hipEvent_t* ev = c->it_ev.data() + 3 * it;
-            float fe = 0.f, fs = 0.f;
-            HIPCHECK(hipEventElapsedTime(&fe, ev[0], ev[1]));
-            HIPCHECK(hipEventElapsedTime(&fs, ev[1], ev[2]));
-            out[2] += fe;
-            out[4] += fs;
-            if (c->cam_last && it % per_gen == 0) {
-                out[1] += fe;
-                out[3] += 1;
-            }
-        }
-        out[5] = c->it_recorded;
-        out[6] = c->it_recorded;
-        out[7] = c->generations;
+        // the resolve launches make up the rest of [0]
+        rc = add_stage_times(c, out);
+        if (rc) return rc;
     }
     return MFX_OK;
 }
@@ -1873,6 +1919,7 @@ static int ahead_render(mfx_ctx* c, uint8_t* rgba) {
         HIPCHECK(hipStreamSynchronize(d->copy_stream));
     }
     HIPCHECK(hipSetDevice(c->device));
+    for (double& t : c->rep_timing) t = 0.0;
     c->rep_valid = true;
     c->ab_cur = xi;
     c->ab_last_k = k;
@@ -2055,6 +2102,161 @@ int mfx_sample(mfx_ctx* c, int32_t spp, double* frame) {
     rc = mfx_accum_read_mean(c, (double)spp, frame);
     if (rc) return rc;
     return mfx_sync(c);
+}
+
+// ---- adaptive sampling ---------------------------------------------------------------------------
+// mfx_sample with a per-tile early stop (the rule: include/mafrix_rt.h). The host drives one pass at
+// a time: a listed wavefront trace of the active tiles (wf_trace's TileList: `ns` samples from one
+// sample base, k_resolve's moments instance), the tile check and the compaction of the tiles that go
+// on (mfx_wf_tile_check), then a read of the 4-byte active count, which is the pass's only host round
+// trip. The lists ping-pong between two buffers of one entry per tile; the pool is the first pass's
+// (no pass runs larger generations), so it is allocated once. A pixel's samples are summed by its own
+// k_resolve thread in sample order across the passes, so its sum over n samples is mfx_sample(n)'s.
+static int adaptive_alloc(mfx_ctx* c, int64_t ntiles) {
+    if (c->d_mom) return MFX_OK;
+    auto ck = [](hipError_t e) { return e == hipSuccess; };
+    bool ok = ck(hipMalloc((void**)&c->d_mom, 2 * sizeof(double) * (size_t)c->npix));
+    for (int k = 0; k < 2 && ok; ++k) ok = ck(hipMalloc((void**)&c->d_tiles[k], sizeof(int32_t) * (size_t)ntiles));
+    ok = ok && ck(hipMalloc((void**)&c->d_tile_flags, sizeof(int32_t) * (size_t)ntiles));
+    ok = ok && ck(hipMalloc((void**)&c->d_tile_spp, sizeof(int32_t) * (size_t)ntiles));
+    ok = ok && ck(hipMalloc((void**)&c->d_tile_count, 64));
+    ok = ok && ck(hipEventCreate(&c->adp_ev0)) && ck(hipEventCreate(&c->adp_ev1));
+    if (!ok) {
+        (void)hipGetLastError();
+        return fail(MFX_E_NOMEM, "mfx_sample_adaptive: the moment planes and tile lists could not be allocated");
+    }
+    return MFX_OK;
+}
+
+// MFX_ADAPTIVE_CHECK=1 (debug): a pass's list as the device compacted it — n entries, strictly
+// ascending, every one a tile of the film (list_tile_xy, the function the kernels map it with)
+static int adaptive_check_list(mfx_ctx* c, const int32_t* d_list, int32_t n, int32_t prev_n) {
+    const unsigned tiles_x = (unsigned)(c->host.width + 7) / 8, tiles_y = (unsigned)(c->host.height + 7) / 8;
+    if (n < 0 || n > prev_n) return fail(MFX_E_DEVICE, "mfx_sample_adaptive: active tile count out of range");
+    std::vector<int32_t> h((size_t)n);
+    if (n > 0) HIPCHECK(hipMemcpy(h.data(), d_list, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    for (int32_t k = 0; k < n; ++k) {
+        unsigned tx, ty;
+        if (h[k] < 0 || !list_tile_xy((unsigned)h[k], tiles_x, tiles_y, tx, ty) || (k > 0 && h[k] <= h[k - 1]))
+            return fail(MFX_E_DEVICE, "mfx_sample_adaptive: corrupt tile list at entry " + std::to_string(k));
+    }
+    return MFX_OK;
+}
+
+int mfx_sample_adaptive(mfx_ctx* c, const mfx_adaptive* a, double* frame, int32_t* tile_spp, uint8_t* rgba) {
+    if (!c || !a) return fail(MFX_E_INVALID, "mfx_sample_adaptive: null argument");
+    if (a->min_spp < 2 || a->max_spp < a->min_spp || a->step_spp < 1 || a->reserved != 0)
+        return fail(MFX_E_INVALID, "mfx_sample_adaptive: need 2 <= min_spp <= max_spp, step_spp >= 1, reserved 0");
+    if (!(a->rel_error >= 0.0) || !std::isfinite(a->rel_error) || !(a->abs_floor >= 0.0) || !std::isfinite(a->abs_floor))
+        return fail(MFX_E_INVALID, "mfx_sample_adaptive: rel_error and abs_floor must be finite and >= 0");
+    if (c->api_part_count != 1 || (c->flags & MFX_F_ROW_PARTITION) || c->device_list || !c->peers.empty())
+        return fail(MFX_E_STATE, "mfx_sample_adaptive needs one device and the whole film and sample set "
+                                 "(no device list, part_count == 1, no MFX_F_ROW_PARTITION)");
+    if (c->flags & MFX_F_MEGAKERNEL)
+        return fail(MFX_E_STATE, "mfx_sample_adaptive runs the wavefront pipeline (context has MFX_F_MEGAKERNEL)");
+    HIPCHECK(hipSetDevice(c->device));
+    int rc = ahead_break(c);  // it moves the sample sequence past held frames
+    if (rc) return rc;
+    const int W = c->host.width, H = c->host.height;
+    const int64_t nt64 = (int64_t)((W + 7) / 8) * ((H + 7) / 8);
+    const int32_t ntiles = (int32_t)nt64;
+    rc = adaptive_alloc(c, nt64);
+    if (rc) return rc;
+    rc = mfx_accum_clear(c);
+    if (rc) return rc;
+    HIPCHECK(hipMemsetAsync(c->d_mom, 0, 2 * sizeof(double) * (size_t)c->npix, c->stream));
+    HIPCHECK(hipMemsetAsync(c->d_tile_spp, 0, sizeof(int32_t) * (size_t)ntiles, c->stream));
+    {
+        std::vector<int32_t> all((size_t)ntiles);
+        for (int32_t k = 0; k < ntiles; ++k) all[k] = k;
+        HIPCHECK(hipMemcpy(c->d_tiles[0], all.data(), sizeof(int32_t) * (size_t)ntiles, hipMemcpyHostToDevice));
+    }
+    c->rep_valid = false;
+    c->mega_last = false;
+    double counts[16] = {0}, stage[8] = {0}, ms = 0.0;
+    auto lap = [&]() -> int {  // adp_ev0 .. adp_ev1 have completed: add their device time
+        float f = 0.f;
+        HIPCHECK(hipEventElapsedTime(&f, c->adp_ev0, c->adp_ev1));
+        ms += f;
+        return MFX_OK;
+    };
+    const int64_t first = nt64 * 64 * a->min_spp;
+    int32_t active = ntiles, done = 0;
+    int cur = 0;
+    while (active > 0) {
+        const int32_t ns = done == 0 ? a->min_spp : std::min(a->step_spp, a->max_spp - done);
+        TileList L{c->d_tiles[cur], active, c->d_mom, (first + 4095) / 4096 * 4096};
+        HIPCHECK(hipEventRecord(c->adp_ev0, c->stream));
+        HIPCHECK(hipMemsetAsync(c->d_counters, 0, WF_NCTR * WF_SHARDS * sizeof(unsigned long long), c->stream));
+        rc = wf_trace(c, ns, c->next_sample + done, nullptr, nullptr, nullptr, nullptr, nullptr, &L);
+        if (rc) return rc;
+        HIPCHECK(mfx_launch_counters_add(c->d_counters_total, c->d_counters, WF_NCTR * WF_SHARDS, c->stream));
+        done += ns;
+        TileCheckParams K{};
+        K.tiles = c->d_tiles[cur];
+        K.ntiles = active;
+        K.n = done;
+        K.max_spp = a->max_spp;
+        K.width = W;
+        K.height = H;
+        K.rel2 = a->rel_error * a->rel_error;
+        K.abs_floor = a->abs_floor;
+        K.mom = c->d_mom;
+        K.tile_spp = c->d_tile_spp;
+        K.flags = c->d_tile_flags;
+        K.next = c->d_tiles[cur ^ 1];
+        K.next_count = c->d_tile_count;
+        HIPCHECK(mfx_wf_tile_check(K, c->stream));
+        HIPCHECK(hipEventRecord(c->adp_ev1, c->stream));
+        int32_t next_active = 0;
+        HIPCHECK(hipMemcpyAsync(c->h_counters, c->d_counters, WF_NCTR * WF_SHARDS * sizeof(unsigned long long),
+                                hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(hipMemcpyAsync(&next_active, c->d_tile_count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(hipStreamSynchronize(c->stream));
+        sum_counters(c->h_counters, counts);
+        if (c->wf_auto_pending) {  // the context's first wavefront trace settles the automatic queue start
+            note_live(c, c->h_counters);
+            c->wf_auto_pending = false;
+            c->wf_auto_read = true;
+        }
+        rc = lap();
+        if (rc) return rc;
+        rc = add_stage_times(c, stage);
+        if (rc) return rc;
+        if (c->adaptive_check) {
+            rc = adaptive_check_list(c, c->d_tiles[cur ^ 1], next_active, active);
+            if (rc) return rc;
+        }
+        if (next_active < 0 || next_active > active || (done >= a->max_spp && next_active != 0))
+            return fail(MFX_E_DEVICE, "mfx_sample_adaptive: active tile count out of range");
+        active = next_active;
+        cur ^= 1;
+    }
+    c->next_sample += a->max_spp;
+    HIPCHECK(hipEventRecord(c->adp_ev0, c->stream));
+    HIPCHECK(mfx_launch_adaptive_mean(c->d_accum, c->d_tile_spp, W, H, frame ? c->d_frame : nullptr,
+                                      rgba ? c->d_rgba : nullptr, c->stream));
+    HIPCHECK(hipEventRecord(c->adp_ev1, c->stream));
+    if (frame) {
+        rc = host_readback(c, frame, c->d_frame, 4 * sizeof(double) * (size_t)c->npix, c->stream);
+        if (rc) return rc;
+    }
+    if (rgba) {
+        rc = host_readback(c, rgba, c->d_rgba, 4 * (size_t)c->npix, c->stream);
+        if (rc) return rc;
+    }
+    if (tile_spp)
+        HIPCHECK(hipMemcpyAsync(tile_spp, c->d_tile_spp, sizeof(int32_t) * (size_t)ntiles, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    rc = lap();
+    if (rc) return rc;
+    // the call's statistics: the sum over its passes (mfx_ray_counts, mfx_stats, mfx_last_trace_ms)
+    counts[3] = counts[0];
+    for (int k = 0; k < 16; ++k) c->rep_counts[k] = counts[k];
+    for (int k = 0; k < 8; ++k) c->rep_timing[k] = stage[k];
+    c->rep_ms = ms;
+    c->rep_valid = true;
+    return MFX_OK;
 }
 
 // Without render-ahead (or spp != 1): every device traces its band into its accumulator, adds it

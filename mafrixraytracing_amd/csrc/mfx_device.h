@@ -18,6 +18,16 @@ __host__ __device__ inline int band_row_count(int bi, int bc, int tr) {
     return g + (off < tr - g * bc ? 1 : 0);
 }
 
+// Tile list (adaptive sampling): a trace over a list of the film's 8x8 tiles instead of a band of tile
+// rows. An entry is a whole-film tile index T = ty * tiles_x + tx; this is the one place that splits it.
+// False for an index outside the film (a corrupt list): every caller then starts no path and touches
+// no pixel, and the host checks a list with the same function (MFX_ADAPTIVE_CHECK).
+__host__ __device__ inline bool list_tile_xy(unsigned T, unsigned tiles_x, unsigned tiles_y, unsigned& tx, unsigned& ty) {
+    ty = T / tiles_x;
+    tx = T - ty * tiles_x;
+    return ty < tiles_y;
+}
+
 struct TraceParams {
     const MfxNode* nodes;
     const MfxSlot* slots;
@@ -70,6 +80,9 @@ hipError_t mfx_launch_mean_rgb(const double* accum, int64_t npix, double n, doub
                                int64_t p1);
 hipError_t mfx_launch_film_post(const double* accum, double* film, int w, int h, double spp, double frame_count,
                                 int add, uint8_t* rgba, hipStream_t st);
+// adaptive sampling: accum / tile_spp[the pixel's tile] as x-major RGBA doubles (out) and / or posted RGBA8 (rgba)
+hipError_t mfx_launch_adaptive_mean(const double* accum, const int32_t* tile_spp, int w, int h, double* out,
+                                    uint8_t* rgba, hipStream_t st);
 hipError_t mfx_launch_film_mean(const double* film, int64_t npix, double frame_count, double* out, hipStream_t st);
 hipError_t mfx_launch_accum_add(double* dst, const double* src, int64_t n, hipStream_t st);
 hipError_t mfx_launch_counters_add(unsigned long long* total, const unsigned long long* c, int n, hipStream_t st);

@@ -473,6 +473,31 @@ __global__ void film_mean_kernel(const double* __restrict__ film, int64_t npix, 
     out[4 * q + 3] = 1.0;
 }
 
+// Adaptive sampling (mfx_sample_adaptive): a pixel's mean over its own tile's sample count,
+// color / float n with n = tile_spp[tile of the pixel]: x-major RGBA doubles (out) and / or the same
+// mean through PostProcessAndToScreenBuffer as y-major RGBA8 (rgba); either may be null.
+__global__ void adaptive_mean_kernel(const double* __restrict__ accum, const int32_t* __restrict__ tile_spp, int w,
+                                     int h, double* __restrict__ out, uint8_t* __restrict__ rgba) {
+    const int64_t npix = (int64_t)w * h;
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= npix) return;
+    const int x = (int)(q / h), y = (int)(q % h);
+    const double n = (double)tile_spp[(y >> 3) * ((w + 7) >> 3) + (x >> 3)];
+    const double r = accum[q] / n, g = accum[npix + q] / n, b = accum[2 * npix + q] / n;
+    if (out) {
+        double2* o = (double2*)out + 2 * q;
+        o[0] = make_double2(r, g);
+        o[1] = make_double2(b, 1.0);
+    }
+    if (rgba) {
+        uint8_t* o = rgba + ((int64_t)y * w + x) * 4;
+        o[0] = post_byte(r);
+        o[1] = post_byte(g);
+        o[2] = post_byte(b);
+        o[3] = 255;
+    }
+}
+
 // dst += src, element-wise: one device's accumulator added into another's (the in-order device
 // reduce of a context whose device list repeats a device, where RCCL cannot form a communicator)
 __global__ void accum_add_kernel(double* __restrict__ dst, const double* __restrict__ src, int64_t n) {
@@ -589,6 +614,13 @@ hipError_t mfx_launch_film_post(const double* accum, double* film, int w, int h,
     const int64_t npix = (int64_t)w * h;
     hipLaunchKernelGGL(film_post_kernel, dim3(grid_for(npix, 256)), dim3(256), 0, st, accum, film, w, h, spp,
                        frame_count, add, rgba);
+    return hipGetLastError();
+}
+
+hipError_t mfx_launch_adaptive_mean(const double* accum, const int32_t* tile_spp, int w, int h, double* out,
+                                    uint8_t* rgba, hipStream_t st) {
+    hipLaunchKernelGGL(adaptive_mean_kernel, dim3(grid_for((int64_t)w * h, 256)), dim3(256), 0, st, accum, tile_spp, w,
+                       h, out, rgba);
     return hipGetLastError();
 }
 

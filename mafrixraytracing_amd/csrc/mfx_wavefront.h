@@ -174,7 +174,35 @@ struct WfParams {
     int32_t cam_grid;                     // > 0: a generation's camera rays run k_camera (packets) on this grid
     int32_t iter;                         // the iteration (0 = camera rays); k_extend counts its rays per iteration
     int32_t res_tx0, res_ntx;             // k_resolve: only tile columns [res_tx0, res_tx0 + res_ntx) (0: every column)
+    // Tile list (adaptive sampling, mfx_sample_adaptive): ntiles > 0 makes this a trace of the film's
+    // 8x8 tiles tiles[0 .. ntiles) (whole-film indices ty * tiles_x + tx, ascending) instead of a band
+    // of tile rows: per_sample = ntiles * 64 and path_pixel / k_resolve map the trace's tile k to film
+    // tile tiles[k] (list_tile_xy, mfx_device.h). ntiles == 0: the band mapping above.
+    const int32_t* tiles;
+    int32_t ntiles;
+    // k_resolve's moments instance (mom != null; a listed trace always runs it): beside the accumulator
+    // it adds Y = (fx + fy) + fz of every folded path to mom[pixel] and Y * Y to mom[npix + pixel], in
+    // sample order (the per-pixel sums S1 and S2 of the convergence rule, include/mafrix_rt.h)
+    double* mom;
 };
+
+// The adaptive sampler's tile check (k_tile_check: one wave per active tile) and the compaction of the
+// tiles that go on (k_tile_compact). The rule is stated in include/mafrix_rt.h (mfx_sample_adaptive).
+struct TileCheckParams {
+    const int32_t* tiles;   // [ntiles] the pass's active tiles (film tile indices, ascending)
+    int32_t ntiles;
+    int32_t n;              // samples every pixel of these tiles has had
+    int32_t max_spp;        // a tile that has them stops whatever its error
+    int32_t width, height;
+    double rel2;            // rel_error * rel_error
+    double abs_floor;
+    const double* mom;      // [2][w*h] S1, S2
+    int32_t* tile_spp;      // [tiles_y * tiles_x] a stopped tile's sample count
+    int32_t* flags;         // [ntiles] 1: the tile goes on
+    int32_t* next;          // [ntiles] the tiles that go on, ascending (k_tile_compact)
+    int32_t* next_count;    // [1]
+};
+hipError_t mfx_wf_tile_check(const TileCheckParams& C, hipStream_t st);
 
 #ifndef MFX_RAY_QUEUE
 #define MFX_RAY_QUEUE 1  // continuing paths move to dense ray queues after the first vertex (MFX_RAY_QUEUE=0 at run time: in place)

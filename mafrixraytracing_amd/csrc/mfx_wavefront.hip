@@ -284,22 +284,37 @@ __device__ __forceinline__ bool trav_step(Trav& T, const SceneView& S, const ST&
 // Path index of this generation -> (sample, 8x8 pixel tile, pixel), sample-major and
 // tile-coherent. False for the padding indices of edge tiles (no path). A banded
 // trace (image partition) numbers only its own tile rows: its k-th tile row is film tile row
-// band_index + k * band_count, so pixels, keys and samples are the whole-film trace's.
+// band_index + k * band_count, so pixels, keys and samples are the whole-film trace's. A listed
+// trace (LIST: adaptive sampling's active tiles, ascending, P.ntiles > 0 of them) numbers only the
+// list's tiles: per_sample = ntiles * 64 and tile k is film tile P.tiles[k] (list_tile_xy,
+// mfx_device.h). LIST is a template parameter of the kernels, so the band instances carry none of
+// it (as a run-time branch it moved the scratch size of five k_extend / k_shadow instances).
 // PP: WfParams, or k_shadow's LDS copy of the fields it needs (PixParams)
-template <typename PP>
+template <bool LIST, typename PP>
 __device__ __forceinline__ bool path_pixel(const PP& P, int64_t p, int& x, int& y, int64_t& smp) {
     // p = path_base + s: the 64-bit split of path_base is done once per generation on the host
     // (base_smp, base_q), so only 32-bit divisions remain here (base_q + s < 2^32)
     const unsigned tiles_x = (unsigned)(P.width + 7) >> 3;
-    const unsigned per_sample = tiles_x * (unsigned)P.band_rows * 64;  // < 2^31 (film limit)
+    constexpr bool list = LIST;
+    const unsigned per_sample = (list ? (unsigned)P.ntiles : tiles_x * (unsigned)P.band_rows) * 64;  // < 2^31 (film limit)
     const unsigned qs = (unsigned)P.base_q + (unsigned)(p - P.path_base);
     const unsigned ds = qs / per_sample;
     smp = P.base_smp + ds;
     const unsigned q = qs - ds * per_sample;
     const unsigned tile = q >> 6, within = q & 63;
-    const unsigned tyl = tile / tiles_x;
-    const unsigned ty = (unsigned)band_tile_row(P.band_index, P.band_count, (int)tyl);
-    x = (int)((tile - tyl * tiles_x) * 8 + (within & 7));
+    unsigned tx, ty;
+    if (list) {
+        if (!list_tile_xy((unsigned)P.tiles[tile], tiles_x, (unsigned)(P.height + 7) >> 3, tx, ty)) {
+            x = P.width;  // outside the film: no path
+            y = 0;
+            return false;
+        }
+    } else {
+        const unsigned tyl = tile / tiles_x;
+        ty = (unsigned)band_tile_row(P.band_index, P.band_count, (int)tyl);
+        tx = tile - tyl * tiles_x;
+    }
+    x = (int)(tx * 8 + (within & 7));
     y = (int)(ty * 8 + (within >> 3));
     return x < P.width && y < P.height;
 }
@@ -465,7 +480,8 @@ __device__ __forceinline__ VertexSample sample_vertex(const MfxLight& LT, bool o
 // START: the instance for a generation's first iteration when k_camera does not take its camera
 // rays (two-level scenes, MFX_CAMERA_PACKETS=0); only it carries the camera-ray code (GetRay, the
 // path key, the camera's fields), so the bounce instances hold fewer live scalar registers
-template <bool STATS, bool SPILL, int SK, bool Q, bool START = false>
+// LIST: a START instance for a listed trace (adaptive sampling: path_pixel's tile list)
+template <bool STATS, bool SPILL, int SK, bool Q, bool START = false, bool LIST = false>
 __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
     constexpr bool INST = SK == WF_SK_INST, SLDS = SK == WF_SK_SLDS;
     extern __shared__ int lds_all[];
@@ -524,7 +540,7 @@ __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
             // PixelIntegrator.Sample (Integrators.fs:167-169) + GetRay (Camera.fs:134-139)
             int x, y;
             int64_t smp;
-            path_pixel(P, P.path_base + s, x, y, smp);
+            path_pixel<LIST>(P, P.path_base + s, x, y, smp);
             const int64_t pixel = (int64_t)x * P.height + y;  // Color[w,h] x-major
             const int64_t gsample = P.sample_base + P.part_index + smp * P.part_count;
             const uint64_t key = path_key(P.seed, (uint64_t)pixel, (uint64_t)gsample);
@@ -580,7 +596,7 @@ __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
                         int x, y;
                         int64_t smp;
                         // edge-tile padding starts no path (none when 8 divides the film size)
-                        take = !P.tile_padding || path_pixel(P, P.path_base + j, x, y, smp);
+                        take = !P.tile_padding || path_pixel<LIST>(P, P.path_base + j, x, y, smp);
                     }
                     const uint64_t tm = __ballot(take);
                     // entry: slot | camera-ray flag << 31, or slot | lit mask << 28 (lit_in_entry)
@@ -658,7 +674,8 @@ __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
 // loads more than it issues, and the fifth wave fills those waits
 #define MFX_CAM_WAVES 5
 #endif
-template <bool STATS>
+// LIST: the instance for a listed trace (adaptive sampling): a window's tile is one scalar load
+template <bool STATS, bool LIST = false>
 __global__ void __launch_bounds__(256, MFX_CAM_WAVES) k_camera(WfParams P) {
     extern __shared__ int lds_all[];
     const int lane = lane_id();
@@ -706,7 +723,7 @@ __global__ void __launch_bounds__(256, MFX_CAM_WAVES) k_camera(WfParams P) {
         const int j = jw + lane;
         int x = 0, y = 0;
         int64_t smp = 0;
-        path_pixel(P, P.path_base + jw, x, y, smp);  // the window's first slot: its tile's corner
+        path_pixel<LIST>(P, P.path_base + jw, x, y, smp);  // the window's first slot: its tile's corner
         x += lane & 7;
         y += lane >> 3;
         // edge-tile padding starts no path
@@ -773,11 +790,19 @@ __global__ void __launch_bounds__(256, MFX_CAM_WAVES) k_camera(WfParams P) {
 // the fields path_pixel and path_key read, in k_shadow's LDS (after its array pointers): a shading
 // vertex derives its path's key from the slot, and these are not held in scalar registers through
 // the traversal loop
+// (a trace has a band or a tile list, never both: the list pointer takes the band's two words, so the
+// block is the size it was and k_shadow's LDS footprint does not move)
 struct PixParams {
     int64_t path_base, base_q, base_smp, sample_base;
     uint64_t seed;
-    int32_t width, height, band_index, band_count, band_rows, part_index, part_count, pad;
+    int32_t width, height;
+    union {
+        struct { int32_t band_index, band_count; };
+        const int32_t* tiles;  // ntiles > 0
+    };
+    int32_t band_rows, part_index, part_count, ntiles;
 };
+static_assert(sizeof(PixParams) == 72, "PixParams: k_shadow's LDS layout");
 // k_shadow's array pointers in its LDS (after the light)
 struct ShdPtrs {
     double *ox, *oy, *oz, *dx, *dy, *dz, *vei, *vls;
@@ -800,7 +825,8 @@ struct ShdPtrs {
 // k_shadow: shade HIT slots (listed at scan time), trace the vertex's shadow ray, continue or finish
 // ------------------------------------------------------------------------------------------------
 // Q: the instance that reads a ray queue (P.qslot) or writes the next one (P.ncount), MFX_RAY_QUEUE
-template <bool STATS, bool SPILL, int WAVES, int SK, bool Q>
+// LIST: the instances for a listed trace (adaptive sampling: path_pixel's tile list)
+template <bool STATS, bool SPILL, int WAVES, int SK, bool Q, bool LIST = false>
 __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
     constexpr bool INST = SK == WF_SK_INST, SLDS = SK == WF_SK_SLDS;
     extern __shared__ int lds_all[];
@@ -827,10 +853,19 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
     SceneRefs* refs_lds = (SceneRefs*)((PixParams*)((ShdPtrs*)(light_lds + 1) + 1) + 1);
     if (threadIdx.x == 2)  // (from device memory: kernel arguments beside `nodes` would be loaded with it)
         *refs_lds = SceneRefs{(const int32_t*)P.refs_dev[0], (const uint8_t*)P.refs_dev[1]};
-    if (threadIdx.x == 1)
-        *(PixParams*)((ShdPtrs*)(light_lds + 1) + 1) =
-            PixParams{P.path_base, P.base_q, P.base_smp, P.sample_base, P.seed, P.width, P.height, P.band_index,
-                      P.band_count, P.band_rows, P.part_index, P.part_count, 0};
+    if (threadIdx.x == 1) {
+        PixParams px;
+        px.path_base = P.path_base; px.base_q = P.base_q; px.base_smp = P.base_smp; px.sample_base = P.sample_base;
+        px.seed = P.seed; px.width = P.width; px.height = P.height;
+        if (LIST) {
+            px.tiles = P.tiles;
+        } else {
+            px.band_index = P.band_index; px.band_count = P.band_count;
+        }
+        px.band_rows = P.band_rows; px.part_index = P.part_index; px.part_count = P.part_count;
+        px.ntiles = LIST ? P.ntiles : 0;
+        *(PixParams*)((ShdPtrs*)(light_lds + 1) + 1) = px;
+    }
 #if MFX_NODE_F16
     if (P.nodes_h) load_top_nodes_h((float4*)lds_all, P.nodes_h, P.ntop_shd);
     else
@@ -936,7 +971,7 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
                     {
                         int x, y;
                         int64_t smp;
-                        path_pixel(PX, PX.path_base + jr, x, y, smp);
+                        path_pixel<LIST>(PX, PX.path_base + jr, x, y, smp);
                         const int64_t pixel = (int64_t)x * PX.height + y;
                         key = path_key(PX.seed, (uint64_t)pixel, (uint64_t)(PX.sample_base + PX.part_index + smp * PX.part_count));
                     }
@@ -1211,16 +1246,24 @@ __device__ __forceinline__ void fold_path(const WfParams& P, int64_t j, const Pa
 // ------------------------------------------------------------------------------------------------
 // FRAMES: the render-ahead instance (P.film); the accumulator instance carries none of its code
 // (with it, k_resolve took 99 VGPRs instead of 88, 4 waves per SIMD instead of 5, and twice the time)
-template <bool FRAMES>
+// MODE: WF_RES_MOMENTS is the adaptive sampler's instance, of its own for the same reason. It maps a
+// listed trace's tiles (P.ntiles > 0) and adds the luminance moments (P.mom): Y = (fx + fy) + fz and
+// Y * Y per path, in sample order beside the accumulator (a black path's Y is 0: nothing to add).
+#define WF_RES_ACCUM 0
+#define WF_RES_FRAMES 1
+#define WF_RES_MOMENTS 2
+template <int MODE>
 __global__ void __launch_bounds__(256) k_resolve(WfParams P) {
+    constexpr bool FRAMES = MODE == WF_RES_FRAMES, MOM = MODE == WF_RES_MOMENTS;
     __shared__ double alb[3 * WF_RES_MAT_LDS];
     const int nm = P.nmat < WF_RES_MAT_LDS ? P.nmat : WF_RES_MAT_LDS;
     for (int i = threadIdx.x; i < 3 * nm; i += blockDim.x) alb[i] = P.albedo[i];
     __syncthreads();
     const int tiles_x = (P.width + 7) >> 3;
-    const int64_t per_sample = (int64_t)tiles_x * P.band_rows * 64;
+    const bool list = MOM && P.ntiles > 0;
+    const int64_t per_sample = list ? (int64_t)P.ntiles * 64 : (int64_t)tiles_x * P.band_rows * 64;
     int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (P.res_ntx > 0) {  // a band of tile columns (mfx_sample's banded resolve): thread -> its tile's q
+    if (!list && P.res_ntx > 0) {  // a band of tile columns (mfx_sample's banded resolve): thread -> its tile's q
         const int64_t tl = q >> 6;
         if (tl >= (int64_t)P.res_ntx * P.band_rows) return;
         q = ((tl / P.res_ntx) * tiles_x + P.res_tx0 + tl % P.res_ntx) * 64 + (q & 63);
@@ -1228,14 +1271,27 @@ __global__ void __launch_bounds__(256) k_resolve(WfParams P) {
     if (q >= per_sample) return;
     const int64_t tile = q >> 6;
     const int within = (int)(q & 63);
-    const int x = (int)(tile % tiles_x) * 8 + (within & 7);
-    const int y = band_tile_row(P.band_index, P.band_count, (int)(tile / tiles_x)) * 8 + (within >> 3);  // the band's film row
+    int x, y;
+    if (list) {  // the trace's tile -> the film's (an index outside the film touches no pixel)
+        unsigned tx, ty;
+        if (!list_tile_xy((unsigned)P.tiles[tile], (unsigned)tiles_x, (unsigned)(P.height + 7) >> 3, tx, ty)) return;
+        x = (int)tx * 8 + (within & 7);
+        y = (int)ty * 8 + (within >> 3);
+    } else {
+        x = (int)(tile % tiles_x) * 8 + (within & 7);
+        y = band_tile_row(P.band_index, P.band_count, (int)(tile / tiles_x)) * 8 + (within >> 3);  // the band's film row
+    }
     if (x >= P.width || y >= P.height) return;
     const int64_t npix = (int64_t)P.width * P.height;
     const int64_t pixel = (int64_t)x * P.height + y;
     const int64_t end = P.path_base + P.total;
     double* acc = FRAMES ? P.film : P.accum;
     double ax = acc[pixel], ay = acc[npix + pixel], az = acc[2 * npix + pixel];
+    double s1 = 0.0, s2 = 0.0;
+    if (MOM) {
+        s1 = P.mom[pixel];
+        s2 = P.mom[npix + pixel];
+    }
     constexpr int U = WF_RES_SAMPLES;
     for (int64_t smp0 = P.path_base / per_sample; smp0 * per_sample < end; smp0 += U) {
         int64_t jv[U];
@@ -1278,12 +1334,21 @@ __global__ void __launch_bounds__(256) k_resolve(WfParams P) {
                 ax += fx;
                 ay += fy;
                 az += fz;
+                if (MOM) {
+                    const double yl = (fx + fy) + fz;
+                    s1 += yl;
+                    s2 += yl * yl;
+                }
             }
         }
     }
     acc[pixel] = ax;
     acc[npix + pixel] = ay;
     acc[2 * npix + pixel] = az;
+    if (MOM) {
+        P.mom[pixel] = s1;
+        P.mom[npix + pixel] = s2;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1330,21 +1395,29 @@ hipError_t mfx_wf_kernel_occupancy(bool shadow, int stack_lds, bool spill, int n
     return e;
 }
 
-template <bool SPILL, int SK, bool Q, bool START = false>
+template <bool SPILL, int SK, bool Q, bool START = false, bool LIST = false>
 static void launch_extend_q(const WfParams& P, int grid, bool stats, hipStream_t st, size_t lds) {
     if (stats)
-        hipLaunchKernelGGL((k_extend<true, SPILL, SK, Q, START>), dim3(grid), dim3(256), lds, st, P);
+        hipLaunchKernelGGL((k_extend<true, SPILL, SK, Q, START, LIST>), dim3(grid), dim3(256), lds, st, P);
     else
-        hipLaunchKernelGGL((k_extend<false, SPILL, SK, Q, START>), dim3(grid), dim3(256), lds, st, P);
+        hipLaunchKernelGGL((k_extend<false, SPILL, SK, Q, START, LIST>), dim3(grid), dim3(256), lds, st, P);
 }
 template <bool SPILL, int SK>
 static void launch_extend(const WfParams& P, int grid, bool stats, hipStream_t st, size_t lds) {
     if (P.qcount) launch_extend_q<SPILL, SK, true>(P, grid, stats, st, lds);
+    else if (P.start && P.ntiles > 0) launch_extend_q<SPILL, SK, false, true, true>(P, grid, stats, st, lds);
     else if (P.start) launch_extend_q<SPILL, SK, false, true>(P, grid, stats, st, lds);
     else launch_extend_q<SPILL, SK, false>(P, grid, stats, st, lds);
 }
 template <bool SPILL, int WAVES, int SK, bool Q>
 static void launch_shadow_q(const WfParams& P, int grid, bool stats, hipStream_t st, size_t lds) {
+    if (P.ntiles > 0) {  // a listed trace (adaptive sampling)
+        if (stats)
+            hipLaunchKernelGGL((k_shadow<true, SPILL, WAVES, SK, Q, true>), dim3(grid), dim3(256), lds, st, P);
+        else
+            hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q, true>), dim3(grid), dim3(256), lds, st, P);
+        return;
+    }
     if (stats)
         hipLaunchKernelGGL((k_shadow<true, SPILL, WAVES, SK, Q>), dim3(grid), dim3(256), lds, st, P);
     else
@@ -1395,8 +1468,12 @@ static hipError_t launch_iteration(const WfParams& P, int ext_grid, int shd_grid
                                    hipEvent_t* ev, size_t lds_e, size_t lds_s) {
     const bool inst = P.inst != nullptr;
     if (!inst && P.start && P.cam_grid > 0) {  // camera rays as packets
-        if (stats) hipLaunchKernelGGL(k_camera<true>, dim3(P.cam_grid), dim3(256), cam_lds_bytes(P.stack_size), st, P);
-        else hipLaunchKernelGGL(k_camera<false>, dim3(P.cam_grid), dim3(256), cam_lds_bytes(P.stack_size), st, P);
+        const size_t lds_c = cam_lds_bytes(P.stack_size);
+        if (P.ntiles > 0) {  // a listed trace (adaptive sampling)
+            if (stats) hipLaunchKernelGGL((k_camera<true, true>), dim3(P.cam_grid), dim3(256), lds_c, st, P);
+            else hipLaunchKernelGGL((k_camera<false, true>), dim3(P.cam_grid), dim3(256), lds_c, st, P);
+        } else if (stats) hipLaunchKernelGGL(k_camera<true>, dim3(P.cam_grid), dim3(256), lds_c, st, P);
+        else hipLaunchKernelGGL(k_camera<false>, dim3(P.cam_grid), dim3(256), lds_c, st, P);
     } else {
         switch (scene_kind(inst, P.nslot_ext)) {
             case WF_SK_INST: launch_extend_sk<WF_SK_INST>(P, ext_grid, stats, st, lds_e); break;
@@ -1436,8 +1513,88 @@ hipError_t mfx_wf_iteration(const WfParams& P, int ext_grid, int shd_grid, bool 
 }
 
 hipError_t mfx_wf_resolve(const WfParams& P, hipStream_t st) {
+    if (P.mom || P.ntiles > 0) {  // the adaptive sampler's passes: the moments instance (a listed trace runs no other)
+        if (!P.mom || P.film || P.res_ntx > 0) return hipErrorInvalidValue;
+        const int64_t n = P.ntiles > 0 ? (int64_t)P.ntiles * 64 : (int64_t)((P.width + 7) >> 3) * P.band_rows * 64;
+        hipLaunchKernelGGL(k_resolve<WF_RES_MOMENTS>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P);
+        return hipGetLastError();
+    }
     const int64_t per_sample = (int64_t)(P.res_ntx > 0 ? P.res_ntx : (P.width + 7) >> 3) * P.band_rows * 64;
-    if (P.film) hipLaunchKernelGGL(k_resolve<true>, dim3((unsigned)((per_sample + 255) / 256)), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL(k_resolve<false>, dim3((unsigned)((per_sample + 255) / 256)), dim3(256), 0, st, P);
+    if (P.film) hipLaunchKernelGGL(k_resolve<WF_RES_FRAMES>, dim3((unsigned)((per_sample + 255) / 256)), dim3(256), 0, st, P);
+    else hipLaunchKernelGGL(k_resolve<WF_RES_ACCUM>, dim3((unsigned)((per_sample + 255) / 256)), dim3(256), 0, st, P);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Adaptive sampling: the tile check after a pass (the rule: include/mafrix_rt.h, mfx_sample_adaptive)
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// One wave per active tile, a lane per pixel of the tile: v_p = max(0, S2 - S1 * S1 / n) / (n (n - 1))
+// and S1 / n from the lane's moments, E and M summed over the wave, m counted from the valid lanes'
+// ballot; lane 0 decides E m <= rel^2 (|M| + abs_floor m)^2. A tile that stops (converged, or at
+// max_spp) gets its count; flags[k] tells k_tile_compact which entries go on.
+__global__ void __launch_bounds__(256) k_tile_check(TileCheckParams C) {
+    const int k = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    if (k >= C.ntiles) return;
+    const int lane = lane_id();
+    const unsigned tiles_x = (unsigned)(C.width + 7) >> 3, tiles_y = (unsigned)(C.height + 7) >> 3;
+    const int T = C.tiles[k];  // wave-uniform: one scalar load
+    unsigned tx, ty;
+    const bool in_film = list_tile_xy((unsigned)T, tiles_x, tiles_y, tx, ty);
+    const int x = (int)tx * 8 + (lane & 7), y = (int)ty * 8 + (lane >> 3);
+    const bool valid = in_film && x < C.width && y < C.height;
+    const double n = (double)C.n;
+    double v = 0.0, mean = 0.0;
+    if (valid) {
+        const int64_t npix = (int64_t)C.width * C.height;
+        const int64_t pixel = (int64_t)x * C.height + y;
+        const double s1 = C.mom[pixel], s2 = C.mom[npix + pixel];
+        const double d = s2 - s1 * s1 / n;
+        v = (d > 0.0 ? d : 0.0) / (n * (n - 1.0));
+        mean = s1 / n;
+    }
+    const double E = wave_sum(v), M = wave_sum(mean);
+    const int m = __popcll(__ballot(valid));
+    if (lane == 0) {
+        const double md = (double)m;
+        const double t = fabs(M) + C.abs_floor * md;
+        const bool stop = m == 0 || C.n >= C.max_spp || E * md <= C.rel2 * (t * t);
+        if (stop && m > 0) C.tile_spp[T] = C.n;  // (m > 0: T is a tile of the film)
+        C.flags[k] = stop ? 0 : 1;
+    }
+}
+
+// The tiles that go on, in list order (ascending: the camera packets and the resolve's coalescing rely
+// on tile-row coherence). One block; each wave owns a contiguous run of whole 64-entry rounds, counts
+// its flags by ballot, and after the waves' counts are known writes its survivors at their ranks.
+#define WF_COMPACT_WAVES 16
+__global__ void __launch_bounds__(64 * WF_COMPACT_WAVES) k_tile_compact(TileCheckParams C) {
+    __shared__ int wcount[WF_COMPACT_WAVES];
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const int per = ((C.ntiles + WF_COMPACT_WAVES - 1) / WF_COMPACT_WAVES + 63) / 64 * 64;
+    const int lo = min(wave * per, C.ntiles), hi = min(lo + per, C.ntiles);
+    int cnt = 0;
+    for (int i = lo; i < hi; i += 64) cnt += __popcll(__ballot(i + lane < hi && C.flags[i + lane] != 0));
+    if (lane == 0) wcount[wave] = cnt;
+    __syncthreads();
+    int base = 0;
+    for (int w = 0; w < wave; ++w) base += wcount[w];
+    for (int i = lo; i < hi; i += 64) {
+        const bool f = i + lane < hi && C.flags[i + lane] != 0;
+        const uint64_t b = __ballot(f);
+        if (f) C.next[base + __popcll(b & lanes_below())] = C.tiles[i + lane];
+        base += __popcll(b);
+    }
+    if (threadIdx.x == 64 * WF_COMPACT_WAVES - 1) *C.next_count = base;  // the last wave ends at the total
+}
+
+hipError_t mfx_wf_tile_check(const TileCheckParams& C, hipStream_t st) {
+    if (C.ntiles <= 0 || C.n < 2) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_tile_check, dim3((unsigned)((C.ntiles + 3) / 4)), dim3(256), 0, st, C);
+    hipLaunchKernelGGL(k_tile_compact, dim3(1), dim3(64 * WF_COMPACT_WAVES), 0, st, C);
     return hipGetLastError();
 }

@@ -10,7 +10,8 @@ import ctypes as C
 
 import numpy as np
 
-from .abi import (INSTANCING_KEYS, MFX_F_NONE, MFX_F_TWO_LEVEL, MfxInstance, MfxOptions, SceneArrays, check, dptr, iptr, load_library)
+from .abi import (INSTANCING_KEYS, MFX_F_NONE, MFX_F_TWO_LEVEL, MfxAdaptive, MfxInstance, MfxOptions, SceneArrays, check, dptr,
+                  iptr, load_library)
 
 DEFAULT_SEED = 0x4D414652
 DEFAULT_RENDER_AHEAD = 64  # fsharp/Native.fs DefaultRenderAhead: Scene.Render served from batches of 64 samples
@@ -75,6 +76,22 @@ class NativeContext:
         assert frame.dtype == np.float64 and frame.size == self.w * self.h * 4 and frame.flags.c_contiguous
         check(self.lib.mfx_sample(self._h, spp, dptr(frame)), "mfx_sample")
         return frame
+
+    def sample_adaptive(self, min_spp: int, max_spp: int, step_spp: int, rel_error: float, abs_floor: float,
+                        want_rgba: bool = False):
+        """mfx_sample_adaptive: Sample with a per-tile early stop (the rule: include/mafrix_rt.h,
+        mafrixraytracing_amd/adaptive.py). Returns (frame, tile_spp) or (frame, tile_spp, rgba): the
+        (w*h, 4) x-major mean of every pixel over its own tile's sample count, the (tiles_y, tiles_x)
+        int32 counts of the film's 8x8 tiles, and the same mean as y-major RGBA8 (w*h*4 bytes)."""
+        cfg = MfxAdaptive(min_spp=min_spp, max_spp=max_spp, step_spp=step_spp, reserved=0,
+                          rel_error=rel_error, abs_floor=abs_floor)
+        frame = np.empty((self.w * self.h, 4), dtype=np.float64)
+        tiles = np.zeros(((self.h + 7) // 8, (self.w + 7) // 8), dtype=np.int32)
+        rgba = np.empty(self.w * self.h * 4, dtype=np.uint8) if want_rgba else None
+        check(self.lib.mfx_sample_adaptive(self._h, C.byref(cfg), dptr(frame), iptr(tiles),
+                                           rgba.ctypes.data_as(C.POINTER(C.c_uint8)) if want_rgba else None),
+              "mfx_sample_adaptive")
+        return (frame, tiles, rgba) if want_rgba else (frame, tiles)
 
     def render_rgba8(self, spp: int = 1, want_pixels: bool = True, out: np.ndarray | None = None) -> np.ndarray | None:
         """Film.GetFrame(spp) + post into `out` (a uint8 buffer of w*h*4, allocated if None), as
@@ -255,6 +272,10 @@ class NativePixelIntegrator:
 
     def Sample(self, n: int) -> np.ndarray:
         return self._ctx.sample(n)
+
+    def SampleAdaptive(self, minSpp: int, maxSpp: int, stepSpp: int, relError: float, absFloor: float):
+        """fsharp/Native.fs SampleAdaptive: (Color[w,h] x-major, the tiles' sample counts)."""
+        return self._ctx.sample_adaptive(minSpp, maxSpp, stepSpp, relError, absFloor)
 
 
 class Scene:

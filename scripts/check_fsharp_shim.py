@@ -337,7 +337,8 @@ class Checker:
             return ["p8"]  # pointers
 
         for fs, ct in [("MfxPrim", abi.MfxPrim), ("MfxQuadLight", abi.MfxQuadLight), ("MfxPinhole", abi.MfxPinhole),
-                       ("MfxSceneDesc", abi.MfxSceneDesc), ("MfxOptions", abi.MfxOptions)]:
+                       ("MfxSceneDesc", abi.MfxSceneDesc), ("MfxOptions", abi.MfxOptions),
+                       ("MfxAdaptive", abi.MfxAdaptive)]:
             if self.own_type(fs) is None:
                 self.err(f"Native.fs: struct {fs} missing")
             elif flat_fs(fs) != flat_ct(ct):
