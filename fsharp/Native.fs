@@ -127,6 +127,21 @@ type MfxAdaptive =
     val mutable relError : float
     val mutable absFloor : float
 
+/// mfx_denoise_cfg (56 B): iterations 1..8, source (MFX_DN_SRC_HOST = 0: a host frame, MFX_DN_SRC_ACCUM = 1:
+/// the accumulator / count), reserved 0, and the four sigmas of mfx_denoise (finite, >= 0; 0 switches
+/// the term off)
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type MfxDenoiseCfg =
+    val mutable iterations : int32
+    val mutable source : int32
+    val mutable reserved0 : int32
+    val mutable reserved1 : int32
+    val mutable count : float
+    val mutable sigmaNormal : float
+    val mutable sigmaDepth : float
+    val mutable sigmaAlbedo : float
+    val mutable sigmaColor : float
+
 // ---- entry points --------------------------------------------------------------------------------
 
 module Api =
@@ -138,6 +153,10 @@ module Api =
     extern int mfx_sample(nativeint ctx, int spp, nativeint frameXmajorRgba)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
     extern int mfx_sample_adaptive(nativeint ctx, MfxAdaptive& cfg, nativeint frameXmajorRgba, int[] tileSpp, byte[] rgbaYmajor)
+    [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
+    extern int mfx_aov(nativeint ctx, int spp, int64 sampleBase, float[] outXmajor, nativeint ms)
+    [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
+    extern int mfx_denoise(nativeint ctx, MfxDenoiseCfg& cfg, nativeint colorIn, nativeint outXmajorRgba, byte[] rgbaYmajor, nativeint ms)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
     extern int mfx_render_rgba8(nativeint ctx, int spp, byte[] rgbaYmajor)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
@@ -332,6 +351,35 @@ type NativePixelIntegrator(shapes : IHitable[], light : INewLight, camera : ICam
         finally
             h.Free()
         texture, counts
+    /// First-hit features of the film's own camera rays (mfx_aov), averaged over global samples
+    /// sampleBase .. sampleBase + spp - 1: per pixel (i, j) at (i*h + j)*8 the hit normal, hit t, albedo
+    /// and hit fraction. They stay on the GPU as the feature buffers Denoise is guided by.
+    member this.Aov(spp : int, sampleBase : int64) =
+        let features : float[] = Array.zeroCreate (width * height * 8)
+        check (Api.mfx_aov(ctx, spp, sampleBase, features, 0n)) "mfx_aov"
+        features
+    /// Filters the integrator's texture in place with the edge-avoiding a-trous filter (mfx_denoise;
+    /// the rule is stated in include/mafrix_rt.h), guided by the feature buffers of the last Aov call.
+    /// A sigma of 0 switches its term off. One device only (a device list is refused).
+    member this.Denoise(iterations : int, sigmaNormal : float, sigmaDepth : float, sigmaAlbedo : float,
+                        sigmaColor : float) =
+        let mutable dn = MfxDenoiseCfg()
+        dn.iterations <- iterations
+        dn.source <- 0
+        dn.reserved0 <- 0
+        dn.reserved1 <- 0
+        dn.count <- 0.
+        dn.sigmaNormal <- sigmaNormal
+        dn.sigmaDepth <- sigmaDepth
+        dn.sigmaAlbedo <- sigmaAlbedo
+        dn.sigmaColor <- sigmaColor
+        let h = GCHandle.Alloc(data, GCHandleType.Pinned)
+        try
+            let p = h.AddrOfPinnedObject()
+            check (Api.mfx_denoise(ctx, &dn, p, p, null, 0n)) "mfx_denoise"
+        finally
+            h.Free()
+        texture
     /// Film.Reset (Film.fs:26-30) of the GPU film.
     member this.Reset() = check (Api.mfx_reset ctx) "mfx_reset"
     /// Rays traced (primary + extension + shadow) and device seconds of the last call.

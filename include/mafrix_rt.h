@@ -247,6 +247,61 @@ typedef struct mfx_adaptive {
 int mfx_sample_adaptive(mfx_ctx* ctx, const mfx_adaptive* cfg, double* frame_xmajor_rgba, int32_t* tile_spp,
                         uint8_t* rgba_ymajor);
 
+/* ---- feature buffers and denoising (an extension: the reference shows the raw estimate) --------
+ * Additive in ABI 6.
+ *
+ * mfx_aov: first-hit features of the film's own camera rays. For pixel (i, j) and global sample s the
+ * ray is the path's: key pixel i*h + j, draws 0 and 1 of (seed, pixel, s) give u = (i + d0)/w,
+ * v = (j + d1)/h, PinholeCamera.GetRay(u, v), then Bvh.Hit(ray, 1e-6, 99999999.), i.e. the first
+ * vertex mfx_sample would shade. Per pixel, 8 doubles, each summed over s = sample_base ..
+ * sample_base + spp - 1 in sample order from +0.0 (a miss adds nothing), then divided once by
+ * (double)spp:
+ *   [0..2] hit normal (as mfx_closest_hit returns it), [3] hit t, [4..6] albedo of the hit
+ *   primitive's material, [7] 1.0 per hit (the hit fraction).
+ * The planes stay on the device as the context's feature buffers (allocated at the first call: a
+ * context that never calls this pays nothing) and are what mfx_denoise is guided by.
+ * out_xmajor (may be NULL): out[(i*h + j)*8 + k].  ms (may be NULL): device time from HIP events.
+ * Leaves the accumulator, the film, the moment planes, next_sample and every ray counter untouched.
+ * MFX_E_INVALID: NULL ctx, spp < 1, sample_base < 0. MFX_E_STATE: part_count > 1,
+ * MFX_F_ROW_PARTITION or a device list (as mfx_sample_adaptive). Flat and instanced scenes alike. */
+int mfx_aov(mfx_ctx* ctx, int32_t spp, int64_t sample_base, double* out_xmajor, double* ms);
+
+/* mfx_denoise: an edge-avoiding a-trous filter of a colour image, guided by the feature buffers.
+ * C is the current colour (three channels; at first the source image), N, Z, A the feature buffers'
+ * normal [0..2], depth [3] and albedo [4..6];
+ *     d2(a,b) = ((a0-b0)*(a0-b0) + (a1-b1)*(a1-b1)) + (a2-b2)*(a2-b2),    k = [3/8, 1/4, 1/16].
+ * For iteration i = 0 .. iterations-1 with step s = 2^i, for pixel p = (x, y):
+ *   taps q = (x + dx*s, y + dy*s), dy = -2..2 in the outer loop, dx = -2..2 in the inner one; a tap
+ *   outside the film is skipped. g = 1.0, then, in this order, for each term whose sigma is > 0,
+ *   g = g * (1.0 / (1.0 + term)):
+ *     normal:  term = d2(N_p, N_q) / (sn*sn)
+ *     depth:   dz = Z_p - Z_q; den = (sz*sz) * (Z_p*Z_p + Z_q*Z_q); term = den > 0 ? (dz*dz)/den : 0
+ *     albedo:  term = d2(A_p, A_q) / (sa*sa)
+ *     colour:  term = d2(C_p, C_q) / ((sc*sc) * 0.25^i)          (0.25^i: an exact power of two)
+ *   wt = (k[|dx|] * k[|dy|]) * g;  num_c = num_c + wt * C_q[c] and den = den + wt, both from +0.0 in
+ *   tap order;  out_c = num_c / den (the centre tap has g = 1, so den >= 9/64).
+ * The next iteration reads this output. Everything is FP64, one rounding per operation, no
+ * contraction, and the weights are rational (+ - * / only, no exp), so a host statement of the rule
+ * (mafrixraytracing_amd/denoise.py) gives the same bits. With every sigma 0 it is the plain B3-spline
+ * a-trous transform's smoothing. There is no variance term: soft shadow edges, which no feature
+ * marks, blur as iterations grow.                                                                 */
+#define MFX_DN_SRC_HOST  0  /* color_in: a host frame in mfx_sample's layout (alpha ignored) */
+#define MFX_DN_SRC_ACCUM 1  /* the context's accumulator / count (mfx_accum_read_mean's value); color_in NULL */
+typedef struct mfx_denoise_cfg {
+    int32_t iterations;        /* 1..8 */
+    int32_t source;            /* MFX_DN_SRC_* */
+    int32_t reserved[2];       /* 0 */
+    double count;              /* SRC_ACCUM: > 0; SRC_HOST: ignored */
+    double sigma_normal, sigma_depth, sigma_albedo, sigma_color; /* finite, >= 0; 0 switches the term off */
+} mfx_denoise_cfg; /* 56 bytes */
+/* out_xmajor_rgba (mfx_sample's layout, alpha 1.0), rgba_ymajor (ACES -> sqrt -> RGBA8 of it,
+ * mfx_render_rgba8's layout), ms (device time from HIP events): each may be NULL. Changes no context
+ * state but its own two ping-pong colour buffers (allocated at the first call).
+ * MFX_E_INVALID: a NULL ctx or cfg, a bad struct, SRC_HOST with NULL color_in, SRC_ACCUM with
+ * count <= 0. MFX_E_STATE: as mfx_aov, and additionally when mfx_aov has not run on this context. */
+int mfx_denoise(mfx_ctx* ctx, const mfx_denoise_cfg* cfg, const double* color_in,
+                double* out_xmajor_rgba, uint8_t* rgba_ymajor, double* ms);
+
 /* == Film.GetFrame(integrator, spp) + Scene.PostProcessAndToScreenBuffer
  * (Film.fs:18-34, Scene.fs:315-333): adds spp samples per pixel to the film, then writes the
  * progressive mean through ACES -> sqrt -> int(255.99 c) as RGBA8, y-major:

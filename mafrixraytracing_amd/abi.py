@@ -27,6 +27,8 @@ MFX_F_ROW_PARTITION = 64
 MFX_F_IN_FLIGHT = 128
 MFX_INSTANCE_VERBATIM = 1
 MFX_MAX_DEVICES = 64
+MFX_DN_SRC_HOST = 0
+MFX_DN_SRC_ACCUM = 1
 MFX_ABI_VERSION = 6
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -73,9 +75,17 @@ class MfxAdaptive(C.Structure):
                 ("rel_error", C.c_double), ("abs_floor", C.c_double)]
 
 
+class MfxDenoiseCfg(C.Structure):
+    """mfx_denoise_cfg: iterations, source and the four sigmas of mfx_denoise."""
+    _fields_ = [("iterations", C.c_int32), ("source", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("count", C.c_double), ("sigma_normal", C.c_double), ("sigma_depth", C.c_double),
+                ("sigma_albedo", C.c_double), ("sigma_color", C.c_double)]
+
+
 assert C.sizeof(MfxPrim) == 104
 assert C.sizeof(MfxInstance) == 48
 assert C.sizeof(MfxAdaptive) == 32
+assert C.sizeof(MfxDenoiseCfg) == 56
 
 # numpy structured dtype with the same layout as mfx_prim (for building big prim arrays fast)
 PRIM_DTYPE = np.dtype([("kind", "<i4"), ("material", "<i4"), ("p", "<f8", (4, 3))], align=True)
@@ -158,6 +168,8 @@ def _bind(lib, strict: bool = True):
         "mfx_destroy": (None, [C.c_void_p]),
         "mfx_sample": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
         "mfx_sample_adaptive": (C.c_int, [C.c_void_p, _P(MfxAdaptive), _dp, _ip, _P(C.c_uint8)]),
+        "mfx_aov": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp]),
+        "mfx_denoise": (C.c_int, [C.c_void_p, _P(MfxDenoiseCfg), _dp, _dp, _P(C.c_uint8), _dp]),
         "mfx_render_rgba8": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint8)]),
         "mfx_accumulate_render_rgba8": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint8)]),
         "mfx_stats": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -197,7 +209,7 @@ def _bind(lib, strict: bool = True):
 
 
 EXPORTED_SYMBOLS = [
-    "mfx_create", "mfx_create_instanced", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
+    "mfx_create", "mfx_create_instanced", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_aov", "mfx_denoise", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
     "mfx_film_mean", "mfx_stats",
     "mfx_trace_accumulate", "mfx_accum_clear", "mfx_accum_reduce", "mfx_accum_device_ptr", "mfx_accum_attach", "mfx_accum_read_mean",
     "mfx_sync", "mfx_stream", "mfx_ray_counts", "mfx_last_trace_ms", "mfx_trace_timing", "mfx_ray_counts_total", "mfx_closest_hit", "mfx_any_hit", "mfx_ref_leaves",

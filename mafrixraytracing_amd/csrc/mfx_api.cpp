@@ -29,6 +29,7 @@
 
 #include "../../include/mafrix_rt.h"
 #include "mfx_device.h"
+#include "mfx_denoise.h"
 #include "mfx_scene.h"
 #include "mfx_wavefront.h"
 
@@ -294,6 +295,12 @@ struct mfx_ctx {
     hipEvent_t adp_ev0 = nullptr, adp_ev1 = nullptr;  // around a pass (trace, check) and the mean
     bool adaptive_check = false;         // MFX_ADAPTIVE_CHECK=1: the host validates every pass's tile list
 
+    // ---- feature buffers and denoising (mfx_aov, mfx_denoise); allocated at their first calls ----
+    double* d_feat = nullptr;            // [MFX_AOV_PLANES][npix] the feature planes (mfx_aov)
+    double* d_feat_out = nullptr;        // [npix][MFX_AOV_PLANES] staging of mfx_aov's host output
+    double* d_dn[2] = {nullptr, nullptr};  // [3][npix] each: the filter's ping-pong colour buffers
+    hipEvent_t dn_ev0 = nullptr, dn_ev1 = nullptr;  // around either call's kernels
+
     // ---- multi-device (primary context only) ----
     bool device_list = false;            // created with a device list (mfx_options.ndevices > 0)
     int api_part_count = 1;              // the caller's partition count (mfx_options.part_count)
@@ -359,8 +366,10 @@ static void free_ctx(mfx_ctx* c) {
     for (void* b : {(void*)c->d_mom, (void*)c->d_tiles[0], (void*)c->d_tiles[1], (void*)c->d_tile_flags,
                     (void*)c->d_tile_spp, (void*)c->d_tile_count})
         if (b) (void)hipFree(b);
-    for (hipEvent_t e : {c->adp_ev0, c->adp_ev1})
+    for (hipEvent_t e : {c->adp_ev0, c->adp_ev1, c->dn_ev0, c->dn_ev1})
         if (e) (void)hipEventDestroy(e);
+    for (void* b : {(void*)c->d_feat, (void*)c->d_feat_out, (void*)c->d_dn[0], (void*)c->d_dn[1]})
+        if (b) (void)hipFree(b);
     ahead_free(c);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->sample_copy2) (void)hipStreamDestroy(c->sample_copy2);
@@ -2256,6 +2265,153 @@ int mfx_sample_adaptive(mfx_ctx* c, const mfx_adaptive* a, double* frame, int32_
     for (int k = 0; k < 8; ++k) c->rep_timing[k] = stage[k];
     c->rep_ms = ms;
     c->rep_valid = true;
+    return MFX_OK;
+}
+
+// ---- feature buffers and denoising ----------------------------------------------------------------
+// mfx_aov traces the film's own camera rays once more, per lane (k_aov), into eight FP64 planes that
+// stay on the device; mfx_denoise runs one k_atrous launch per iteration between two colour buffers,
+// guided by those planes (the rule: include/mafrix_rt.h). Both launch on the context's stream and
+// touch nothing the trace calls keep: not the accumulator, the film, the moment planes, the sample
+// counter, the ray counters or held render-ahead frames.
+static int dn_whole_film(mfx_ctx* c, const char* who) {
+    if (c->api_part_count != 1 || (c->flags & MFX_F_ROW_PARTITION) || c->device_list || !c->peers.empty())
+        return fail(MFX_E_STATE, std::string(who) + " needs one device and the whole film and sample set "
+                                                    "(no device list, part_count == 1, no MFX_F_ROW_PARTITION)");
+    return MFX_OK;
+}
+
+static int dn_events(mfx_ctx* c) {
+    if (!c->dn_ev0) HIPCHECK(hipEventCreate(&c->dn_ev0));
+    if (!c->dn_ev1) HIPCHECK(hipEventCreate(&c->dn_ev1));
+    return MFX_OK;
+}
+
+static int dn_alloc(mfx_ctx* c, double** p, size_t doubles, const char* who) {
+    if (*p) return MFX_OK;
+    if (hipMalloc((void**)p, sizeof(double) * doubles) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        return fail(MFX_E_NOMEM, std::string(who) + ": its device buffers could not be allocated");
+    }
+    return MFX_OK;
+}
+
+int mfx_aov(mfx_ctx* c, int32_t spp, int64_t sample_base, double* out, double* ms) {
+    if (!c) return fail(MFX_E_INVALID, "mfx_aov: null context");
+    if (spp < 1) return fail(MFX_E_INVALID, "mfx_aov: spp must be >= 1");
+    if (sample_base < 0) return fail(MFX_E_INVALID, "mfx_aov: sample_base must be >= 0");
+    int rc = dn_whole_film(c, "mfx_aov");
+    if (rc) return rc;
+    HIPCHECK(hipSetDevice(c->device));
+    rc = dn_alloc(c, &c->d_feat, (size_t)MFX_AOV_PLANES * (size_t)c->npix, "mfx_aov");
+    if (rc) return rc;
+    if (out) {
+        rc = dn_alloc(c, &c->d_feat_out, (size_t)MFX_AOV_PLANES * (size_t)c->npix, "mfx_aov");
+        if (rc) return rc;
+    }
+    rc = dn_events(c);
+    if (rc) return rc;
+    AovParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.nodes = c->d_nodes;
+    P.slots = c->d_slots;
+    P.slot_ref = c->d_slot_ref;
+    P.ref_blob = c->d_ref_blob;
+    P.shade = c->d_shade;
+    P.inst = c->d_inst;
+    P.cam = c->host.camera;
+    P.seed = c->seed;
+    P.sample_base = sample_base;
+    P.spp = spp;
+    P.width = c->host.width;
+    P.height = c->host.height;
+    P.stack_size = c->stack_size;
+    P.feat = c->d_feat;
+    P.out = out ? c->d_feat_out : nullptr;
+    HIPCHECK(hipEventRecord(c->dn_ev0, c->stream));
+    HIPCHECK(mfx_launch_aov(P, c->stream));
+    HIPCHECK(hipEventRecord(c->dn_ev1, c->stream));
+    if (out) {
+        rc = host_readback(c, out, c->d_feat_out, sizeof(double) * MFX_AOV_PLANES * (size_t)c->npix, c->stream);
+        if (rc) return rc;
+    }
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (ms) {
+        float f = 0.f;
+        HIPCHECK(hipEventElapsedTime(&f, c->dn_ev0, c->dn_ev1));
+        *ms = f;
+    }
+    return MFX_OK;
+}
+
+int mfx_denoise(mfx_ctx* c, const mfx_denoise_cfg* a, const double* color_in, double* out, uint8_t* rgba, double* ms) {
+    if (!c || !a) return fail(MFX_E_INVALID, "mfx_denoise: null argument");
+    if (a->iterations < 1 || a->iterations > 8 || a->reserved[0] != 0 || a->reserved[1] != 0)
+        return fail(MFX_E_INVALID, "mfx_denoise: need 1 <= iterations <= 8 and reserved 0");
+    if (a->source != MFX_DN_SRC_HOST && a->source != MFX_DN_SRC_ACCUM)
+        return fail(MFX_E_INVALID, "mfx_denoise: unknown source");
+    for (double s : {a->sigma_normal, a->sigma_depth, a->sigma_albedo, a->sigma_color})
+        if (!(s >= 0.0) || !std::isfinite(s)) return fail(MFX_E_INVALID, "mfx_denoise: every sigma must be finite and >= 0");
+    if (a->source == MFX_DN_SRC_HOST && !color_in)
+        return fail(MFX_E_INVALID, "mfx_denoise: MFX_DN_SRC_HOST needs color_in");
+    if (a->source == MFX_DN_SRC_ACCUM && !(a->count > 0.0))
+        return fail(MFX_E_INVALID, "mfx_denoise: MFX_DN_SRC_ACCUM needs count > 0");
+    int rc = dn_whole_film(c, "mfx_denoise");
+    if (rc) return rc;
+    if (!c->d_feat) return fail(MFX_E_STATE, "mfx_denoise: no feature buffers (call mfx_aov on this context first)");
+    HIPCHECK(hipSetDevice(c->device));
+    for (int k = 0; k < 2; ++k) {
+        rc = dn_alloc(c, &c->d_dn[k], 3 * (size_t)c->npix, "mfx_denoise");
+        if (rc) return rc;
+    }
+    rc = dn_events(c);
+    if (rc) return rc;
+    const int W = c->host.width, H = c->host.height;
+    if (a->source == MFX_DN_SRC_HOST)  // staged through the x-major frame buffer, before the timed part
+        HIPCHECK(hipMemcpyAsync(c->d_frame, color_in, 4 * sizeof(double) * (size_t)c->npix, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(hipEventRecord(c->dn_ev0, c->stream));
+    if (a->source == MFX_DN_SRC_HOST) HIPCHECK(mfx_launch_dn_from_frame(c->d_frame, c->npix, c->d_dn[0], c->stream));
+    else HIPCHECK(mfx_launch_dn_from_accum(c->d_accum, c->npix, a->count, c->d_dn[0], c->stream));
+    AtrousParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.feat = c->d_feat;
+    P.width = W;
+    P.height = H;
+    P.terms = (a->sigma_normal > 0.0 ? 1 : 0) | (a->sigma_depth > 0.0 ? 2 : 0) | (a->sigma_albedo > 0.0 ? 4 : 0) |
+              (a->sigma_color > 0.0 ? 8 : 0);
+    P.sn2 = a->sigma_normal * a->sigma_normal;
+    P.sz2 = a->sigma_depth * a->sigma_depth;
+    P.sa2 = a->sigma_albedo * a->sigma_albedo;
+    const double sc2 = a->sigma_color * a->sigma_color;
+    double quarter = 1.0;  // 0.25^i
+    int cur = 0;
+    for (int i = 0; i < a->iterations; ++i) {
+        P.src = c->d_dn[cur];
+        P.dst = c->d_dn[cur ^ 1];
+        P.step = 1 << i;
+        P.sc2 = sc2 * quarter;
+        HIPCHECK(mfx_launch_atrous(P, c->stream));
+        quarter = quarter * 0.25;
+        cur ^= 1;
+    }
+    if (out || rgba)
+        HIPCHECK(mfx_launch_dn_post(c->d_dn[cur], W, H, out ? c->d_frame : nullptr, rgba ? c->d_rgba : nullptr, c->stream));
+    HIPCHECK(hipEventRecord(c->dn_ev1, c->stream));
+    if (out) {
+        rc = host_readback(c, out, c->d_frame, 4 * sizeof(double) * (size_t)c->npix, c->stream);
+        if (rc) return rc;
+    }
+    if (rgba) {
+        rc = host_readback(c, rgba, c->d_rgba, 4 * (size_t)c->npix, c->stream);
+        if (rc) return rc;
+    }
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (ms) {
+        float f = 0.f;
+        HIPCHECK(hipEventElapsedTime(&f, c->dn_ev0, c->dn_ev1));
+        *ms = f;
+    }
     return MFX_OK;
 }
 

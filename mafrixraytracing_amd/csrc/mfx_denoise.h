@@ -1,0 +1,53 @@
+// mfx_denoise.h — parameter blocks and launchers of the feature-buffer and denoising kernels
+// (mfx_denoise.hip: mfx_aov, mfx_denoise). A translation unit of its own, so the trace kernels' code
+// objects do not change with it.
+#ifndef MFX_DENOISE_H
+#define MFX_DENOISE_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mfx_layout.h"
+
+#define MFX_AOV_PLANES 8  // normal xyz, hit t, albedo rgb, hit fraction
+
+// k_aov: the first hit of the film's own camera rays, averaged over a sample range
+struct AovParams {
+    const MfxNode* nodes;
+    const MfxSlot* slots;
+    const int32_t* slot_ref;
+    const uint8_t* ref_blob;
+    const MfxShade* shade;
+    const MfxInstance* inst;  // two-level scenes (null for a flat scene)
+    MfxCamera cam;            // by value: scalar-loaded
+    uint64_t seed;
+    int64_t sample_base;      // first global sample
+    int32_t spp;
+    int32_t width, height;
+    int32_t stack_size;       // LDS traversal stack entries per lane
+    double* feat;             // [MFX_AOV_PLANES][w*h], x-major pixels
+    double* out;              // null, or [w*h][MFX_AOV_PLANES] (the caller's layout)
+};
+
+// k_atrous: one iteration of the edge-avoiding a-trous filter (the rule: include/mafrix_rt.h)
+struct AtrousParams {
+    const double* src;   // [3][w*h] the current colour
+    double* dst;         // [3][w*h] the iteration's output
+    const double* feat;  // [MFX_AOV_PLANES][w*h]
+    int32_t width, height;
+    int32_t step;        // 2^i
+    int32_t terms;       // bit 0 normal, 1 depth, 2 albedo, 3 colour: the terms whose sigma is > 0
+    double sn2, sz2, sa2;  // sigma * sigma
+    double sc2;            // (sigma_color * sigma_color) * 0.25^i
+};
+
+hipError_t mfx_launch_aov(const AovParams& P, hipStream_t st);
+hipError_t mfx_launch_atrous(const AtrousParams& P, hipStream_t st);
+// colour planes <- accum / n (mfx_accum_read_mean's value)
+hipError_t mfx_launch_dn_from_accum(const double* accum, int64_t npix, double n, double* dst, hipStream_t st);
+// colour planes <- an x-major RGBA frame (alpha dropped)
+hipError_t mfx_launch_dn_from_frame(const double* frame, int64_t npix, double* dst, hipStream_t st);
+// colour planes -> x-major RGBA doubles (alpha 1.0) and / or posted y-major RGBA8; either may be null
+hipError_t mfx_launch_dn_post(const double* src, int w, int h, double* out, uint8_t* rgba, hipStream_t st);
+
+#endif

@@ -1,0 +1,219 @@
+// mfx_denoise.hip — gfx950 kernels of mfx_aov (first-hit feature buffers of the film's own camera
+// rays) and mfx_denoise (the edge-avoiding a-trous filter they guide). The rule of both is stated in
+// include/mafrix_rt.h and, in numpy, in mafrixraytracing_amd/denoise.py.
+//
+// Compiled with -ffp-contract=off like the rest of the library: every FP64 expression below has one
+// rounding per operation in the order written, so the device gives the host statement's bits. The
+// filter's weights are rational (+ - * / only): no exp whose last bit differs between libraries.
+//
+// A translation unit of its own: the trace kernels' code objects (mfx_kernels.hip, mfx_wavefront.hip)
+// do not change with it.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "mfx_layout.h"
+#include "mfx_denoise.h"
+#include "mfx_trace_common.h"
+
+// ----------------------------------------------------------------------------------------------
+// k_aov: one lane per pixel, x-major (a wave's 64 pixels are 64 consecutive rows of one column, or
+// the end of one column and the start of the next: neighbouring rays), the samples looped in
+// registers. The ray is the path's own camera ray (k_camera / trace_kernel: key pixel x*h + y, draws
+// 0 and 1), the hit Bvh.Hit(ray, 1e-6, 99999999.) by the per-lane walk of closest_kernel.
+// ----------------------------------------------------------------------------------------------
+template <bool INST>
+__global__ void __launch_bounds__(256) k_aov(AovParams P) {
+    extern __shared__ int lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int* stack = lds + wave * P.stack_size * 64 + lane;
+    const int64_t npix = (int64_t)P.width * P.height;
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= npix) return;
+    const SceneView S{P.nodes, P.slots, P.slot_ref, P.ref_blob, P.inst, nullptr, 0};
+    const MfxCamera& CAM = P.cam;
+    const int x = (int)(q / P.height), y = (int)(q - (int64_t)x * P.height);
+    double f[MFX_AOV_PLANES];
+#pragma unroll
+    for (int k = 0; k < MFX_AOV_PLANES; ++k) f[k] = 0.0;
+    for (int32_t s = 0; s < P.spp; ++s) {
+        // PixelIntegrator.Sample (Integrators.fs:166-169) + PinholeCamera.GetRay (Camera.fs:134-139)
+        const uint64_t key = path_key(P.seed, (uint64_t)q, (uint64_t)(P.sample_base + s));
+        uint32_t rn = 0;
+        const double u = ((double)x + rng_next(key, rn)) / (double)P.width;
+        const double v = ((double)y + rng_next(key, rn)) / (double)P.height;
+        const DV target = vadd(vadd(ld3(CAM.topleft), vmul(ld3(CAM.right), u)), vmul(ld3(CAM.down), v));
+        const DV o = ld3(CAM.position);
+        const DV d = vnormalize(vsub(target, o));
+        Best B;
+        Stats st{0, 0, 0};
+        if (!traverse<false, false, INST>(S, o, d, 1e-6, 99999999., stack, B, st)) continue;  // a miss adds nothing
+        const MfxShade sh = P.shade[B.info & MFX_INFO_SHADE_MASK];
+        DV nm;
+        if ((sh.prim_kind & 3) == MFX_KIND_SPHERE)
+            nm = vnormalize(vsub(vadd(o, vmul(d, B.t)), ld3(sh.n)));  // Sphere.fs:39-43
+        else
+            nm = ld3(sh.n);
+        f[0] = f[0] + nm.x;
+        f[1] = f[1] + nm.y;
+        f[2] = f[2] + nm.z;
+        f[3] = f[3] + B.t;
+        f[4] = f[4] + sh.albedo[0];
+        f[5] = f[5] + sh.albedo[1];
+        f[6] = f[6] + sh.albedo[2];
+        f[7] = f[7] + 1.0;
+    }
+    const double n = (double)P.spp;
+#pragma unroll
+    for (int k = 0; k < MFX_AOV_PLANES; ++k) {
+        f[k] = f[k] / n;
+        P.feat[k * npix + q] = f[k];
+    }
+    if (P.out) {
+        double2* o = (double2*)(P.out + MFX_AOV_PLANES * q);
+#pragma unroll
+        for (int k = 0; k < MFX_AOV_PLANES / 2; ++k) o[k] = make_double2(f[2 * k], f[2 * k + 1]);
+    }
+}
+
+// ----------------------------------------------------------------------------------------------
+// k_atrous: one thread per pixel, x-major; colour and features are planes, so a wave's 64 pixels
+// (consecutive y at one x) read every tap as one coalesced run of 64 doubles per plane. No LDS
+// tiling: at steps 1 and 2 neighbouring threads' taps overlap in L1 / L2.
+// ----------------------------------------------------------------------------------------------
+__device__ __forceinline__ double d2(double a0, double a1, double a2, double b0, double b1, double b2) {
+    return ((a0 - b0) * (a0 - b0) + (a1 - b1) * (a1 - b1)) + (a2 - b2) * (a2 - b2);
+}
+
+__global__ void __launch_bounds__(256) k_atrous(AtrousParams P) {
+    const int W = P.width, H = P.height;
+    const int64_t npix = (int64_t)W * H;
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    const int x = (int)(p / H), y = (int)(p - (int64_t)x * H);
+    const double* __restrict__ C0 = P.src;
+    const double* __restrict__ C1 = P.src + npix;
+    const double* __restrict__ C2 = P.src + 2 * npix;
+    const double* __restrict__ F = P.feat;
+    const bool tn = P.terms & 1, tz = P.terms & 2, ta = P.terms & 4, tc = P.terms & 8;
+    const double cp0 = C0[p], cp1 = C1[p], cp2 = C2[p];
+    double np0 = 0, np1 = 0, np2 = 0, zp = 0, ap0 = 0, ap1 = 0, ap2 = 0;
+    if (tn) { np0 = F[p]; np1 = F[npix + p]; np2 = F[2 * npix + p]; }
+    if (tz) zp = F[3 * npix + p];
+    if (ta) { ap0 = F[4 * npix + p]; ap1 = F[5 * npix + p]; ap2 = F[6 * npix + p]; }
+    double n0 = 0.0, n1 = 0.0, n2 = 0.0, den = 0.0;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int yy = y + dy * P.step;
+        if (yy < 0 || yy >= H) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int xx = x + dx * P.step;
+            if (xx < 0 || xx >= W) continue;
+            const int64_t q = (int64_t)xx * H + yy;  // inside the film: 0 <= q < npix
+            const double cq0 = C0[q], cq1 = C1[q], cq2 = C2[q];
+            double g = 1.0;
+            if (tn) {
+                const double term = d2(np0, np1, np2, F[q], F[npix + q], F[2 * npix + q]) / P.sn2;
+                g = g * (1.0 / (1.0 + term));
+            }
+            if (tz) {
+                const double zq = F[3 * npix + q];
+                const double dz = zp - zq;
+                const double dd = P.sz2 * (zp * zp + zq * zq);
+                const double term = dd > 0.0 ? (dz * dz) / dd : 0.0;
+                g = g * (1.0 / (1.0 + term));
+            }
+            if (ta) {
+                const double term = d2(ap0, ap1, ap2, F[4 * npix + q], F[5 * npix + q], F[6 * npix + q]) / P.sa2;
+                g = g * (1.0 / (1.0 + term));
+            }
+            if (tc) {
+                const double term = d2(cp0, cp1, cp2, cq0, cq1, cq2) / P.sc2;
+                g = g * (1.0 / (1.0 + term));
+            }
+            const double kx = dx == 0 ? 0.375 : (dx == 1 || dx == -1) ? 0.25 : 0.0625;
+            const double ky = dy == 0 ? 0.375 : (dy == 1 || dy == -1) ? 0.25 : 0.0625;
+            const double wt = (kx * ky) * g;
+            n0 = n0 + wt * cq0;
+            n1 = n1 + wt * cq1;
+            n2 = n2 + wt * cq2;
+            den = den + wt;
+        }
+    }
+    // the centre tap has g = 1: den >= 9/64
+    P.dst[p] = n0 / den;
+    P.dst[npix + p] = n1 / den;
+    P.dst[2 * npix + p] = n2 / den;
+}
+
+__global__ void k_dn_from_accum(const double* __restrict__ accum, int64_t npix, double n, double* __restrict__ dst) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= npix) return;
+    dst[q] = accum[q] / n;  // color / float n (mean_kernel)
+    dst[npix + q] = accum[npix + q] / n;
+    dst[2 * npix + q] = accum[2 * npix + q] / n;
+}
+
+__global__ void k_dn_from_frame(const double* __restrict__ frame, int64_t npix, double* __restrict__ dst) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= npix) return;
+    const double2* f = (const double2*)frame + 2 * q;
+    const double2 a = f[0], b = f[1];
+    dst[q] = a.x;
+    dst[npix + q] = a.y;
+    dst[2 * npix + q] = b.x;
+}
+
+__global__ void k_dn_post(const double* __restrict__ src, int w, int h, double* __restrict__ out, uint8_t* __restrict__ rgba) {
+    const int64_t npix = (int64_t)w * h;
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= npix) return;
+    const double r = src[q], g = src[npix + q], b = src[2 * npix + q];
+    if (out) {
+        double2* o = (double2*)out + 2 * q;
+        o[0] = make_double2(r, g);
+        o[1] = make_double2(b, 1.0);
+    }
+    if (rgba) {  // PostProcessAndToScreenBuffer (Scene.fs:315-330), y-major
+        const int x = (int)(q / h), y = (int)(q % h);
+        uint8_t* o = rgba + ((int64_t)y * w + x) * 4;
+        o[0] = post_byte(r);
+        o[1] = post_byte(g);
+        o[2] = post_byte(b);
+        o[3] = 255;
+    }
+}
+
+// ----------------------------------------------------------------------------------------------
+// Host-side launchers (called from mfx_api.cpp)
+// ----------------------------------------------------------------------------------------------
+static inline unsigned dn_grid(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
+
+hipError_t mfx_launch_aov(const AovParams& P, hipStream_t st) {
+    const size_t lds = (size_t)4 * P.stack_size * 64 * sizeof(int);  // mfx_launch_query's: a column per lane
+    const dim3 g(dn_grid((int64_t)P.width * P.height, 256));
+    if (P.inst) hipLaunchKernelGGL(k_aov<true>, g, dim3(256), lds, st, P);
+    else hipLaunchKernelGGL(k_aov<false>, g, dim3(256), lds, st, P);
+    return hipGetLastError();
+}
+
+hipError_t mfx_launch_atrous(const AtrousParams& P, hipStream_t st) {
+    hipLaunchKernelGGL(k_atrous, dim3(dn_grid((int64_t)P.width * P.height, 256)), dim3(256), 0, st, P);
+    return hipGetLastError();
+}
+
+hipError_t mfx_launch_dn_from_accum(const double* accum, int64_t npix, double n, double* dst, hipStream_t st) {
+    hipLaunchKernelGGL(k_dn_from_accum, dim3(dn_grid(npix, 256)), dim3(256), 0, st, accum, npix, n, dst);
+    return hipGetLastError();
+}
+
+hipError_t mfx_launch_dn_from_frame(const double* frame, int64_t npix, double* dst, hipStream_t st) {
+    hipLaunchKernelGGL(k_dn_from_frame, dim3(dn_grid(npix, 256)), dim3(256), 0, st, frame, npix, dst);
+    return hipGetLastError();
+}
+
+hipError_t mfx_launch_dn_post(const double* src, int w, int h, double* out, uint8_t* rgba, hipStream_t st) {
+    hipLaunchKernelGGL(k_dn_post, dim3(dn_grid((int64_t)w * h, 256)), dim3(256), 0, st, src, w, h, out, rgba);
+    return hipGetLastError();
+}

@@ -1,0 +1,101 @@
+"""The denoiser's rule on the host (numpy only, no GPU): what mfx_denoise must return, bit for bit, for
+a colour image and the feature buffers mfx_aov gives.
+
+The rule (include/mafrix_rt.h, DESIGN.md "Feature buffers and denoising"). C is the current colour,
+N, Z, A the features' normal [0..2], depth [3] and albedo [4..6];
+
+    d2(a, b) = ((a0-b0)*(a0-b0) + (a1-b1)*(a1-b1)) + (a2-b2)*(a2-b2)        k = [3/8, 1/4, 1/16]
+
+For iteration i = 0 .. iterations-1 with step s = 2^i, for pixel p = (x, y): taps q = (x + dx*s,
+y + dy*s), dy = -2..2 outside, dx = -2..2 inside, a tap outside the film skipped. g = 1.0, then in
+this order, for each term whose sigma is > 0, g = g * (1.0 / (1.0 + term)):
+
+    normal   term = d2(N_p, N_q) / (sn*sn)
+    depth    dz = Z_p - Z_q; den = (sz*sz) * (Z_p*Z_p + Z_q*Z_q); term = (dz*dz)/den if den > 0 else 0
+    albedo   term = d2(A_p, A_q) / (sa*sa)
+    colour   term = d2(C_p, C_q) / ((sc*sc) * 0.25^i)
+
+wt = (k[|dx|] * k[|dy|]) * g; num_c = num_c + wt * C_q[c], den = den + wt, both from +0.0 in tap order;
+out_c = num_c / den. The next iteration reads this output. FP64, one rounding per operation; the
+weights are rational, so numpy and the GPU agree to the bit.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+
+K = (0.375, 0.25, 0.0625)  # the B3 spline's taps 3/8, 1/4, 1/16 at |d| = 0, 1, 2
+
+
+@dataclass(frozen=True)
+class DenoiseConfig:
+    iterations: int = 3
+    sigma_normal: float = 0.1
+    sigma_depth: float = 0.02
+    sigma_albedo: float = 0.05
+    sigma_color: float = 0.0
+
+    def __post_init__(self):
+        if not 1 <= self.iterations <= 8:
+            raise ValueError("need 1 <= iterations <= 8")
+        for s in (self.sigma_normal, self.sigma_depth, self.sigma_albedo, self.sigma_color):
+            if not (np.isfinite(s) and s >= 0):
+                raise ValueError("every sigma must be finite and >= 0")
+
+
+def _d2(a, b):
+    """d2 of two (..., 3) arrays, in the rule's order."""
+    e0, e1, e2 = a[..., 0] - b[..., 0], a[..., 1] - b[..., 1], a[..., 2] - b[..., 2]
+    return (e0 * e0 + e1 * e1) + e2 * e2
+
+
+def reference_denoise(color: np.ndarray, features: np.ndarray, w: int, h: int,
+                      cfg: DenoiseConfig = DenoiseConfig()) -> np.ndarray:
+    """color: (w*h, >=3) x-major (pixel x*h + y; alpha ignored); features: (w*h, >=7) as mfx_aov
+    returns them. Returns the (w*h, 4) filtered image, alpha 1.0. All pixels advance together, one tap
+    at a time: every accumulator takes its additions in tap order (never np.sum, which sums pairwise)."""
+    C = np.array(np.asarray(color, dtype=np.float64)[:, :3]).reshape(w, h, 3)
+    F = np.asarray(features, dtype=np.float64).reshape(w, h, -1)
+    N, Z, A = F[..., 0:3], F[..., 3], F[..., 4:7]
+    sn2 = cfg.sigma_normal * cfg.sigma_normal
+    sz2 = cfg.sigma_depth * cfg.sigma_depth
+    sa2 = cfg.sigma_albedo * cfg.sigma_albedo
+    sc2 = cfg.sigma_color * cfg.sigma_color
+    X, Y = np.meshgrid(np.arange(w), np.arange(h), indexing="ij")
+    quarter = 1.0  # 0.25^i
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for i in range(cfg.iterations):
+            s = 1 << i
+            num = np.zeros((w, h, 3))
+            den = np.zeros((w, h))
+            for dy in range(-2, 3):
+                for dx in range(-2, 3):
+                    xq, yq = X + dx * s, Y + dy * s
+                    ok = (xq >= 0) & (xq < w) & (yq >= 0) & (yq < h)
+                    if not ok.any():
+                        continue
+                    xq, yq = np.clip(xq, 0, w - 1), np.clip(yq, 0, h - 1)  # (a skipped tap's value is unused)
+                    Cq = C[xq, yq]
+                    g = np.ones((w, h))
+                    if cfg.sigma_normal > 0:
+                        g = g * (1.0 / (1.0 + _d2(N, N[xq, yq]) / sn2))
+                    if cfg.sigma_depth > 0:
+                        Zq = Z[xq, yq]
+                        dz = Z - Zq
+                        dd = sz2 * (Z * Z + Zq * Zq)
+                        pos = dd > 0
+                        term = np.where(pos, (dz * dz) / np.where(pos, dd, 1.0), 0.0)
+                        g = g * (1.0 / (1.0 + term))
+                    if cfg.sigma_albedo > 0:
+                        g = g * (1.0 / (1.0 + _d2(A, A[xq, yq]) / sa2))
+                    if cfg.sigma_color > 0:
+                        g = g * (1.0 / (1.0 + _d2(C, Cq) / (sc2 * quarter)))
+                    wt = (K[abs(dx)] * K[abs(dy)]) * g
+                    num = np.where(ok[..., None], num + wt[..., None] * Cq, num)
+                    den = np.where(ok, den + wt, den)
+            C = num / den[..., None]
+            quarter = quarter * 0.25
+    out = np.ones((w * h, 4))
+    out[:, :3] = C.reshape(w * h, 3)
+    return out

@@ -10,8 +10,9 @@ import ctypes as C
 
 import numpy as np
 
-from .abi import (INSTANCING_KEYS, MFX_F_NONE, MFX_F_TWO_LEVEL, MfxAdaptive, MfxInstance, MfxOptions, SceneArrays, check, dptr,
-                  iptr, load_library)
+from .abi import (INSTANCING_KEYS, MFX_DN_SRC_ACCUM, MFX_DN_SRC_HOST, MFX_F_NONE, MFX_F_TWO_LEVEL, MfxAdaptive,
+                  MfxDenoiseCfg, MfxInstance, MfxOptions, SceneArrays, check, dptr, iptr, load_library)
+from .denoise import DenoiseConfig
 
 DEFAULT_SEED = 0x4D414652
 DEFAULT_RENDER_AHEAD = 64  # fsharp/Native.fs DefaultRenderAhead: Scene.Render served from batches of 64 samples
@@ -92,6 +93,38 @@ class NativeContext:
                                            rgba.ctypes.data_as(C.POINTER(C.c_uint8)) if want_rgba else None),
               "mfx_sample_adaptive")
         return (frame, tiles, rgba) if want_rgba else (frame, tiles)
+
+    def aov(self, spp: int, sample_base: int = 0) -> np.ndarray:
+        """mfx_aov: the (w*h, 8) x-major first-hit features of the film's own camera rays, averaged over
+        global samples sample_base .. sample_base + spp - 1: normal xyz, hit t, albedo rgb, hit fraction.
+        They stay on the device as the context's feature buffers (what denoise is guided by)."""
+        out = np.empty((self.w * self.h, 8), dtype=np.float64)
+        ms = C.c_double()
+        check(self.lib.mfx_aov(self._h, spp, sample_base, dptr(out), C.byref(ms)), "mfx_aov")
+        self.last_aov_ms = ms.value
+        return out
+
+    def denoise(self, frame: np.ndarray | None = None, count: float | None = None,
+                cfg: DenoiseConfig = DenoiseConfig(), want_rgba: bool = False):
+        """mfx_denoise: the edge-avoiding a-trous filter (the rule: include/mafrix_rt.h,
+        mafrixraytracing_amd/denoise.py) of `frame` ((w*h, 4) x-major, alpha ignored), or with
+        frame=None of the context's accumulator / count; guided by the feature buffers of the last
+        aov call. Returns the (w*h, 4) filtered frame, or (frame, rgba) with its y-major RGBA8 post."""
+        c = MfxDenoiseCfg(iterations=cfg.iterations, source=MFX_DN_SRC_ACCUM if frame is None else MFX_DN_SRC_HOST,
+                          count=float(count) if count is not None else 0.0, sigma_normal=cfg.sigma_normal,
+                          sigma_depth=cfg.sigma_depth, sigma_albedo=cfg.sigma_albedo, sigma_color=cfg.sigma_color)
+        src = None
+        if frame is not None:
+            src = np.ascontiguousarray(frame, dtype=np.float64)
+            assert src.size == self.w * self.h * 4
+        out = np.empty((self.w * self.h, 4), dtype=np.float64)
+        rgba = np.empty(self.w * self.h * 4, dtype=np.uint8) if want_rgba else None
+        ms = C.c_double()
+        check(self.lib.mfx_denoise(self._h, C.byref(c), dptr(src) if src is not None else None, dptr(out),
+                                   rgba.ctypes.data_as(C.POINTER(C.c_uint8)) if want_rgba else None, C.byref(ms)),
+              "mfx_denoise")
+        self.last_denoise_ms = ms.value
+        return (out, rgba) if want_rgba else out
 
     def render_rgba8(self, spp: int = 1, want_pixels: bool = True, out: np.ndarray | None = None) -> np.ndarray | None:
         """Film.GetFrame(spp) + post into `out` (a uint8 buffer of w*h*4, allocated if None), as

@@ -338,7 +338,7 @@ class Checker:
 
         for fs, ct in [("MfxPrim", abi.MfxPrim), ("MfxQuadLight", abi.MfxQuadLight), ("MfxPinhole", abi.MfxPinhole),
                        ("MfxSceneDesc", abi.MfxSceneDesc), ("MfxOptions", abi.MfxOptions),
-                       ("MfxAdaptive", abi.MfxAdaptive)]:
+                       ("MfxAdaptive", abi.MfxAdaptive), ("MfxDenoiseCfg", abi.MfxDenoiseCfg)]:
             if self.own_type(fs) is None:
                 self.err(f"Native.fs: struct {fs} missing")
             elif flat_fs(fs) != flat_ct(ct):
