@@ -186,7 +186,7 @@ __global__ void k_dn_post(const double* __restrict__ src, int w, int h, double* 
 }
 
 // ----------------------------------------------------------------------------------------------
-// Host-side launchers (called from mfx_api.cpp)
+// Host-side launchers (called from mfx_denoise_api.cpp)
 // ----------------------------------------------------------------------------------------------
 static inline unsigned dn_grid(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 

@@ -1,0 +1,117 @@
+// mfx_denoise_api.cpp — feature buffers and denoising.
+// mfx_aov traces the film's own camera rays once more, per lane (k_aov), into eight FP64 planes that
+// stay on the device; mfx_denoise runs one k_atrous launch per iteration between two colour buffers,
+// guided by those planes (the rule: include/mafrix_rt.h). Both launch on the context's stream and
+// touch nothing the trace calls keep: not the accumulator, the film, the moment planes, the sample
+// counter, the ray counters or held render-ahead frames.
+#include "mfx_ctx.h"
+
+using namespace mfxh;
+
+static int dn_events(mfx_ctx* c) {
+    if (!c->dn.ev0) HIPCHECK(c->dn.ev0.create());
+    if (!c->dn.ev1) HIPCHECK(c->dn.ev1.create());
+    return MFX_OK;
+}
+
+// the call's work has been enqueued: wait for it; ms: its kernels' device time (ev0 .. ev1)
+static int dn_finish(mfx_ctx* c, double* ms) {
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    float f = 0.f;
+    if (ms) HIPCHECK(hipEventElapsedTime(&f, c->dn.ev0, c->dn.ev1));
+    if (ms) *ms = f;
+    return MFX_OK;
+}
+
+static int dn_alloc(DevBuf<double>& p, size_t doubles, const char* who) {
+    if (p) return MFX_OK;
+    if (p.alloc(doubles) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MFX_E_NOMEM, std::string(who) + ": its device buffers could not be allocated");
+    }
+    return MFX_OK;
+}
+
+extern "C" int mfx_aov(mfx_ctx* c, int32_t spp, int64_t sample_base, double* out, double* ms) {
+    if (!c) return fail(MFX_E_INVALID, "mfx_aov: null context");
+    if (spp < 1) return fail(MFX_E_INVALID, "mfx_aov: spp must be >= 1");
+    if (sample_base < 0) return fail(MFX_E_INVALID, "mfx_aov: sample_base must be >= 0");
+    MFX_TRY(whole_film_single_device(c, "mfx_aov"));
+    HIPCHECK(hipSetDevice(c->device));
+    Denoise& dn = c->dn;
+    MFX_TRY(dn_alloc(dn.feat, (size_t)MFX_AOV_PLANES * (size_t)c->npix, "mfx_aov"));
+    if (out) MFX_TRY(dn_alloc(dn.feat_out, (size_t)MFX_AOV_PLANES * (size_t)c->npix, "mfx_aov"));
+    MFX_TRY(dn_events(c));
+    AovParams P;
+    std::memset(&P, 0, sizeof(P));
+    fill_scene_ptrs(c, P);
+    P.cam = c->host.camera;
+    P.seed = c->seed;
+    P.sample_base = sample_base;
+    P.spp = spp;
+    P.width = c->host.width;
+    P.height = c->host.height;
+    P.stack_size = c->stack_size;
+    P.feat = dn.feat;
+    P.out = out ? dn.feat_out.get() : nullptr;
+    HIPCHECK(hipEventRecord(dn.ev0, c->stream));
+    HIPCHECK(mfx_launch_aov(P, c->stream));
+    HIPCHECK(hipEventRecord(dn.ev1, c->stream));
+    if (out) MFX_TRY(host_readback(c, out, dn.feat_out, sizeof(double) * MFX_AOV_PLANES * (size_t)c->npix, c->stream));
+    return dn_finish(c, ms);
+}
+
+extern "C" int mfx_denoise(mfx_ctx* c, const mfx_denoise_cfg* a, const double* color_in, double* out, uint8_t* rgba, double* ms) {
+    if (!c || !a) return fail(MFX_E_INVALID, "mfx_denoise: null argument");
+    if (a->iterations < 1 || a->iterations > 8 || a->reserved[0] != 0 || a->reserved[1] != 0)
+        return fail(MFX_E_INVALID, "mfx_denoise: need 1 <= iterations <= 8 and reserved 0");
+    if (a->source != MFX_DN_SRC_HOST && a->source != MFX_DN_SRC_ACCUM)
+        return fail(MFX_E_INVALID, "mfx_denoise: unknown source");
+    for (double s : {a->sigma_normal, a->sigma_depth, a->sigma_albedo, a->sigma_color})
+        if (!(s >= 0.0) || !std::isfinite(s)) return fail(MFX_E_INVALID, "mfx_denoise: every sigma must be finite and >= 0");
+    if (a->source == MFX_DN_SRC_HOST && !color_in)
+        return fail(MFX_E_INVALID, "mfx_denoise: MFX_DN_SRC_HOST needs color_in");
+    if (a->source == MFX_DN_SRC_ACCUM && !(a->count > 0.0))
+        return fail(MFX_E_INVALID, "mfx_denoise: MFX_DN_SRC_ACCUM needs count > 0");
+    MFX_TRY(whole_film_single_device(c, "mfx_denoise"));
+    Denoise& dn = c->dn;
+    if (!dn.ready()) return fail(MFX_E_STATE, "mfx_denoise: no feature buffers (call mfx_aov on this context first)");
+    HIPCHECK(hipSetDevice(c->device));
+    for (int k = 0; k < 2; ++k) MFX_TRY(dn_alloc(dn.buf[k], 3 * (size_t)c->npix, "mfx_denoise"));
+    MFX_TRY(dn_events(c));
+    const int W = c->host.width, H = c->host.height;
+    if (a->source == MFX_DN_SRC_HOST)  // staged through the x-major frame buffer, before the timed part
+        HIPCHECK(hipMemcpyAsync(c->d_frame, color_in, 4 * sizeof(double) * (size_t)c->npix, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(hipEventRecord(dn.ev0, c->stream));
+    if (a->source == MFX_DN_SRC_HOST) HIPCHECK(mfx_launch_dn_from_frame(c->d_frame, c->npix, dn.buf[0], c->stream));
+    else HIPCHECK(mfx_launch_dn_from_accum(c->d_accum, c->npix, a->count, dn.buf[0], c->stream));
+    AtrousParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.feat = dn.feat;
+    P.width = W;
+    P.height = H;
+    P.terms = (a->sigma_normal > 0.0 ? 1 : 0) | (a->sigma_depth > 0.0 ? 2 : 0) | (a->sigma_albedo > 0.0 ? 4 : 0) |
+              (a->sigma_color > 0.0 ? 8 : 0);
+    P.sn2 = a->sigma_normal * a->sigma_normal;
+    P.sz2 = a->sigma_depth * a->sigma_depth;
+    P.sa2 = a->sigma_albedo * a->sigma_albedo;
+    const double sc2 = a->sigma_color * a->sigma_color;
+    double quarter = 1.0;  // 0.25^i
+    int cur = 0;
+    for (int i = 0; i < a->iterations; ++i) {
+        P.src = dn.buf[cur];
+        P.dst = dn.buf[cur ^ 1];
+        P.step = 1 << i;
+        P.sc2 = sc2 * quarter;
+        HIPCHECK(mfx_launch_atrous(P, c->stream));
+        quarter = quarter * 0.25;
+        cur ^= 1;
+    }
+    if (out || rgba)
+        HIPCHECK(mfx_launch_dn_post(dn.buf[cur], W, H, out ? c->d_frame.get() : nullptr, rgba ? c->d_rgba.get() : nullptr,
+                                    c->stream));
+    HIPCHECK(hipEventRecord(dn.ev1, c->stream));
+    if (out) MFX_TRY(host_readback(c, out, c->d_frame, 4 * sizeof(double) * (size_t)c->npix, c->stream));
+    if (rgba) MFX_TRY(host_readback(c, rgba, c->d_rgba, 4 * (size_t)c->npix, c->stream));
+    return dn_finish(c, ms);
+}

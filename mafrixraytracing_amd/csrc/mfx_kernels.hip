@@ -535,7 +535,7 @@ __global__ void aabb_selftest_kernel(const double* rec, int64_t n, int32_t* out)
 }
 
 // ----------------------------------------------------------------------------------------------
-// Host-side launchers (called from mfx_api.cpp)
+// Host-side launchers (called from the boundary's files: mfx_trace.cpp, mfx_query.cpp, ...)
 // ----------------------------------------------------------------------------------------------
 static inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 

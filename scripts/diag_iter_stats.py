@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-bounce ray counts, node/leaf/primitive visits per ray and kernel times of the wavefront
-(MFX_DIAG_ITER with MFX_F_COUNT_STATS; stderr lines from mfx_api.cpp). Usage: diag_iter_stats.py [SCENE] [SPP]"""
+(MFX_DIAG_ITER with MFX_F_COUNT_STATS; stderr lines from mfx_trace.cpp). Usage: diag_iter_stats.py [SCENE] [SPP]"""
 import os
 import re
 import subprocess
