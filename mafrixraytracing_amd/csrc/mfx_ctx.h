@@ -384,6 +384,7 @@ void fill_scene_ptrs(const mfx_ctx* c, P& p) {
     p.ref_blob = c->d_ref_blob;
     p.shade = c->d_shade;
     p.inst = c->d_inst;
+    p.tslack = c->host.tslack;
 }
 
 // MFX_OK, or MFX_E_STATE for a call that needs one device and the whole film and sample set

@@ -19,6 +19,7 @@ struct AovParams {
     const uint8_t* ref_blob;
     const MfxShade* shade;
     const MfxInstance* inst;  // two-level scenes (null for a flat scene)
+    double tslack;            // MfxHostScene::tslack (SceneView::tslack)
     MfxCamera cam;            // by value: scalar-loaded
     uint64_t seed;
     int64_t sample_base;      // first global sample

@@ -30,7 +30,7 @@ __global__ void __launch_bounds__(256) k_aov(AovParams P) {
     const int64_t npix = (int64_t)P.width * P.height;
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= npix) return;
-    const SceneView S{P.nodes, P.slots, P.slot_ref, P.ref_blob, P.inst, nullptr, 0};
+    const SceneView S{P.nodes, P.slots, P.slot_ref, P.ref_blob, P.inst, nullptr, 0, nullptr, 0, nullptr, P.tslack};
     const MfxCamera& CAM = P.cam;
     const int x = (int)(q / P.height), y = (int)(q - (int64_t)x * P.height);
     double f[MFX_AOV_PLANES];

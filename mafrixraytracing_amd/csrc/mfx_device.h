@@ -50,6 +50,7 @@ struct TraceParams {
     int32_t chunk;                   // path indices a wave takes per atomic
     double* vscratch;                // [max_depth + 1][6][grid * 256] per-lane vertex records (a_v, c_v)
     int32_t waves;                   // the kernel instance: 4 (128-VGPR budget) or 1 (unbounded)
+    double tslack;                   // MfxHostScene::tslack (SceneView::tslack)
 };
 
 struct QueryParams {
@@ -68,6 +69,7 @@ struct QueryParams {
     int64_t n;
     double tmin, tmax;
     int32_t stack_size;
+    double tslack;  // MfxHostScene::tslack (SceneView::tslack)
 };
 
 hipError_t mfx_launch_trace(const TraceParams& P, bool stats, int grid, hipStream_t st);

@@ -36,7 +36,7 @@ __global__ void __launch_bounds__(256, WAVES) trace_kernel(TraceParams P) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     int* stack = lds + wave * P.stack_size * 64 + lane;
-    const SceneView S{P.nodes, P.slots, P.slot_ref, P.ref_blob, P.inst, nullptr, 0};
+    const SceneView S{P.nodes, P.slots, P.slot_ref, P.ref_blob, P.inst, nullptr, 0, nullptr, 0, nullptr, P.tslack};
     const MfxLight& LT = P.light;
     const MfxCamera& CAM = P.cam;
     const int W = P.width, H = P.height;
@@ -251,7 +251,7 @@ __global__ void __launch_bounds__(256) closest_kernel(QueryParams Q) {
     int* stack = lds + wave * Q.stack_size * 64 + lane;
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= Q.n) return;
-    const SceneView S{Q.nodes, Q.slots, Q.slot_ref, Q.ref_blob, Q.inst, nullptr, 0};
+    const SceneView S{Q.nodes, Q.slots, Q.slot_ref, Q.ref_blob, Q.inst, nullptr, 0, nullptr, 0, nullptr, Q.tslack};
     const DV o = ld3(Q.rays + 6 * k), d = ld3(Q.rays + 6 * k + 3);
     Best B;
     Stats st{0, 0, 0};
@@ -284,7 +284,7 @@ __global__ void __launch_bounds__(256) anyhit_kernel(QueryParams Q) {
     int* stack = lds + wave * Q.stack_size * 64 + lane;
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= Q.n) return;
-    const SceneView S{Q.nodes, Q.slots, Q.slot_ref, Q.ref_blob, Q.inst, nullptr, 0};
+    const SceneView S{Q.nodes, Q.slots, Q.slot_ref, Q.ref_blob, Q.inst, nullptr, 0, nullptr, 0, nullptr, Q.tslack};
     const DV o = ld3(Q.rays + 6 * k), d = ld3(Q.rays + 6 * k + 3);
     Best B;
     Stats st{0, 0, 0};
@@ -315,7 +315,7 @@ __global__ void __launch_bounds__(256) anyhit_packet16_kernel(QueryParams Q, uns
     int* stk = lds + (wave * 4 + g) * Q.stack_size * 3;  // per entry: node, mask low, mask high
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool act = k < Q.n;
-    const SceneView S{Q.nodes, Q.slots, Q.slot_ref, Q.ref_blob, Q.inst, nullptr, 0};
+    const SceneView S{Q.nodes, Q.slots, Q.slot_ref, Q.ref_blob, Q.inst, nullptr, 0, nullptr, 0, nullptr, Q.tslack};
     DV o = dv(0, 0, 0), d = dv(0, 0, 1);
     double tmax = 0.0;
     if (act) {
@@ -324,7 +324,7 @@ __global__ void __launch_bounds__(256) anyhit_packet16_kernel(QueryParams Q, uns
         tmax = Q.tmax_per_ray[k];
     }
     const RayF rf = make_rayf(o, d);
-    const float tlim = f_tlim(tmax);
+    const float tlim = f_tlim(tmax + Q.tslack);
     bool alive = act;  // not (yet) found occluded
     bool occ = false;
     uint64_t mask = __ballot(alive) & gbits;  // sub-packet-uniform: its lanes whose test hit `node`

@@ -741,6 +741,23 @@ bool mfx_build_scene(const mfx_scene_desc* d0, MfxHostScene& s, std::string& err
         lf.kinds = 0;
         for (int k = 0; k < lf.count; ++k) lf.kinds |= d->prims[s.ref_indices[lf.first + k]].kind << (2 * k);
     }
+    // ---- tslack (mfx_scene.h): the largest diagonal of a reference leaf none of whose primitives' boxes
+    // is the leaf's own (4e-6 more: directions are unit to 1e-6, Sphere.fs:23)
+    s.tslack = 0.0;
+    for (int c = 0; c < nc; ++c) {
+        if (s.leaf_count[c] < 2) continue;
+        const MfxLeaf& lf = leaves[c];
+        bool own = false;
+        for (int k = 0; k < lf.count; ++k) {
+            const Box& q = pb[s.ref_indices[lf.first + k]];
+            own = own || (q.lo.x == lf.lo[0] && q.lo.y == lf.lo[1] && q.lo.z == lf.lo[2] && q.hi.x == lf.hi[0] &&
+                          q.hi.y == lf.hi[1] && q.hi.z == lf.hi[2]);
+        }
+        if (own) continue;
+        const double diag = len(D3{lf.hi[0] - lf.lo[0], lf.hi[1] - lf.lo[1], lf.hi[2] - lf.lo[2]});
+        if (diag > s.tslack) s.tslack = diag;
+    }
+    s.tslack *= 1.0 + 4e-6;
 
     // ---- camera (Camera.fs:96-133) and light (Light.fs:31-40) -------------------------------
     {

@@ -30,6 +30,13 @@ struct MfxHostScene {
     int32_t bvh_depth = 0;     // longest root-to-leaf path in nodes[]
     int32_t stack_entries = 1; // traversal stack bound: pushes along any root-to-node path
     float eps = 0.f;           // conservative box widening
+    // How far beyond tMax a query's node tests must still enter boxes until its first hit.
+    // A reference leaf whose box is entered before tMax and whose primitives are all hit beyond tMax is
+    // a hit (Triangle.Hit ignores tMax; the leaf's minBy then has no miss key), and the traversal finds
+    // it through one of those primitives' own boxes, which may be entered only after tMax: later than
+    // the leaf's box by at most its diagonal (unit directions), by nothing when one primitive's box is
+    // the leaf's. The largest such distance over the reference leaves, rounded up.
+    double tslack = 0.0;
     // build record (mfx_build_info)
     bool bvh_gpu = false;      // traversal BVH2 built on the GPU (mfx_build.hip)
     bool images_gpu = false;   // and its BVH4 collapse and image layout too (flat scenes)

@@ -246,6 +246,10 @@ struct SceneView {
     const int4* slots_lds;
     int nslot_lds;
     const SceneRefs* refs = nullptr;  // non-null: slot_ref / ref_blob are read from here (LDS)
+    // how far beyond a query's tMax the node tests still enter boxes until the first hit (mfx_scene.h,
+    // MfxHostScene::tslack): a reference leaf entered before tMax whose primitives are all hit beyond it is a
+    // hit (Triangle.Hit ignores tMax), and their own boxes may be entered only after tMax
+    double tslack = 0.0;
 };
 
 // An instance's record: from the kernel's LDS copy when it holds it, else from global memory
@@ -1043,7 +1047,7 @@ template <bool STATS, bool PH, bool UNI>
 __device__ __forceinline__ void packet_walk(const SceneView& S, DV o, DV d, const RayF& rf, uint64_t mask, Best& B,
                                             int* stk, uint64_t* stm, Stats& st, uint32_t& pk_nodes,
                                             uint32_t& pk_slots, uint64_t* ph, const PacketPlanes& pp) {
-    const double tMax = B.t;
+    const double tMax = B.t;  // (camera rays: 99999999., beyond every box, so no SceneView::tslack here)
     float tlim = f_tlim(tMax);
     const int rep = __builtin_ctzll(mask);
     int sp = 0, node = 0;
@@ -1115,7 +1119,7 @@ __device__ bool traverse(const SceneView& S, DV o, DV d, double tMin, double tMa
                          Best& B, Stats& st) {
     B = Best{tMax, -1, -1, false};
     RayF rf = make_rayf(o, d);
-    float tlim = f_tlim(tMax);
+    float tlim = f_tlim(tMax + S.tslack);
     int sp = 0;
     int node = 0;
     int inst = -1, inst_sp = 0;

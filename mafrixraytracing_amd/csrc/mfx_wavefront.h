@@ -96,6 +96,7 @@ struct WfParams {
     const uint8_t* ref_blob;
     const MfxShade* shade;
     const MfxInstance* inst;  // two-level scenes: instances (null for a flat scene)
+    double tslack;            // MfxHostScene::tslack (SceneView::tslack)
     MfxLight light;  // by value: kernel arguments are scalar-loaded, never per-lane gathers (k_resolve)
     const MfxCamera* cam_dev;   // the camera in device memory: k_camera copies it into LDS
 #if MFX_NODE_F16

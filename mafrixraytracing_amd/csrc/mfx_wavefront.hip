@@ -220,7 +220,7 @@ __device__ __forceinline__ void trav_begin(Trav& T, const SceneView& S, DV o, DV
     T.o = o;
     T.d = d;
     T.tmax64 = tmax;
-    T.B = Best{tmax, -1, -1, false};
+    T.B = Best{tmax + S.tslack, -1, -1, false};  // B.t is the node tests' limit until the first hit
     T.sp = 0;
     T.node = 0;
     T.inst = -1;
@@ -248,7 +248,7 @@ __device__ __forceinline__ bool trav_step(Trav& T, const SceneView& S, const ST&
     // the FP32 ray and the node-test limit are recomputed each round (the same values) rather than
     // held through the leaf tests: fewer live registers, fewer spills (+1 to +5 %)
     rf = INST ? frame_ray(S, T.inst, T.o, T.d) : make_rayf(T.o, T.d);
-    const float tlim = f_tlim(T.B.t);  // the query's tMax until the first hit, then the best t
+    const float tlim = f_tlim(T.B.t);  // the query's tMax + tslack until the first hit (trav_begin), then the best t
     while (T.node >= 0) {
         if (STATS) st.nodes++;
 #ifdef MFX_DIAG_OCCLUSION
@@ -507,7 +507,7 @@ __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
     const Stack stack = make_stack<SPILL>(lds + wave * P.stack_lds_ext * 64 + lane, P, P.stack_lds_ext);
     int* pend = lds + 4 * P.stack_lds_ext * 64 + wave * WF_EXT_PEND;
     uint32_t* red = (uint32_t*)(lds + 4 * P.stack_lds_ext * 64 + 4 * WF_EXT_PEND);
-    const SceneView S{P.nodes, P.slots, P.slot_ref, P.ref_blob, P.inst, inst_lds, INST ? P.ninst_lds : 0, slot_lds, nslot};
+    const SceneView S{P.nodes, P.slots, P.slot_ref, P.ref_blob, P.inst, inst_lds, INST ? P.ninst_lds : 0, slot_lds, nslot, nullptr, P.tslack};
     const int shard_size = P.pool / WF_SHARDS;
 
     Scanner sc{};
@@ -883,7 +883,7 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
     using Stack = typename std::conditional<SPILL, SpillStack, LdsStack>::type;
     const Stack stack = make_stack<SPILL>(lds + wave * P.stack_lds_shd * 64 + lane, P, P.stack_lds_shd);
     const PendShd pd(pend_base + wave * PendShd::BYTES);
-    const SceneView S{P.nodes, P.slots, nullptr, nullptr, P.inst, inst_lds, INST ? P.ninst_lds : 0, slot_lds, nslot, refs_lds};
+    const SceneView S{P.nodes, P.slots, nullptr, nullptr, P.inst, inst_lds, INST ? P.ninst_lds : 0, slot_lds, nslot, refs_lds, P.tslack};
     const int shard_size = P.pool / WF_SHARDS;
 
     int* shl = (int*)(red + 16) + wave * 2 * WF_SHD_LIST;  // shade list: [0,128) path slots, [128,256) shade indices

@@ -9,16 +9,12 @@ _features = {}
 _frames = {}
 
 
-def oracle_features(oracle, name, w, h, spp, base):
-    """(w*h, 8) x-major: for pixel (i, j) and global sample s the path's own camera ray (key pixel
-    i*h + j, draws 0 and 1 -> u, v -> PinholeCamera.GetRay) and its Bvh.Hit; normal, t, the hit
-    primitive's material's albedo and 1.0 per hit, summed in sample order from +0.0 (a miss adds
-    nothing), divided once by float(spp). Computed once per case and left unchanged."""
-    world = name.replace("@2l", "")  # the same world scene however it is traced
-    key = (world, w, h, spp, base)
-    if key in _features:
-        return _features[key]
-    a = scene(world, w, h)
+def scene_features(oracle, a, spp, base):
+    """(w*h, 8) x-major features of a SceneArrays: for pixel (i, j) and global sample s the path's own
+    camera ray (key pixel i*h + j, draws 0 and 1 -> u, v -> PinholeCamera.GetRay) and its Bvh.Hit;
+    normal, t, the hit primitive's material's albedo and 1.0 per hit, summed in sample order from +0.0
+    (a miss adds nothing), divided once by float(spp)."""
+    w, h = a.width, a.height
     cam = a.camera
     o = oracle.OracleScene(a)
     acc = np.zeros((w * h, 8))
@@ -36,7 +32,16 @@ def oracle_features(oracle, name, w, h, spp, base):
         alb = a.albedo[a.prims["material"][np.where(hit, prim, 0)]]
         add = np.concatenate([nrm, t[:, None], alb, np.ones((w * h, 1))], axis=1)
         acc = np.where(hit[:, None], acc + add, acc)
-    f = acc / float(spp)
+    return acc / float(spp)
+
+
+def oracle_features(oracle, name, w, h, spp, base):
+    """scene_features of scenes/<name>.xml at w x h. Computed once per case and left unchanged."""
+    world = name.replace("@2l", "")  # the same world scene however it is traced
+    key = (world, w, h, spp, base)
+    if key in _features:
+        return _features[key]
+    f = scene_features(oracle, scene(world, w, h), spp, base)
     f.setflags(write=False)
     _features[key] = f
     return f
