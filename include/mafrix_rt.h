@@ -452,6 +452,24 @@ int mfx_aabb_selftest(int32_t device, int64_t n, const double* rec, int32_t* out
  * band_index), out[5 + g] = device g's HIP ordinal. cap = entries of out (>= 5 + G).          */
 int mfx_device_info(mfx_ctx* ctx, int32_t* out, int32_t cap);
 
+/* The launch shape the context's creation chose for its wavefront kernels and the megakernel (ABI 6,
+ * additive): which template instances run and on what grids, the MFX_* tuning variables applied
+ * and clamped. cap = entries of out (>= MFX_LAUNCH_INFO_N). The primary device's values:
+ * out[0] = traversal-stack bound (entries per lane), out[1] / out[2] = of which in LDS in k_extend /
+ * k_shadow, out[3] / out[4] = 1 if k_extend / k_shadow run their spill instances (deeper entries in
+ * a global column), out[5] / out[6] = top BVH nodes in LDS (k_extend / k_shadow), out[7] / out[8] =
+ * slots in LDS (> 0: the small-scene instances), out[9] = instance records in LDS (two-level
+ * scenes; the others are read from global memory), out[10] = k_shadow's build (3 or 4 waves per
+ * SIMD), out[11] = the megakernel's (1 or 4), out[12] = 1 if a HIT state word carries the lit mask,
+ * out[13] = 1 if a lit vertex's direct term is recorded as one double (a gray light), out[14] = 1 if
+ * camera rays run as packets, out[15] / out[16] / out[17] = blocks of k_extend / k_shadow / k_camera
+ * (0: no packets), out[18] = the spill buffer's entries per lane, out[19] = the lanes it holds,
+ * out[20] = slots per chunk fetch, out[21] = 1 if k_shadow takes half chunks on small frames,
+ * out[22] = the first iteration that moves paths to a ray queue (-1 never, -2 automatic),
+ * out[23] = path slots of the pool at most (saturated at 2^31 - 1).                           */
+#define MFX_LAUNCH_INFO_N 24
+int mfx_launch_info(mfx_ctx* ctx, int32_t* out, int32_t cap);
+
 /* ---- misc -------------------------------------------------------------------------------- */
 const char* mfx_last_error(void);
 int mfx_abi_version(void);

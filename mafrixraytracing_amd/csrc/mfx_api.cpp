@@ -314,6 +314,8 @@ static int ctx_setup(mfx_ctx* c) {
         const size_t lanes = (size_t)std::max(c->wf_ext_grid, c->wf_shd_grid) * 256;
         const int deep = c->stack_size - std::min(A.stack_lds_ext, A.stack_lds_shd);
         CK(c->d_spill.alloc(lanes * std::max(1, deep)));
+        c->spill_deep = std::max(1, deep);
+        c->spill_lanes = (int)lanes;
     }
     CK(c->d_vscratch.alloc(6 * (size_t)(c->host.max_depth + 1) * c->grid * 256));
 #undef CK
@@ -563,6 +565,21 @@ int mfx_device_info(mfx_ctx* c, int32_t* out, int32_t cap) {
     out[3] = c->band_index;
     out[4] = c->band_count;
     for (size_t g = 0; g < ds.size(); ++g) out[5 + g] = ds[g]->device;
+    return MFX_OK;
+}
+
+int mfx_launch_info(mfx_ctx* c, int32_t* out, int32_t cap) {
+    if (!c || !out) return fail(MFX_E_INVALID, "null argument");
+    if (cap < MFX_LAUNCH_INFO_N) return fail(MFX_E_INVALID, "mfx_launch_info: cap < MFX_LAUNCH_INFO_N");
+    const WfParams& A = c->pool.params;
+    const bool inst = !c->host.inst.empty();
+    const int32_t v[MFX_LAUNCH_INFO_N] = {
+        c->stack_size, A.stack_lds_ext, A.stack_lds_shd, A.stack_lds_ext < c->stack_size, A.stack_lds_shd < c->stack_size,
+        A.ntop_ext, A.ntop_shd, A.nslot_ext, A.nslot_shd, inst ? std::min<int>((int)c->host.inst.size(), WF_INST_LDS) : 0,
+        A.shadow_waves, c->mega_waves, wf_lit_in_hit(c), wf_gray_light(c), !inst && c->wf_cam_grid > 0,
+        c->wf_ext_grid, c->wf_shd_grid, inst ? 0 : c->wf_cam_grid, c->spill_deep, c->spill_lanes,
+        c->wf_chunk, c->wf_shd_half, c->pool.queue_from, (int32_t)std::min<int64_t>(c->pool.max, INT32_MAX)};
+    std::copy(v, v + MFX_LAUNCH_INFO_N, out);
     return MFX_OK;
 }
 

@@ -329,8 +329,9 @@ struct __attribute__((visibility("hidden"))) mfx_ctx {
     bool wf_shd_half = true;  // k_shadow takes half chunks in place on frames of at most 2^25 paths (MFX_SHD_HALF)
     int mega_chunk = 0;   // megakernel: paths a wave takes per atomic (0: by the call's size)
     int mega_waves = 1;   // megakernel instance: 4 (128-VGPR budget) or 1 (mfx_kernels.hip)
-    mfxh::DevBuf<int32_t> d_spill;      // deep traversal-stack entries
-    mfxh::DevBuf<double> d_vscratch;    // megakernel: per-lane vertex records [max_depth + 1][6][grid * 256]
+    mfxh::DevBuf<int32_t> d_spill;      // deep traversal-stack entries [spill_deep][spill_lanes]
+    int spill_deep = 0, spill_lanes = 0;
+    mfxh::DevBuf<double> d_vscratch;   // megakernel: per-lane vertex records [max_depth + 1][6][grid * 256]
     mfxh::DevBuf<double> d_albedo;      // [nmat][3]
     mfxh::DevBuf<MfxLight> d_light;     // the light (k_shadow reads it into LDS)
     mfxh::DevBuf<MfxCamera> d_cam;      // the camera (k_camera reads it into LDS)
@@ -385,6 +386,17 @@ void fill_scene_ptrs(const mfx_ctx* c, P& p) {
     p.shade = c->d_shade;
     p.inst = c->d_inst;
     p.tslack = c->host.tslack;
+}
+
+// a gray light (bitwise equal intensities): k_shadow records a lit vertex's direct term itself
+inline bool wf_gray_light(const mfx_ctx* c) {
+    const double* I = c->host.light.color;
+    return std::memcmp(&I[0], &I[1], sizeof(double)) == 0 && std::memcmp(&I[0], &I[2], sizeof(double)) == 0 &&
+           !getenv("MFX_NO_GRAY_LIGHT");
+}
+// in place, a HIT state word carries the path's lit mask (WfParams.lit_in_hit)
+inline bool wf_lit_in_hit(const mfx_ctx* c) {
+    return c->host.max_depth <= 3 && c->host.shade.size() <= ((size_t)1 << 25) && !getenv("MFX_NO_LIT_IN_HIT");
 }
 
 // MFX_OK, or MFX_E_STATE for a call that needs one device and the whole film and sample set

@@ -144,10 +144,8 @@ static void fill_scene_params(mfx_ctx* c, WfParams& P) {
     P.light_dev = c->d_light;
     P.cam_dev = c->d_cam;
     P.refs_dev = c->d_refs;
-    // a gray light (bitwise equal intensities): k_shadow records a lit vertex's direct term itself
-    P.gray_light = std::memcmp(&P.light.color[0], &P.light.color[1], sizeof(double)) == 0 &&
-                   std::memcmp(&P.light.color[0], &P.light.color[2], sizeof(double)) == 0 && !getenv("MFX_NO_GRAY_LIGHT");
-    P.lit_in_hit = c->host.max_depth <= 3 && c->host.shade.size() <= ((size_t)1 << 25) && !getenv("MFX_NO_LIT_IN_HIT");
+    P.gray_light = wf_gray_light(c);
+    P.lit_in_hit = wf_lit_in_hit(c);
     P.albedo = c->d_albedo;
     P.nmat = (int32_t)(c->host.albedo.size() / 3);
 }

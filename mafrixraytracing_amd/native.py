@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from .abi import (INSTANCING_KEYS, MFX_DN_SRC_ACCUM, MFX_DN_SRC_HOST, MFX_F_NONE, MFX_F_TWO_LEVEL, MfxAdaptive,
+from .abi import (INSTANCING_KEYS, LAUNCH_INFO_KEYS, MFX_DN_SRC_ACCUM, MFX_DN_SRC_HOST, MFX_F_NONE, MFX_F_TWO_LEVEL, MfxAdaptive,
                   MfxDenoiseCfg, MfxInstance, MfxOptions, SceneArrays, check, dptr, iptr, load_library)
 from .denoise import DenoiseConfig
 
@@ -244,6 +244,16 @@ class NativeContext:
         return {"devices": [int(d) for d in out[5:5 + g]], "communicators": int(out[1]),
                 "merge": {0: "none", 1: "rccl_reduce", 2: "ordered_adds"}[int(out[2])],
                 "band_index": int(out[3]), "band_count": int(out[4])}
+
+    def launch_info(self) -> dict:
+        """What creation chose for the kernels (mfx_launch_info): the traversal-stack bound and its LDS
+        shares, the spill flags, top nodes / slots / instance records in LDS, the k_shadow and megakernel
+        builds, lit_in_hit, gray_light, camera packets, the grids and the spill buffer's size. The
+        flags are bools, the rest ints."""
+        out = np.zeros(len(LAUNCH_INFO_KEYS), dtype=np.int32)
+        check(self.lib.mfx_launch_info(self._h, iptr(out), len(out)), "mfx_launch_info")
+        flags = ("spill_ext", "spill_shd", "lit_in_hit", "gray_light", "camera_packets", "shd_half")
+        return {k: bool(v) if k in flags else int(v) for k, v in zip(LAUNCH_INFO_KEYS, out)}
 
     def instancing_info(self) -> dict:
         """How instances are traced (mfx_instancing_info): two-level shape and image bytes."""
