@@ -107,7 +107,9 @@ typedef struct mfx_scene_desc {
  * the list; a pixel is +0.0 on every device but its own, so the sum is an exact merge). A list that
  * repeats a device (e.g. {0,0}) merges by device-ordered adds instead (RCCL needs distinct devices). */
 typedef struct mfx_options {  /* ABI 4: the former `reserved` field is render_ahead (0 = off); layout unchanged since */
-    uint64_t seed;      /* counter-RNG seed; the reference uses unseeded System.Random */
+    uint64_t seed;      /* counter-RNG seed; the reference uses unseeded System.Random.
+                         * All 64 bits enter every path's key; the key takes the global sample index
+                         * modulo 2^32, so a pixel's sample streams repeat with period 2^32 */
     int32_t device;     /* HIP device ordinal when ndevices == 0 */
     int32_t flags;      /* MFX_F_* */
     int32_t part_index; /* this context renders sample partition part_index of part_count */
@@ -261,6 +263,7 @@ int mfx_sample_adaptive(mfx_ctx* ctx, const mfx_adaptive* cfg, double* frame_xma
  * The planes stay on the device as the context's feature buffers (allocated at the first call: a
  * context that never calls this pays nothing) and are what mfx_denoise is guided by.
  * out_xmajor (may be NULL): out[(i*h + j)*8 + k].  ms (may be NULL): device time from HIP events.
+ * The key takes s modulo 2^32, as in mfx_trace_accumulate: sample 2^32 + k gives sample k's ray.
  * Leaves the accumulator, the film, the moment planes, next_sample and every ray counter untouched.
  * MFX_E_INVALID: NULL ctx, spp < 1, sample_base < 0. MFX_E_STATE: part_count > 1,
  * MFX_F_ROW_PARTITION or a device list (as mfx_sample_adaptive). Flat and instanced scenes alike. */
@@ -341,7 +344,10 @@ int mfx_film_mean(mfx_ctx* ctx, double* frame_xmajor_rgba);
 /* Adds, for global samples [sample_base, sample_base + spp) of this context's partition,
  * the per-pixel radiance sums into the context's device accumulator (FP64, 3 planes of w*h,
  * plane-major, x-major pixels); on a multi-device context each device into its own.
- * Does not synchronise; mfx_sync() does.                                                     */
+ * Does not synchronise; mfx_sync() does.
+ * Global sample indices are 64-bit, and the path key takes them modulo 2^32:
+ * global sample 2^32 + k is sample k again, so a range that crosses 2^32 continues with
+ * samples 0, 1, ...                                                                           */
 int mfx_trace_accumulate(mfx_ctx* ctx, int32_t spp, int64_t sample_base);
 /* Multi-device context: sum every device's accumulator into the primary's (RCCL reduce, root
  * devices[0]), ordered after each device's trace: after a clear and a trace, an exact merge of

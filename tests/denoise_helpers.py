@@ -9,7 +9,7 @@ _features = {}
 _frames = {}
 
 
-def scene_features(oracle, a, spp, base):
+def scene_features(oracle, a, spp, base, seed=SEED):
     """(w*h, 8) x-major features of a SceneArrays: for pixel (i, j) and global sample s the path's own
     camera ray (key pixel i*h + j, draws 0 and 1 -> u, v -> PinholeCamera.GetRay) and its Bvh.Hit;
     normal, t, the hit primitive's material's albedo and 1.0 per hit, summed in sample order from +0.0
@@ -23,7 +23,7 @@ def scene_features(oracle, a, spp, base):
         for i in range(w):
             for j in range(h):
                 p = i * h + j
-                d = oracle.rng_draws(SEED, p, s, 2)
+                d = oracle.rng_draws(seed, p, s, 2)
                 u, v = (i + d[0]) / w, (j + d[1]) / h
                 ro, rd = oracle.kat_camera_ray(cam["position"], cam["direction"], cam["fov"], cam["aspect"], u, v)
                 rays[p, :3], rays[p, 3:] = ro, rd
@@ -35,13 +35,13 @@ def scene_features(oracle, a, spp, base):
     return acc / float(spp)
 
 
-def oracle_features(oracle, name, w, h, spp, base):
+def oracle_features(oracle, name, w, h, spp, base, seed=SEED):
     """scene_features of scenes/<name>.xml at w x h. Computed once per case and left unchanged."""
     world = name.replace("@2l", "")  # the same world scene however it is traced
-    key = (world, w, h, spp, base)
+    key = (world, w, h, spp, base, seed)
     if key in _features:
         return _features[key]
-    f = scene_features(oracle, scene(world, w, h), spp, base)
+    f = scene_features(oracle, scene(world, w, h), spp, base, seed)
     f.setflags(write=False)
     _features[key] = f
     return f

@@ -14,6 +14,7 @@ import os
 import numpy as np
 import pytest
 
+from adaptive_helpers import check_parity, reference, run
 from conftest import SEED, scene
 
 pytestmark = pytest.mark.gpu
@@ -22,9 +23,6 @@ W, H = 44, 36  # both sides leave edge tiles
 BASE = dict(min_spp=4, step_spp=4, max_spp=32, abs_floor=0.01)
 QUEUE_MODES = ["-1", "0", "1", "2", "-2"]  # tests/test_gpu_ray_queue.py's MODES and QCHUNKS
 QCHUNKS = [{}, {"MFX_QCHUNK": "64", "MFX_CHUNK": "1024"}]
-
-_frames = {}
-_refs = {}
 
 
 def _ctx(a, env=None, **kw):
@@ -47,58 +45,6 @@ def _cfg(rel_error, **kw):
     d = dict(BASE, rel_error=rel_error)
     d.update(kw)
     return AdaptiveConfig(d["min_spp"], d["max_spp"], d["step_spp"], d["rel_error"], d["abs_floor"])
-
-
-def reference(oracle, name, w, h, cfg):
-    """(tile_spp, mean, rgba8, ray statistics) the call must return: computed once per case, shared."""
-    from mafrixraytracing_amd.adaptive import luminance, reference_mean, reference_tile_spp, tile_pixels
-    world = name.replace("@2l", "")  # the same world scene however it is traced
-    key = (world, w, h, cfg)
-    if key in _refs:
-        return _refs[key]
-    o = oracle.OracleScene(scene(world, w, h))
-    fk = (world, w, h)
-    if fk not in _frames or len(_frames[fk]) < cfg.max_spp:
-        f = np.stack([o.sample(1, SEED, sample_base=s) for s in range(max(32, cfg.max_spp))])
-        f.setflags(write=False)
-        _frames[fk] = f
-    frames = _frames[fk][:cfg.max_spp]
-    spp, gap = reference_tile_spp(luminance(frames), w, h, cfg)
-    print(f"{name} {w}x{h} {cfg}: smallest gap {gap:.3g}, mean spp {spp.mean():.2f}")
-    assert gap > 1e-6, (name, gap)  # the condition on the inputs: no tile near a tie
-    mean = reference_mean(frames, spp, w, h)
-    px, py, ps = [], [], []
-    for ty in range(spp.shape[0]):
-        for tx in range(spp.shape[1]):
-            p = tile_pixels(w, h, tx, ty)
-            n = int(spp[ty, tx])
-            px.append(np.repeat(p // h, n))
-            py.append(np.repeat(p % h, n))
-            ps.append(np.tile(np.arange(n), len(p)))
-    st = o.paths(np.concatenate(px), np.concatenate(py), np.concatenate(ps), SEED)[1][:3]
-    r = (spp, mean, oracle.post_rgba8(mean, w, h), st)
-    for a in r:
-        a.setflags(write=False)
-    _refs[key] = r
-    return r
-
-
-def run(ctx, cfg, want_rgba=True):
-    return ctx.sample_adaptive(cfg.min_spp, cfg.max_spp, cfg.step_spp, cfg.rel_error, cfg.abs_floor, want_rgba=want_rgba)
-
-
-def check_parity(ctx, ref, what=""):
-    spp, mean, rgba, st = ref[:4]
-    cfg = ref[4]
-    frame, tiles, out8 = run(ctx, cfg)
-    c = ctx.ray_counts()
-    assert np.array_equal(tiles, spp), (what, tiles.tolist(), spp.tolist())
-    assert np.array_equal(frame, mean), (what, np.abs(frame - mean).max())
-    assert np.array_equal(frame[:, 3], np.ones(len(frame)))
-    assert np.array_equal(out8, rgba), what
-    assert (c[0], c[1], c[2]) == (st[0], st[1], st[2]), (what, c[:3], st)
-    assert c[3] == c[0]
-    return frame, tiles, out8, c
 
 
 @pytest.mark.parametrize("name,rel", [("cornell", 0.25), ("spot", 0.3), ("two_spheres_plane", 0.3),
