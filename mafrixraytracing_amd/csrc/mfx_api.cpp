@@ -538,20 +538,7 @@ int mfx_build_info(mfx_ctx* c, double out[8], uint64_t* digest) {
         out[6] = h.nodes2;
         out[7] = h.bvh_levels;
     }
-    if (digest) {  // FNV-1a over the device images
-        uint64_t x = 1469598103934665603ULL;
-        auto mix = [&](const void* p, size_t n) {
-            const uint8_t* b = (const uint8_t*)p;
-            for (size_t i = 0; i < n; ++i) x = (x ^ b[i]) * 1099511628211ULL;
-        };
-        mix(h.nodes.data(), h.nodes.size() * sizeof(MfxNode));
-        mix(h.slots.data(), h.slots.size() * sizeof(MfxSlot));
-        mix(h.slot_ref.data(), h.slot_ref.size() * sizeof(int32_t));
-        mix(h.ref_blob.data(), h.ref_blob.size());
-        mix(h.shade.data(), h.shade.size() * sizeof(MfxShade));
-        mix(h.inst.data(), h.inst.size() * sizeof(MfxInstance));
-        *digest = x;
-    }
+    if (digest) *digest = mfx_scene_digest(h);
     return MFX_OK;
 }
 

@@ -9,29 +9,13 @@
 
 #include "mfx_layout.h"
 
-// A binned-SAH BVH2 over primitives, as mfx_scene.cpp's host SahBuilder produces it: internal
-// node i has two children (>= 0 internal node, < 0 ~leaf) and their FP32 boxes; leaf l is the
-// range [leaf_b[l], leaf_e[l]) of the primitive permutation `ids`. Node and leaf numbering is the
-// build's own; everything downstream follows child references only.
-struct MfxBvh2 {
-    std::vector<float> box;       // [nodes][2][6]: child box lo xyz, hi xyz
-    std::vector<int32_t> child;   // [nodes][2]
-    std::vector<int32_t> leaf_b, leaf_e;
-    std::vector<int32_t> ids;     // primitive permutation
-    int32_t root = 0;             // 0 (internal) or ~0 (the whole scene is one leaf)
-    float root_box[6] = {0, 0, 0, 0, 0, 0};
-    int32_t levels = 0;           // breadth-first levels (kernel launches)
-};
-
-// Build on the current HIP device. prim_box: [n][6] conservative FP32 boxes (lo xyz, hi xyz);
-// cent: [n][3] centroids; weight: [n] slots per primitive (the intersection cost weight).
-// Same parameters as SahBuilder: leaves of at most max_leaf primitives, intersection cost c_isect.
-hipError_t mfx_gpu_sah_build(const float* prim_box, const float* cent, const int32_t* weight, int n, int max_leaf,
-                             float c_isect, MfxBvh2& out);
-
-// The whole traversal image of a flat scene on the GPU: the BVH2 above, its BVH4 collapse and the
+// The whole traversal image of a flat scene, built on the current HIP device: a binned-SAH BVH2
+// over the primitives (the tree mfx_scene_bvh.cpp's host SahBuilder produces, with its parameters:
+// leaves of at most max_leaf primitives, intersection cost c_isect), its BVH4 collapse and the
 // layout (nodes renumbered, traversal leaves' slots in depth-first order) — the bytes the host
-// path (mfx_scene.cpp: Collapse4 + layout) produces. Per primitive p the caller gives its slots
+// path (mfx_scene.cpp: Collapse4 + layout) produces. prim_box: [n][6] conservative FP32 boxes (lo
+// xyz, hi xyz); cent: [n][3] centroids; weight: [n] slots per primitive (the intersection cost
+// weight); levels: the BVH2's breadth-first levels (kernel launches). Per primitive p the caller gives its slots
 // pslots[slot_of[p] .. slot_of[p + 1]) with the reference-leaf box, `first` and the info bits
 // other than the shade index already set, their shade records and the reference leaf's ref_blob
 // offset.

@@ -591,38 +591,6 @@ static hipError_t bvh2_build(const float* prim_box, const float* cent, const int
     return e;
 }
 
-hipError_t mfx_gpu_sah_build(const float* prim_box, const float* cent, const int32_t* weight, int n, int max_leaf,
-                             float c_isect, MfxBvh2& out) {
-    DevBvh2 D;
-    hipError_t e = bvh2_build(prim_box, cent, weight, n, max_leaf, c_isect, D);
-    auto ok = [&](hipError_t r) {
-        if (e == hipSuccess) e = r;
-        return e == hipSuccess;
-    };
-    if (e == hipSuccess) {
-        const BArgs& A = D.A;
-        out.box.resize(12 * (size_t)D.nodes);
-        out.child.resize(2 * (size_t)D.nodes);
-        std::vector<int2> lv(D.nleaves);
-        out.ids.resize(n);
-        ok(hipMemcpy(out.box.data(), A.node_box, sizeof(float) * out.box.size(), hipMemcpyDeviceToHost));
-        ok(hipMemcpy(out.child.data(), A.node_child, sizeof(int) * out.child.size(), hipMemcpyDeviceToHost));
-        ok(hipMemcpy(lv.data(), A.leaves, sizeof(int2) * lv.size(), hipMemcpyDeviceToHost));
-        ok(hipMemcpy(out.ids.data(), A.ids, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
-        ok(hipMemcpy(out.root_box, A.root_box, sizeof(float) * 6, hipMemcpyDeviceToHost));
-        out.root = D.root;
-        out.leaf_b.resize(lv.size());
-        out.leaf_e.resize(lv.size());
-        for (size_t l = 0; l < lv.size(); ++l) {
-            out.leaf_b[l] = lv[l].x;
-            out.leaf_e[l] = lv[l].y;
-        }
-        out.levels = D.levels;
-    }
-    bvh2_free(D);
-    return e;
-}
-
 hipError_t mfx_gpu_build_images(const float* prim_box, const float* cent, const int32_t* weight, int n, int max_leaf,
                                 float c_isect, const MfxGpuLayoutIn& in, MfxGpuImages& out) {
     DevBvh2 D;

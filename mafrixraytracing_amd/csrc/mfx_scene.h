@@ -54,5 +54,7 @@ bool mfx_build_scene(const mfx_scene_desc* d, MfxHostScene& s, std::string& err,
 // The world primitive list of an instanced scene (mfx_instance: template + offset, FP64).
 bool mfx_expand(const mfx_prim* prims, int64_t nprims, const mfx_instance* inst, int ninst,
                 std::vector<mfx_prim>& world, std::string& err);
+// FNV-1a over the device images (nodes, slots, slot_ref, ref_blob, shade, inst): mfx_build_info's digest.
+uint64_t mfx_scene_digest(const MfxHostScene& s);
 
 #endif

@@ -170,7 +170,7 @@ def test_all_equal_keys_follow_dotnet_order(oracle):
 
 @pytest.mark.parametrize("n,quant", [(20000, 0), (40000, 6)])
 def test_threaded_grouping_matches_oracle(oracle, n, quant):
-    """Ranges of >= 8,192 primitives split onto host threads (mfx_scene.cpp RefBvh): the leaves and
+    """Ranges of >= 8,192 primitives split onto host threads (mfx_scene_bvh.cpp RefBvh): the leaves and
     their order equal the oracle's sequential recursion, with and without tied keys."""
     from mafrixraytracing_amd.abi import build_leaves
     rng = np.random.default_rng(n + quant)

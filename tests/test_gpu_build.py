@@ -1,6 +1,6 @@
 """On-GPU traversal-BVH build (the reference builds on the host, Bvh.Build,
 BvhNode.fs:24-61) against the host build: mfx_build.hip builds the same binned-SAH tree as
-mfx_scene.cpp's SahBuilder, so the device images are byte-identical (equal FNV digests) and every
+mfx_scene_bvh.cpp's SahBuilder, so the device images are byte-identical (equal FNV digests) and every
 traversal, counter and image is identical too. The default context builds on the GPU, so every
 other GPU parity test also runs on the GPU-built tree."""
 import numpy as np
