@@ -225,26 +225,28 @@ static int ctx_setup(mfx_ctx* c) {
     // nothing there).
     WfParams& A = c->pool.params;  // the launch shapes go straight into the trace's parameters
     int ebpc = 0, sbpc = 0;
+    const MfxNodeH* nodes_h = c->d_nodes_h;
+    const bool fp16 = nodes_h != nullptr;  // the node format the trace kernels' instances are chosen by
     const int shd_target_max = getenv("MFX_SHADOW_TARGET_BLOCKS") ? atoi(getenv("MFX_SHADOW_TARGET_BLOCKS")) : 8;
     for (const bool shd : {false, true}) {
         int full = 0;
-        CK(mfx_wf_kernel_occupancy(shd, c->stack_size, false, 0, ninst, &full));
+        CK(mfx_wf_kernel_occupancy(shd, c->stack_size, false, 0, ninst, &full, 0, fp16));
         int nlds = c->stack_size, blocks = full;
         if (c->stack_size > WF_STACK_LDS) {
             int b16 = 0;
-            CK(mfx_wf_kernel_occupancy(shd, WF_STACK_LDS, true, 0, ninst, &b16));
+            CK(mfx_wf_kernel_occupancy(shd, WF_STACK_LDS, true, 0, ninst, &b16, 0, fp16));
             const int target = shd ? std::max(full, std::min(shd_target_max, b16)) : b16;
             if (full < target) {
                 int lo = WF_STACK_LDS, hi = c->stack_size - 1;  // blocks only fall as the share grows
                 while (lo < hi) {
                     const int mid = (lo + hi + 1) / 2;
                     int b = 0;
-                    CK(mfx_wf_kernel_occupancy(shd, mid, true, 0, ninst, &b));
+                    CK(mfx_wf_kernel_occupancy(shd, mid, true, 0, ninst, &b, 0, fp16));
                     if (b >= target) lo = mid;
                     else hi = mid - 1;
                 }
                 nlds = lo;
-                CK(mfx_wf_kernel_occupancy(shd, nlds, true, 0, ninst, &blocks));
+                CK(mfx_wf_kernel_occupancy(shd, nlds, true, 0, ninst, &blocks, 0, fp16));
             }
             if (c->diag_iter)
                 fprintf(stderr, "wavefront: %s blocks/CU: full %d-entry stacks %d, %d in LDS %d; chosen %d in LDS, %d\n",
@@ -252,7 +254,7 @@ static int ctx_setup(mfx_ctx* c) {
         }
         if (const char* e = getenv("MFX_STACK_LDS")) {
             nlds = std::max(1, std::min(c->stack_size, atoi(e)));
-            CK(mfx_wf_kernel_occupancy(shd, nlds, nlds < c->stack_size, 0, ninst, &blocks));
+            CK(mfx_wf_kernel_occupancy(shd, nlds, nlds < c->stack_size, 0, ninst, &blocks, 0, fp16));
         }
         (shd ? A.stack_lds_shd : A.stack_lds_ext) = nlds;
         (shd ? sbpc : ebpc) = blocks;
@@ -266,7 +268,7 @@ static int ctx_setup(mfx_ctx* c) {
             while (lo < hi) {
                 const int mid = (lo + hi + 1) / 2;
                 int b = 0;
-                CK(mfx_wf_kernel_occupancy(shd, nlds, nlds < c->stack_size, mid, ninst, &b));
+                CK(mfx_wf_kernel_occupancy(shd, nlds, nlds < c->stack_size, mid, ninst, &b, 0, fp16));
                 if (b >= want) lo = mid;
                 else hi = mid - 1;
             }
@@ -278,7 +280,7 @@ static int ctx_setup(mfx_ctx* c) {
             if (ns > WF_SLOT_LDS_MAX || (getenv("MFX_SLOT_LDS") && atoi(getenv("MFX_SLOT_LDS")) == 0)) ns = 0;
             if (ns > 0) {
                 int b = 0;
-                CK(mfx_wf_kernel_occupancy(shd, nlds, nlds < c->stack_size, lo, ninst, &b, ns));
+                CK(mfx_wf_kernel_occupancy(shd, nlds, nlds < c->stack_size, lo, ninst, &b, ns, fp16));
                 if (b < want) ns = 0;
             }
             (shd ? A.nslot_shd : A.nslot_ext) = ns;

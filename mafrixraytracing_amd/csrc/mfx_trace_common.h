@@ -675,6 +675,27 @@ __device__ __forceinline__ RayF frame_ray(const SceneView& S, int inst, DV o, DV
     return make_rayf(o, d);
 }
 
+// A node step's far-first pushes into an LDS column, stack[sp + j] = v_j for j < nh - 1 (nh <= 4), as
+// three stores under a shrinking exec mask and no branch (written as `if (nh >= k) store`, each push
+// compiles to a compare, s_and_saveexec, a branch over one ds_write and s_or: three such sequences a
+// step). Lanes that do not push store nothing, as before: the stack holds the pushes alone.
+__device__ __forceinline__ void lds_push3(int* col, int nh, int v0, int v1, int v2) {
+    const uint32_t a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int*)col;
+    uint64_t saved;
+    asm volatile(
+        "s_mov_b64 %0, exec\n\t"
+        "v_cmpx_lt_u32_e32 vcc, 1, %2\n\t"
+        "ds_write_b32 %1, %3\n\t"
+        "v_cmpx_lt_u32_e32 vcc, 2, %2\n\t"
+        "ds_write_b32 %1, %4 offset:256\n\t"
+        "v_cmpx_lt_u32_e32 vcc, 3, %2\n\t"
+        "ds_write_b32 %1, %5 offset:512\n\t"
+        "s_mov_b64 exec, %0"
+        : "=&s"(saved)
+        : "v"(a), "v"(nh), "v"(v0), "v"(v1), "v"(v2)
+        : "memory", "vcc");
+}
+
 // A lane's traversal stack. LdsStack: the whole bound in an LDS column (stride 64 dwords:
 // conflict-free). SpillStack: the first `nlds` entries in LDS and deeper ones in a global column
 // (stride `gstride`), so the LDS a wave needs — which caps the resident waves — no longer grows
@@ -686,6 +707,10 @@ struct LdsStack {
     __device__ __forceinline__ bool deep(int) const { return false; }
     __device__ __forceinline__ int get(int i, bool) const { return lds[i * 64]; }
     __device__ __forceinline__ void put(int i, int v, bool) const { lds[i * 64] = v; }
+    // the masked pushes of a step at depth sp (the wavefront kernels' stacks are LDS columns)
+    __device__ __forceinline__ void push3(int sp, int nh, int v0, int v1, int v2, bool) const {
+        lds_push3(lds + sp * 64, nh, v0, v1, v2);
+    }
 };
 struct SpillStack {
     int* lds;
@@ -699,6 +724,15 @@ struct SpillStack {
     __device__ __forceinline__ void put(int i, int v, bool dp) const {
         if (!dp || i < nlds) lds[i * 64] = v;
         else spill[(i - nlds) * gstride] = v;
+    }
+    __device__ __forceinline__ void push3(int sp, int nh, int v0, int v1, int v2, bool dp) const {
+        if (!dp) {  // (wave-uniform) every entry of the step in LDS
+            lds_push3(lds + sp * 64, nh, v0, v1, v2);
+            return;
+        }
+        if (nh >= 2) put(sp, v0, dp);
+        if (nh >= 3) put(sp + 1, v1, dp);
+        if (nh >= 4) put(sp + 2, v2, dp);
     }
 };
 
@@ -809,7 +843,7 @@ __device__ __forceinline__ uint64_t diag_clock() {
 // widened exactly (v_cvt_f32_f16), then the same FP32 slab test, order and pushes. The boxes are the
 // FP32 ones rounded outward, so a lane visits a superset of its FP32 walk's nodes; the leaf tests
 // decide the hits (§3), and the images are the same bits
-template <bool TOP, bool FAR, typename ST>
+template <bool TOP, bool FAR, bool MASKED, typename ST>
 __device__ __forceinline__ int node_step_h(int node, const RayF& r, float tlim, const ST& stack, int& sp, TopNodes tn,
                                            uint64_t* lat) {
     const bool dp = stack.deep(sp + 3);
@@ -848,21 +882,34 @@ __device__ __forceinline__ int node_step_h(int node, const RayF& r, float tlim, 
     cswap(d[0], c[0], d[2], c[2]);
     cswap(d[1], c[1], d[3], c[3]);
     cswap(d[1], c[1], d[2], c[2]);
-    if (nh >= 2) stack.put(sp, nh == 4 ? c[3] : (nh == 3 ? c[2] : c[1]), dp);
-    if (nh >= 3) stack.put(sp + 1, nh == 4 ? c[2] : c[1], dp);
-    if (nh >= 4) stack.put(sp + 2, c[1], dp);
+    if (MASKED) {
+        stack.push3(sp, nh, nh == 4 ? c[3] : (nh == 3 ? c[2] : c[1]), nh == 4 ? c[2] : c[1], c[1], dp);
+    } else {
+        if (nh >= 2) stack.put(sp, nh == 4 ? c[3] : (nh == 3 ? c[2] : c[1]), dp);
+        if (nh >= 3) stack.put(sp + 1, nh == 4 ? c[2] : c[1], dp);
+        if (nh >= 4) stack.put(sp + 2, c[1], dp);
+    }
     const bool pop = nh == 0 && sp > 0;
     const int next = nh > 0 ? c[0] : (pop ? top : MFX_TRAV_EXIT);
     sp += nh > 0 ? nh - 1 : (pop ? -1 : 0);
     return next;
 }
 #endif
-template <bool TOP = false, bool FAR = false, typename ST>
+// NF: the node format the caller's kernel instance is built for. MFX_NF_ANY: either, chosen per step
+// by a wave-uniform branch on tn.nodes_h (both bodies in the node loop); MFX_NF_H / MFX_NF_F32: only
+// that step is compiled in (the caller passes FP16 nodes exactly when NF says so)
+#define MFX_NF_ANY 0
+#define MFX_NF_H 1
+#define MFX_NF_F32 2
+// MASKED: the pushes as branch-free masked LDS stores (ST::push3: the wavefront kernels' stacks)
+template <bool TOP = false, bool FAR = false, int NF = MFX_NF_ANY, bool MASKED = false, typename ST>
 __device__ __forceinline__ int node_step(const MfxNode* __restrict__ nodes, int node, const RayF& r, float tlim,
                                          const ST& stack, int& sp, TopNodes tn = TopNodes{nullptr, 0},
                                          uint64_t* lat = nullptr) {
 #if MFX_NODE_F16
-    if (tn.nodes_h) return node_step_h<TOP, FAR>(node, r, tlim, stack, sp, tn, lat);
+    if (NF == MFX_NF_H || (NF == MFX_NF_ANY && tn.nodes_h)) return node_step_h<TOP, FAR, MASKED>(node, r, tlim, stack, sp, tn, lat);
+#else
+    static_assert(NF != MFX_NF_H, "FP16 nodes need an MFX_NODE_F16 build");
 #endif
     const bool dp = stack.deep(sp + 3);  // this step reads sp - 1 and may write sp .. sp + 2
     const int top = stack.get(sp > 0 ? sp - 1 : 0, dp);
@@ -904,11 +951,15 @@ __device__ __forceinline__ int node_step(const MfxNode* __restrict__ nodes, int 
     cswap(d[0], c[0], d[2], c[2]);
     cswap(d[1], c[1], d[3], c[3]);
     cswap(d[1], c[1], d[2], c[2]);
-    // far-first pushes: stack[sp + j] = c[nh - 1 - j] for j < nh - 1 (exec-masked stores, so the
-    // stack never holds more than the pushes themselves: mfx_scene.cpp's Collapse4 bound)
-    if (nh >= 2) stack.put(sp, nh == 4 ? c[3] : (nh == 3 ? c[2] : c[1]), dp);
-    if (nh >= 3) stack.put(sp + 1, nh == 4 ? c[2] : c[1], dp);
-    if (nh >= 4) stack.put(sp + 2, c[1], dp);
+    // far-first pushes: stack[sp + j] = c[nh - 1 - j] for j < nh - 1 (exec-masked stores either way, so
+    // the stack never holds more than the pushes themselves: mfx_scene.cpp's Collapse4 bound)
+    if (MASKED) {
+        stack.push3(sp, nh, nh == 4 ? c[3] : (nh == 3 ? c[2] : c[1]), nh == 4 ? c[2] : c[1], c[1], dp);
+    } else {
+        if (nh >= 2) stack.put(sp, nh == 4 ? c[3] : (nh == 3 ? c[2] : c[1]), dp);
+        if (nh >= 3) stack.put(sp + 1, nh == 4 ? c[2] : c[1], dp);
+        if (nh >= 4) stack.put(sp + 2, c[1], dp);
+    }
     const bool pop = nh == 0 && sp > 0;
     const int next = nh > 0 ? c[0] : (pop ? top : MFX_TRAV_EXIT);
     sp += nh > 0 ? nh - 1 : (pop ? -1 : 0);

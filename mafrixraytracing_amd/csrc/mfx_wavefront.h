@@ -232,9 +232,10 @@ hipError_t mfx_wf_tile_check(const TileCheckParams& C, hipStream_t st);
 #endif
 // resident blocks per CU of k_extend / k_shadow with `stack_lds` stack entries per lane (spill: the
 // SpillStack instance), ntop top BVH nodes and min(ninst, WF_INST_LDS) instance records in LDS
-// (and nslot slots' test prefixes)
+// (and nslot slots' test prefixes); fp16: the context walks FP16 nodes (WfParams::nodes_h set), which
+// selects the flat scene kind's per-format instance, the one its launches run
 hipError_t mfx_wf_kernel_occupancy(bool shadow, int stack_lds, bool spill, int ntop, int ninst, int* blocks_per_cu,
-                                   int nslot = 0);
+                                   int nslot, bool fp16);
 // resident blocks per CU of k_camera (camera-ray packets)
 hipError_t mfx_cam_occupancy(int stack_size, int* blocks_per_cu);
 // a ray queue's arrays (MFX_RAY_QUEUE): entries in the pool's shard ranges, counts per shard

@@ -50,6 +50,10 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 #define MFX_NODE_LANES_MIN_SHD 12  // the same for shadow rays
 #endif
 
+#ifndef MFX_MASKED_PUSH
+#define MFX_MASKED_PUSH 1  // node_step's pushes as masked stores without branches (0: three branches a step)
+#endif
+
 #ifndef MFX_DIAG_STAMPS
 #define MFX_DIAG_STAMPS 0  // diagnostic build only: 1 = k_extend phase stamps, 2 = k_shadow, 3 = k_camera
 #endif
@@ -228,10 +232,10 @@ __device__ __forceinline__ void trav_begin(Trav& T, const SceneView& S, DV o, DV
 }
 
 // one node step of the per-lane traversal (BVH4; shadow rays far-first)
-template <bool SHADOW, typename ST>
+template <bool SHADOW, int NF, typename ST>
 __device__ __forceinline__ int trav_node_step(const SceneView& S, int node, const RayF& rf, float tlim, const ST& stack,
                                               int& sp, TopNodes tn, uint64_t* lat) {
-    return node_step<true, SHADOW && MFX_SHADOW_ORDER == 1>(S.nodes, node, rf, tlim, stack, sp, tn, lat);
+    return node_step<true, SHADOW && MFX_SHADOW_ORDER == 1, NF, MFX_MASKED_PUSH != 0>(S.nodes, node, rf, tlim, stack, sp, tn, lat);
 }
 
 // Internal nodes until this lane reaches a leaf (while-while), then that one reference leaf in
@@ -239,7 +243,8 @@ __device__ __forceinline__ int trav_node_step(const SceneView& S, int node, cons
 // stack empty).
 // INST: a two-level scene; a lane enters and leaves instances inside the node loop (inst_frame).
 // SLDS: the scene's slots are read from the kernel's LDS copy (a small flat scene, SceneView::slots_lds).
-template <bool SHADOW, bool STATS, bool INST, bool SLDS, typename ST>
+// NF: the kernel instance's node format (node_step).
+template <bool SHADOW, bool STATS, bool INST, bool SLDS, int NF, typename ST>
 __device__ __forceinline__ bool trav_step(Trav& T, const SceneView& S, const ST& stack, TopNodes tn, Stats& st,
                                           DiagAcc& dg, bool diag) {
     // the frame of the entry popped at the end of the last round (an instance left or entered)
@@ -255,7 +260,7 @@ __device__ __forceinline__ bool trav_step(Trav& T, const SceneView& S, const ST&
         if (STATS && !SHADOW && T.B.found) st.after_nodes++;
 #endif
         if (diag && lane_id() == __builtin_amdgcn_readfirstlane(lane_id())) dg.node_iters++;  // once per wave iteration
-        T.node = trav_node_step<SHADOW>(S, T.node, rf, tlim, stack, T.sp, tn, diag ? &dg.lat : nullptr);
+        T.node = trav_node_step<SHADOW, NF>(S, T.node, rf, tlim, stack, T.sp, tn, diag ? &dg.lat : nullptr);
         if (INST) T.node = inst_frame(S, T.node, T.inst, T.inst_sp, T.sp, T.o, T.d, rf);
         // leave the node loop once few lanes still step: the rest resume next round, after the
         // leaf tests and a refill of the idle lanes
@@ -347,12 +352,34 @@ struct PendShd {
 #define MFX_HEMI_WAVE_FIRST 1  // trials each owner makes alone before the wave shares them (r02bi: 1 vs 2, C3 +0.8 %, C4 +0.6 %, C2 -0.5 %)
 #endif
 
+// hemisphere_ball_wave's share of a round with np pending owners, from a table (one scalar load, no
+// divide in the round; the quotients through v_rcp_f32 instead cost the round what the even share
+// saved): word 0 = b << 24 | M(b), word 1 = M(b + 1), with b = floor(64 / np) and
+// M(d) = floor(65536 / d) + 1 the multiplier with floor(n / d) = (n * M(d)) >> 16 for n < 128, d <= 65
+// (n * (M d - 65536) <= 127 * 65 < 65536). The 24-bit multiply reads M under b.
+struct EvenShareTab {
+    uint32_t w[65][2];
+};
+constexpr EvenShareTab make_even_share() {
+    EvenShareTab t{};
+    for (uint32_t n = 1; n <= 64; ++n) {
+        const uint32_t b = 64 / n;
+        t.w[n][0] = (b << 24) | (65536 / b + 1);
+        t.w[n][1] = 65536 / (b + 1) + 1;
+    }
+    return t;
+}
+__constant__ EvenShareTab even_share_tab = make_even_share();
+
 // GetRandomInUnitSphere(nm) (Material.fs:9-14) for the wave's shading lanes (`own`), the same
 // accepted trial, point and draw count as hemisphere_ball. A lane's loop runs until its first
 // accepted trial (3.8 trials on average), but the wave runs until its slowest lane's (about 16):
-// after a first round in which every owner tries its own first MFX_HEMI_WAVE_FIRST trials, the owners
-// still rejecting share the wave's 64 lanes, m = 2^k consecutive trials each (np * m <= 64), and
-// each owner takes the lowest accepted trial of its round (all lower ones were rejected before).
+// after a first round in which every owner tries its own first MFX_HEMI_WAVE_FIRST trials, the np
+// owners still rejecting share all 64 lanes of every round evenly: with b = floor(64 / np) and
+// e = 64 - b * np, the owner of rank r < e gets b + 1 consecutive trials and the others b, on
+// consecutive lanes from lane r * b + min(r, e) (a power-of-two share, m = 2^k with np * m <= 64,
+// left 12 to 29 of the 64 lanes idle in the middle rounds and took about one round more). Each owner
+// takes the lowest accepted trial of its round (all lower ones were rejected before).
 // A worker lane draws from the owner's key and draw count (the trial's three draws at their
 // counter positions) and decides with hemi_trial, so p is the owner's own computation's bits.
 // scratch: 64 ints of the wave's LDS (owner lane ids in rank order).
@@ -379,31 +406,34 @@ __device__ __forceinline__ DV hemisphere_ball_wave(bool own, DV nm, uint64_t key
         const uint64_t pend = __ballot(!done);
         if (pend == 0) break;
         const int np = __popcll(pend);
-        int sh = 0;  // trials per pending owner: m = 2^sh, np * m <= 64
-        while ((np << (sh + 1)) <= 64) ++sh;
+        // trials per pending owner (wave-uniform): b + 1 for the first e ranks, b for the rest; 64 in all
+        const uint32_t w0 = even_share_tab.w[np][0], w1 = even_share_tab.w[np][1];
+        const int b = (int)(w0 >> 24), e = 64 - b * np;
         const int rank = __popcll(pend & lanes_below());
         if (!done) scratch[rank] = lane;
         wave_lds_sync();
-        const int slot = lane >> sh, t = lane & ((1 << sh) - 1);
-        const bool work = slot < np;
-        const int owner = work ? scratch[slot] : lane;
+        // this lane works for the owner of rank `slot`, on its trial t of the round
+        const bool wide = lane < e * (b + 1);
+        const uint32_t ln = (uint32_t)(wide ? lane : lane - e);
+        const int slot = (int)(__umul24(ln, wide ? w1 : w0) >> 16);
+        const int t = (int)ln - __mul24(slot, wide ? b + 1 : b);
+        const int owner = scratch[slot];
         wave_lds_sync();
         const uint64_t k = __shfl(key, owner);
-        const uint32_t b = (uint32_t)__shfl((int)base, owner);
+        const uint32_t ob = (uint32_t)__shfl((int)base, owner);
         const uint32_t nt = (uint32_t)__shfl((int)next, owner);
         const DV q = dv(__shfl(nm.x, owner), __shfl(nm.y, owner), __shfl(nm.z, owner));
-        bool acc = false;
         DV pt = dv(0, 0, 0);
-        if (work) {
-            uint32_t r = b + 3 * (nt + (uint32_t)t);
-            const uint64_t zx = rng_bits(k, r);
-            const uint64_t zy = rng_bits(k, r);
-            const uint64_t zz = rng_bits(k, r);
-            acc = hemi_trial(q, (float)q.x, (float)q.y, (float)q.z, zx, zy, zz, pt);
-        }
+        uint32_t r = ob + 3 * (nt + (uint32_t)t);
+        const uint64_t zx = rng_bits(k, r);
+        const uint64_t zy = rng_bits(k, r);
+        const uint64_t zz = rng_bits(k, r);
+        const bool acc = hemi_trial(q, (float)q.x, (float)q.y, (float)q.z, zx, zy, zz, pt);
         const uint64_t A = __ballot(acc);
-        const int first_lane = done ? lane : (rank << sh);
-        const uint64_t seg = done ? 0 : (A >> first_lane) & (sh == 6 ? ~0ULL : ((1ULL << (1 << sh)) - 1));
+        // the owner's own share of the round: m trials on the lanes from first_lane
+        const int m = b + (rank < e ? 1 : 0);
+        const int first_lane = done ? lane : __mul24(rank, b) + min(rank, e);
+        const uint64_t seg = done ? 0 : (A >> first_lane) & (~0ULL >> (64 - m));  // 1 <= m <= 64
         const int src = done ? lane : first_lane + (seg ? __builtin_ctzll(seg) : 0);
         const DV ps = dv(__shfl(pt.x, src), __shfl(pt.y, src), __shfl(pt.z, src));
         if (!done) {
@@ -412,7 +442,7 @@ __device__ __forceinline__ DV hemisphere_ball_wave(bool own, DV nm, uint64_t key
                 rn = base + 3 * (next + (uint32_t)__builtin_ctzll(seg) + 1);
                 done = true;
             } else {
-                next += 1u << sh;
+                next += (uint32_t)m;
             }
         }
     }
@@ -481,7 +511,10 @@ __device__ __forceinline__ VertexSample sample_vertex(const MfxLight& LT, bool o
 // rays (two-level scenes, MFX_CAMERA_PACKETS=0); only it carries the camera-ray code (GetRay, the
 // path key, the camera's fields), so the bounce instances hold fewer live scalar registers
 // LIST: a START instance for a listed trace (adaptive sampling: path_pixel's tile list)
-template <bool STATS, bool SPILL, int SK, bool Q, bool START = false, bool LIST = false>
+// NF: the node format (node_step): the instances a flat scene's default path launches (the bounce and
+// queue ones, wf_nf) are built for one format each, so their node loop holds one step and none of the
+// other's registers; the rest (STATS, START, LIST, the other scene kinds) take either (MFX_NF_ANY)
+template <bool STATS, bool SPILL, int SK, bool Q, bool START = false, bool LIST = false, int NF = MFX_NF_ANY>
 __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
     constexpr bool INST = SK == WF_SK_INST, SLDS = SK == WF_SK_SLDS;
     extern __shared__ int lds_all[];
@@ -491,7 +524,7 @@ __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
     const TopNodes tn{(const float4*)lds_all, P.ntop_ext};
 #endif
 #if MFX_NODE_F16
-    if (P.nodes_h) load_top_nodes_h((float4*)lds_all, P.nodes_h, P.ntop_ext);
+    if (NF == MFX_NF_H || (NF == MFX_NF_ANY && P.nodes_h)) load_top_nodes_h((float4*)lds_all, P.nodes_h, P.ntop_ext);
     else
 #endif
         load_top_nodes((float4*)lds_all, P.nodes, P.ntop_ext);
@@ -627,7 +660,7 @@ __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
         DIAG_MARK(dg, fetch, DG);
         if (DG) dg.outer++;
         bool fin = false;
-        if (active) fin = trav_step<false, STATS, INST, SLDS>(T, S, stack, tn, st, dg, DG);
+        if (active) fin = trav_step<false, STATS, INST, SLDS, NF>(T, S, stack, tn, st, dg, DG);
         DIAG_MARK(dg, leaf, DG);
         if (fin) finish_ray();
         DIAG_MARK(dg, fin, DG);
@@ -826,7 +859,8 @@ struct ShdPtrs {
 // ------------------------------------------------------------------------------------------------
 // Q: the instance that reads a ray queue (P.qslot) or writes the next one (P.ncount), MFX_RAY_QUEUE
 // LIST: the instances for a listed trace (adaptive sampling: path_pixel's tile list)
-template <bool STATS, bool SPILL, int WAVES, int SK, bool Q, bool LIST = false>
+// NF: the node format, as k_extend's
+template <bool STATS, bool SPILL, int WAVES, int SK, bool Q, bool LIST = false, int NF = MFX_NF_ANY>
 __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
     constexpr bool INST = SK == WF_SK_INST, SLDS = SK == WF_SK_SLDS;
     extern __shared__ int lds_all[];
@@ -867,7 +901,7 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
         *(PixParams*)((ShdPtrs*)(light_lds + 1) + 1) = px;
     }
 #if MFX_NODE_F16
-    if (P.nodes_h) load_top_nodes_h((float4*)lds_all, P.nodes_h, P.ntop_shd);
+    if (NF == MFX_NF_H || (NF == MFX_NF_ANY && P.nodes_h)) load_top_nodes_h((float4*)lds_all, P.nodes_h, P.ntop_shd);
     else
 #endif
         load_top_nodes((float4*)lds_all, P.nodes, P.ntop_shd);
@@ -1081,7 +1115,7 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
             fin = true;
         }
 #else
-        if (active) fin = trav_step<true, STATS, INST, SLDS>(T, S, stack, tn, st, dg, DG);
+        if (active) fin = trav_step<true, STATS, INST, SLDS, NF>(T, S, stack, tn, st, dg, DG);
 #endif
         DIAG_MARK(dg, leaf, DG);
         if (fin) {
@@ -1376,20 +1410,42 @@ static int wf_lds_blocks(size_t bytes) {
 // the scene kind a kernel instance is built for (k_extend / k_shadow SK)
 static int scene_kind(bool inst, int nslot) { return inst ? WF_SK_INST : (nslot > 0 ? WF_SK_SLDS : WF_SK_FLAT); }
 
-template <int SK>
+// The node format of the instance launched for scene kind SK (k_extend / k_shadow NF): a flat scene's
+// in-place and queue instances without STATS, START or LIST are built per format, FP16 nodes when the
+// context has them (fp16: WfParams::nodes_h), FP32 under MFX_NODE_F32; every other instance takes either
+template <int SK, bool STATS, bool START, bool LIST>
+static constexpr bool wf_nf_fixed() { return SK == WF_SK_FLAT && !STATS && !START && !LIST; }
+static bool wf_fp16(const WfParams& P) {
+#if MFX_NODE_F16
+    return P.nodes_h != nullptr;
+#else
+    return false;
+#endif
+}
+
+// the instance a launch of this shape runs (the 4-wave k_shadow: ctx_setup chooses the 3-wave build from
+// its answer; k_extend's bounce instance, or for the kinds without per-format instances the START
+// one: a superset of the bounce instance's code)
+template <int SK, int NF>
 static const void* occ_kernel(bool shadow, bool spill) {
     if (shadow)
-        return spill ? (const void*)k_shadow<false, true, 4, SK, false> : (const void*)k_shadow<false, false, 4, SK, false>;
-    // (the START instance: a superset of the bounce instance's code)
-    return spill ? (const void*)k_extend<false, true, SK, false, true> : (const void*)k_extend<false, false, SK, false, true>;
+        return spill ? (const void*)k_shadow<false, true, 4, SK, false, false, NF>
+                     : (const void*)k_shadow<false, false, 4, SK, false, false, NF>;
+    constexpr bool START = NF == MFX_NF_ANY;
+    return spill ? (const void*)k_extend<false, true, SK, false, START, false, NF>
+                 : (const void*)k_extend<false, false, SK, false, START, false, NF>;
 }
 
 hipError_t mfx_wf_kernel_occupancy(bool shadow, int stack_lds, bool spill, int ntop, int ninst, int* blocks_per_cu,
-                                   int nslot) {
+                                   int nslot, bool fp16) {
     const size_t lds = wf_lds_bytes(stack_lds, shadow, ntop, std::min(ninst, WF_INST_LDS), nslot);
     const int sk = scene_kind(ninst > 0, nslot);
-    const void* k = sk == WF_SK_INST ? occ_kernel<WF_SK_INST>(shadow, spill)
-                                     : (sk == WF_SK_SLDS ? occ_kernel<WF_SK_SLDS>(shadow, spill) : occ_kernel<WF_SK_FLAT>(shadow, spill));
+    const void* k = sk == WF_SK_INST ? occ_kernel<WF_SK_INST, MFX_NF_ANY>(shadow, spill)
+                    : sk == WF_SK_SLDS ? occ_kernel<WF_SK_SLDS, MFX_NF_ANY>(shadow, spill)
+#if MFX_NODE_F16
+                    : fp16 ? occ_kernel<WF_SK_FLAT, MFX_NF_H>(shadow, spill)
+#endif
+                           : occ_kernel<WF_SK_FLAT, MFX_NF_F32>(shadow, spill);
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k, 256, lds);
     *blocks_per_cu = std::min(*blocks_per_cu, wf_lds_blocks(lds));
     return e;
@@ -1397,10 +1453,18 @@ hipError_t mfx_wf_kernel_occupancy(bool shadow, int stack_lds, bool spill, int n
 
 template <bool SPILL, int SK, bool Q, bool START = false, bool LIST = false>
 static void launch_extend_q(const WfParams& P, int grid, bool stats, hipStream_t st, size_t lds) {
-    if (stats)
+    if (stats) {
         hipLaunchKernelGGL((k_extend<true, SPILL, SK, Q, START, LIST>), dim3(grid), dim3(256), lds, st, P);
-    else
+    } else if constexpr (wf_nf_fixed<SK, false, START, LIST>()) {
+#if MFX_NODE_F16
+        if (wf_fp16(P))
+            hipLaunchKernelGGL((k_extend<false, SPILL, SK, Q, START, LIST, MFX_NF_H>), dim3(grid), dim3(256), lds, st, P);
+        else
+#endif
+            hipLaunchKernelGGL((k_extend<false, SPILL, SK, Q, START, LIST, MFX_NF_F32>), dim3(grid), dim3(256), lds, st, P);
+    } else {
         hipLaunchKernelGGL((k_extend<false, SPILL, SK, Q, START, LIST>), dim3(grid), dim3(256), lds, st, P);
+    }
 }
 template <bool SPILL, int SK>
 static void launch_extend(const WfParams& P, int grid, bool stats, hipStream_t st, size_t lds) {
@@ -1418,10 +1482,18 @@ static void launch_shadow_q(const WfParams& P, int grid, bool stats, hipStream_t
             hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q, true>), dim3(grid), dim3(256), lds, st, P);
         return;
     }
-    if (stats)
+    if (stats) {
         hipLaunchKernelGGL((k_shadow<true, SPILL, WAVES, SK, Q>), dim3(grid), dim3(256), lds, st, P);
-    else
+    } else if constexpr (wf_nf_fixed<SK, false, false, false>()) {
+#if MFX_NODE_F16
+        if (wf_fp16(P))
+            hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q, false, MFX_NF_H>), dim3(grid), dim3(256), lds, st, P);
+        else
+#endif
+            hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q, false, MFX_NF_F32>), dim3(grid), dim3(256), lds, st, P);
+    } else {
         hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q>), dim3(grid), dim3(256), lds, st, P);
+    }
 }
 // MFX_SHADOW_Q_WAVES=3 (an A/B knob, VERDICT r05 Next #7): the queue instances of a 4-wave k_shadow
 // run the 3-wave build instead (no scratch spill; 3 of the grid's 4 blocks per CU)
