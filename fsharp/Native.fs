@@ -142,6 +142,21 @@ type MfxDenoiseCfg =
     val mutable sigmaAlbedo : float
     val mutable sigmaColor : float
 
+/// mfx_denoise_var_cfg (56 B): iterations 1..8, source (MFX_DN_SRC_HOST = 0: a host frame and variance,
+/// MFX_DN_SRC_ADAPTIVE = 2: the last mfx_sample_adaptive's result on the device), reserved 0, the four
+/// sigmas of mfx_denoise_var (finite, >= 0; 0 switches the term off) and its luminance floor (finite, > 0)
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type MfxDenoiseVarCfg =
+    val mutable iterations : int32
+    val mutable source : int32
+    val mutable reserved0 : int32
+    val mutable reserved1 : int32
+    val mutable sigmaNormal : float
+    val mutable sigmaDepth : float
+    val mutable sigmaAlbedo : float
+    val mutable sigmaLuma : float
+    val mutable lumaFloor : float
+
 // ---- entry points --------------------------------------------------------------------------------
 
 module Api =
@@ -157,6 +172,8 @@ module Api =
     extern int mfx_aov(nativeint ctx, int spp, int64 sampleBase, float[] outXmajor, nativeint ms)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
     extern int mfx_denoise(nativeint ctx, MfxDenoiseCfg& cfg, nativeint colorIn, nativeint outXmajorRgba, byte[] rgbaYmajor, nativeint ms)
+    [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
+    extern int mfx_denoise_var(nativeint ctx, MfxDenoiseVarCfg& cfg, nativeint colorIn, nativeint varianceIn, nativeint outXmajorRgba, nativeint varOut, byte[] rgbaYmajor, nativeint ms)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
     extern int mfx_render_rgba8(nativeint ctx, int spp, byte[] rgbaYmajor)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
@@ -377,6 +394,29 @@ type NativePixelIntegrator(shapes : IHitable[], light : INewLight, camera : ICam
         try
             let p = h.AddrOfPinnedObject()
             check (Api.mfx_denoise(ctx, &dn, p, p, null, 0n)) "mfx_denoise"
+        finally
+            h.Free()
+        texture
+    /// Filters the last SampleAdaptive's result, as it lies on the GPU, with the variance-guided a-trous
+    /// filter (mfx_denoise_var from MFX_DN_SRC_ADAPTIVE; the rule is stated in include/mafrix_rt.h) into the
+    /// integrator's texture: beside Denoise's feature terms, a luminance term scaled by each pixel's own
+    /// variance keeps the edges no feature marks. Needs an Aov call, and SampleAdaptive as the last call
+    /// that traced. A sigma of 0 switches its term off. One device only (a device list is refused).
+    member this.DenoiseVariance(iterations : int, sigmaNormal : float, sigmaDepth : float, sigmaAlbedo : float,
+                                sigmaLuma : float, lumaFloor : float) =
+        let mutable dv = MfxDenoiseVarCfg()
+        dv.iterations <- iterations
+        dv.source <- 2
+        dv.reserved0 <- 0
+        dv.reserved1 <- 0
+        dv.sigmaNormal <- sigmaNormal
+        dv.sigmaDepth <- sigmaDepth
+        dv.sigmaAlbedo <- sigmaAlbedo
+        dv.sigmaLuma <- sigmaLuma
+        dv.lumaFloor <- lumaFloor
+        let h = GCHandle.Alloc(data, GCHandleType.Pinned)
+        try
+            check (Api.mfx_denoise_var(ctx, &dv, 0n, 0n, h.AddrOfPinnedObject(), 0n, null, 0n)) "mfx_denoise_var"
         finally
             h.Free()
         texture

@@ -286,8 +286,8 @@ int mfx_aov(mfx_ctx* ctx, int32_t spp, int64_t sample_base, double* out_xmajor, 
  * The next iteration reads this output. Everything is FP64, one rounding per operation, no
  * contraction, and the weights are rational (+ - * / only, no exp), so a host statement of the rule
  * (mafrixraytracing_amd/denoise.py) gives the same bits. With every sigma 0 it is the plain B3-spline
- * a-trous transform's smoothing. There is no variance term: soft shadow edges, which no feature
- * marks, blur as iterations grow.                                                                 */
+ * a-trous transform's smoothing. There is no variance term here: soft shadow edges, which no feature
+ * marks, blur as iterations grow (mfx_denoise_var below has one).                                 */
 #define MFX_DN_SRC_HOST  0  /* color_in: a host frame in mfx_sample's layout (alpha ignored) */
 #define MFX_DN_SRC_ACCUM 1  /* the context's accumulator / count (mfx_accum_read_mean's value); color_in NULL */
 typedef struct mfx_denoise_cfg {
@@ -304,6 +304,52 @@ typedef struct mfx_denoise_cfg {
  * count <= 0. MFX_E_STATE: as mfx_aov, and additionally when mfx_aov has not run on this context. */
 int mfx_denoise(mfx_ctx* ctx, const mfx_denoise_cfg* cfg, const double* color_in,
                 double* out_xmajor_rgba, uint8_t* rgba_ymajor, double* ms);
+
+/* mfx_denoise_var: mfx_denoise's filter with a variance-guided luminance term, and the composition
+ * of the adaptive sampler with it on the device. Additive in ABI 6.
+ * C, N, Z, A, d2 and k are mfx_denoise's; V is the current variance of the pixel's mean luminance
+ * (one plane; at first the source's), L(c) = (c0 + c1) + c2, k3 = [1/2, 1/4].
+ * For iteration i = 0 .. iterations-1 with step s = 2^i, for pixel p = (x, y):
+ *   1. variance prefilter, only when sigma_luma > 0: pn = pd = +0.0; for dy = -1..1 in the outer loop
+ *      and dx = -1..1 in the inner one, q = (x + dx, y + dy) (always one pixel apart, whatever s is; a
+ *      tap outside the film is skipped): kk = k3[|dx|] * k3[|dy|]; pn = pn + kk * V_q; pd = pd + kk.
+ *      Vf = pn / pd;  lden = (sigma_luma*sigma_luma) * Vf + luma_floor.
+ *   2. taps q = (x + dx*s, y + dy*s) exactly as in mfx_denoise (dy outer, dx inner, outside skipped):
+ *      g = 1.0, then the normal, depth and albedo terms as there and in that order, then, if
+ *      sigma_luma > 0:  dl = L(C_p) - L(C_q); term = (dl*dl) / lden; g = g * (1.0 / (1.0 + term)).
+ *   3. wt = (k[|dx|] * k[|dy|]) * g;  num_c = num_c + wt * C_q[c], den = den + wt and
+ *      vn = vn + (wt*wt) * V_q, all from +0.0 in tap order;  out_c = num_c / den,
+ *      V'_p = vn / (den*den). The next iteration reads C' and V'.
+ * FP64, one rounding per operation, no contraction, rational weights: the host statement
+ * (mafrixraytracing_amd/denoise.py, reference_denoise_var) gives the same bits. With sigma_luma = 0
+ * the colour is mfx_denoise's with sigma_color = 0 on the same frame and features, bit for bit; the
+ * variance is still propagated. A pixel whose neighbourhood is noisy (large Vf) takes its
+ * neighbours' luminance as it comes; one whose samples agree keeps an edge no feature marks.        */
+#define MFX_DN_SRC_ADAPTIVE 2  /* the last mfx_sample_adaptive's result, on the device */
+typedef struct mfx_denoise_var_cfg {
+    int32_t iterations;   /* 1..8 */
+    int32_t source;       /* MFX_DN_SRC_HOST or MFX_DN_SRC_ADAPTIVE */
+    int32_t reserved[2];  /* 0 */
+    double sigma_normal, sigma_depth, sigma_albedo, sigma_luma; /* finite, >= 0; 0 switches the term off */
+    double luma_floor;    /* finite, > 0 */
+} mfx_denoise_var_cfg;    /* 56 bytes */
+/* MFX_DN_SRC_HOST: color_in is a frame in mfx_sample's layout (alpha ignored), variance_in[x*h + y]
+ * w*h doubles (expected >= 0, not validated); both are required. MFX_DN_SRC_ADAPTIVE: both must be
+ * NULL; with n = (double)tile_spp[tile of the pixel], C = accum / n (the frame mfx_sample_adaptive
+ * returned) and, from the moment planes, d = S2 - (S1*S1)/n, V = (d > 0 ? d : +0.0) / (n*(n - 1.0)):
+ * the tile check's v_p.
+ * out_xmajor_rgba, rgba_ymajor and ms are mfx_denoise's; var_out[x*h + y] is the last iteration's V'.
+ * Each output may be NULL. The call changes no context state but buffers of its own (allocated at
+ * its first call: two variance planes, and the colour buffers it shares with mfx_denoise): the
+ * accumulator, the moment planes, the tiles' counts, the film, next_sample and every ray counter
+ * are left untouched.
+ * MFX_E_INVALID: a NULL ctx or cfg, a bad struct, pointers that do not fit the source.
+ * MFX_E_STATE: as mfx_aov; when mfx_aov has not run on this context; MFX_DN_SRC_ADAPTIVE when the
+ * accumulator does not hold an mfx_sample_adaptive result (none yet, or a trace, mfx_accum_clear or
+ * mfx_accum_attach since).                                                                        */
+int mfx_denoise_var(mfx_ctx* ctx, const mfx_denoise_var_cfg* cfg, const double* color_in,
+                    const double* variance_in, double* out_xmajor_rgba, double* var_out,
+                    uint8_t* rgba_ymajor, double* ms);
 
 /* == Film.GetFrame(integrator, spp) + Scene.PostProcessAndToScreenBuffer
  * (Film.fs:18-34, Scene.fs:315-333): adds spp samples per pixel to the film, then writes the

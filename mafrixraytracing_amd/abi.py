@@ -29,6 +29,7 @@ MFX_INSTANCE_VERBATIM = 1
 MFX_MAX_DEVICES = 64
 MFX_DN_SRC_HOST = 0
 MFX_DN_SRC_ACCUM = 1
+MFX_DN_SRC_ADAPTIVE = 2
 MFX_ABI_VERSION = 6
 # mfx_launch_info's entries, in order (MFX_LAUNCH_INFO_N of them)
 LAUNCH_INFO_KEYS = ("stack_size", "stack_lds_ext", "stack_lds_shd", "spill_ext", "spill_shd", "ntop_ext", "ntop_shd",
@@ -87,10 +88,18 @@ class MfxDenoiseCfg(C.Structure):
                 ("sigma_albedo", C.c_double), ("sigma_color", C.c_double)]
 
 
+class MfxDenoiseVarCfg(C.Structure):
+    """mfx_denoise_var_cfg: iterations, source, the four sigmas and the luminance floor of mfx_denoise_var."""
+    _fields_ = [("iterations", C.c_int32), ("source", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("sigma_normal", C.c_double), ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double),
+                ("sigma_luma", C.c_double), ("luma_floor", C.c_double)]
+
+
 assert C.sizeof(MfxPrim) == 104
 assert C.sizeof(MfxInstance) == 48
 assert C.sizeof(MfxAdaptive) == 32
 assert C.sizeof(MfxDenoiseCfg) == 56
+assert C.sizeof(MfxDenoiseVarCfg) == 56
 
 # numpy structured dtype with the same layout as mfx_prim (for building big prim arrays fast)
 PRIM_DTYPE = np.dtype([("kind", "<i4"), ("material", "<i4"), ("p", "<f8", (4, 3))], align=True)
@@ -175,6 +184,7 @@ def _bind(lib, strict: bool = True):
         "mfx_sample_adaptive": (C.c_int, [C.c_void_p, _P(MfxAdaptive), _dp, _ip, _P(C.c_uint8)]),
         "mfx_aov": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp]),
         "mfx_denoise": (C.c_int, [C.c_void_p, _P(MfxDenoiseCfg), _dp, _dp, _P(C.c_uint8), _dp]),
+        "mfx_denoise_var": (C.c_int, [C.c_void_p, _P(MfxDenoiseVarCfg), _dp, _dp, _dp, _dp, _P(C.c_uint8), _dp]),
         "mfx_render_rgba8": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint8)]),
         "mfx_accumulate_render_rgba8": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint8)]),
         "mfx_stats": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -215,7 +225,7 @@ def _bind(lib, strict: bool = True):
 
 
 EXPORTED_SYMBOLS = [
-    "mfx_create", "mfx_create_instanced", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_aov", "mfx_denoise", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
+    "mfx_create", "mfx_create_instanced", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
     "mfx_film_mean", "mfx_stats",
     "mfx_trace_accumulate", "mfx_accum_clear", "mfx_accum_reduce", "mfx_accum_device_ptr", "mfx_accum_attach", "mfx_accum_read_mean",
     "mfx_sync", "mfx_stream", "mfx_ray_counts", "mfx_last_trace_ms", "mfx_trace_timing", "mfx_ray_counts_total", "mfx_closest_hit", "mfx_any_hit", "mfx_ref_leaves",

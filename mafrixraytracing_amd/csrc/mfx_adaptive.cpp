@@ -134,5 +134,6 @@ extern "C" int mfx_sample_adaptive(mfx_ctx* c, const mfx_adaptive* a, double* fr
     for (int k = 0; k < 8; ++k) c->rep_timing[k] = stage[k];
     c->rep_ms = ms;
     c->rep_valid = true;
+    ad.accum_valid = true;  // the accumulator, the moments and tile_spp belong together (mfx_denoise_var's device source)
     return MFX_OK;
 }

@@ -239,14 +239,18 @@ struct Adaptive {
     DevBuf<int32_t> tile_count;   // [1] tiles that go on
     Event ev0, ev1;               // around a pass (trace, check) and the mean
     bool check = false;           // MFX_ADAPTIVE_CHECK=1: the host validates every pass's tile list
+    bool accum_valid = false;     // the accumulator, mom and tile_spp hold the last mfx_sample_adaptive's result:
+                                  // set when it succeeds, cleared by whatever else writes or swaps the accumulator
+                                  // (a trace's parameters, mfx_accum_clear, mfx_accum_attach); mfx_denoise_var reads it
     bool ready() const { return ev1 != nullptr; }  // the last one adaptive_alloc creates
 };
 
-// Feature buffers and denoising (mfx_aov, mfx_denoise); allocated at their first calls
+// Feature buffers and denoising (mfx_aov, mfx_denoise, mfx_denoise_var); allocated at their first calls
 struct Denoise {
     DevBuf<double> feat;          // [MFX_AOV_PLANES][npix] the feature planes (mfx_aov)
     DevBuf<double> feat_out;      // [npix][MFX_AOV_PLANES] staging of mfx_aov's host output
     DevBuf<double> buf[2];        // [3][npix] each: the filter's ping-pong colour buffers
+    DevBuf<double> var[2];        // [npix] each: mfx_denoise_var's ping-pong variance planes
     Event ev0, ev1;               // around either call's kernels
     bool ready() const { return feat != nullptr; }  // mfx_aov has run
 };

@@ -1,5 +1,5 @@
 // mfx_denoise.h — parameter blocks and launchers of the feature-buffer and denoising kernels
-// (mfx_denoise.hip: mfx_aov, mfx_denoise). A translation unit of its own, so the trace kernels' code
+// (mfx_denoise.hip: mfx_aov, mfx_denoise, mfx_denoise_var). A translation unit of its own, so the trace kernels' code
 // objects do not change with it.
 #ifndef MFX_DENOISE_H
 #define MFX_DENOISE_H
@@ -42,8 +42,27 @@ struct AtrousParams {
     double sc2;            // (sigma_color * sigma_color) * 0.25^i
 };
 
+// k_atrous_var: one iteration of the variance-guided filter (mfx_denoise_var; the rule: include/mafrix_rt.h)
+struct AtrousVarParams {
+    const double* src;   // [3][w*h] the current colour
+    const double* vsrc;  // [w*h] the current variance of the pixel's mean luminance
+    double* dst;         // [3][w*h] the iteration's colour
+    double* vdst;        // [w*h] and its variance
+    const double* feat;  // [MFX_AOV_PLANES][w*h]
+    int32_t width, height;
+    int32_t step;        // 2^i
+    int32_t terms;       // bit 0 normal, 1 depth, 2 albedo, 3 luminance: the terms whose sigma is > 0
+    double sn2, sz2, sa2;  // sigma * sigma
+    double sl2;            // sigma_luma * sigma_luma
+    double luma_floor;
+};
+
 hipError_t mfx_launch_aov(const AovParams& P, hipStream_t st);
 hipError_t mfx_launch_atrous(const AtrousParams& P, hipStream_t st);
+hipError_t mfx_launch_atrous_var(const AtrousVarParams& P, hipStream_t st);
+// colour planes <- accum / n, variance plane <- max(0, S2 - S1*S1/n) / (n (n - 1)), n = tile_spp[the pixel's tile]
+hipError_t mfx_launch_dn_from_adaptive(const double* accum, const double* mom, const int32_t* tile_spp, int w, int h,
+                                       double* dst, double* vdst, hipStream_t st);
 // colour planes <- accum / n (mfx_accum_read_mean's value)
 hipError_t mfx_launch_dn_from_accum(const double* accum, int64_t npix, double n, double* dst, hipStream_t st);
 // colour planes <- an x-major RGBA frame (alpha dropped)

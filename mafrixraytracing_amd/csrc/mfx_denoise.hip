@@ -1,6 +1,7 @@
 // mfx_denoise.hip — gfx950 kernels of mfx_aov (first-hit feature buffers of the film's own camera
-// rays) and mfx_denoise (the edge-avoiding a-trous filter they guide). The rule of both is stated in
-// include/mafrix_rt.h and, in numpy, in mafrixraytracing_amd/denoise.py.
+// rays), mfx_denoise (the edge-avoiding a-trous filter they guide) and mfx_denoise_var (that filter
+// with a variance-guided luminance term, fed by the adaptive sampler's moments). The rule of each is
+// stated in include/mafrix_rt.h and, in numpy, in mafrixraytracing_amd/denoise.py.
 //
 // Compiled with -ffp-contract=off like the rest of the library: every FP64 expression below has one
 // rounding per operation in the order written, so the device gives the host statement's bits. The
@@ -147,6 +148,119 @@ __global__ void __launch_bounds__(256) k_atrous(AtrousParams P) {
     P.dst[2 * npix + p] = n2 / den;
 }
 
+// ----------------------------------------------------------------------------------------------
+// k_atrous_var: k_atrous with the variance plane beside the colour (mfx_denoise_var). Thread
+// mapping, tap order and the feature terms are k_atrous's, statement for statement, so with the
+// luminance term off the colour is k_atrous's without its colour term, bit for bit. Before the taps a
+// thread smooths its own pixel's variance over the 3x3 pixels around it (always one pixel apart: the
+// prefilter follows the image's grid, not the iteration's step); a wave reads each of those nine taps,
+// like the 25 of every plane, as one coalesced run.
+// ----------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_atrous_var(AtrousVarParams P) {
+    const int W = P.width, H = P.height;
+    const int64_t npix = (int64_t)W * H;
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    const int x = (int)(p / H), y = (int)(p - (int64_t)x * H);
+    const double* __restrict__ C0 = P.src;
+    const double* __restrict__ C1 = P.src + npix;
+    const double* __restrict__ C2 = P.src + 2 * npix;
+    const double* __restrict__ V = P.vsrc;
+    const double* __restrict__ F = P.feat;
+    const bool tn = P.terms & 1, tz = P.terms & 2, ta = P.terms & 4, tl = P.terms & 8;
+    const double cp0 = C0[p], cp1 = C1[p], cp2 = C2[p];
+    double np0 = 0, np1 = 0, np2 = 0, zp = 0, ap0 = 0, ap1 = 0, ap2 = 0;
+    if (tn) { np0 = F[p]; np1 = F[npix + p]; np2 = F[2 * npix + p]; }
+    if (tz) zp = F[3 * npix + p];
+    if (ta) { ap0 = F[4 * npix + p]; ap1 = F[5 * npix + p]; ap2 = F[6 * npix + p]; }
+    double lp = 0.0, lden = 1.0;
+    if (tl) {
+        double pn = 0.0, pd = 0.0;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy) {
+            const int yy = y + dy;
+            if (yy < 0 || yy >= H) continue;
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int xx = x + dx;
+                if (xx < 0 || xx >= W) continue;
+                const double kk = (dx == 0 ? 0.5 : 0.25) * (dy == 0 ? 0.5 : 0.25);
+                pn = pn + kk * V[(int64_t)xx * H + yy];  // inside the film
+                pd = pd + kk;
+            }
+        }
+        const double vf = pn / pd;  // the centre tap: pd >= 1/4
+        lden = P.sl2 * vf + P.luma_floor;
+        lp = (cp0 + cp1) + cp2;
+    }
+    double n0 = 0.0, n1 = 0.0, n2 = 0.0, den = 0.0, vn = 0.0;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int yy = y + dy * P.step;
+        if (yy < 0 || yy >= H) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int xx = x + dx * P.step;
+            if (xx < 0 || xx >= W) continue;
+            const int64_t q = (int64_t)xx * H + yy;  // inside the film: 0 <= q < npix
+            const double cq0 = C0[q], cq1 = C1[q], cq2 = C2[q];
+            const double vq = V[q];
+            double g = 1.0;
+            if (tn) {
+                const double term = d2(np0, np1, np2, F[q], F[npix + q], F[2 * npix + q]) / P.sn2;
+                g = g * (1.0 / (1.0 + term));
+            }
+            if (tz) {
+                const double zq = F[3 * npix + q];
+                const double dz = zp - zq;
+                const double dd = P.sz2 * (zp * zp + zq * zq);
+                const double term = dd > 0.0 ? (dz * dz) / dd : 0.0;
+                g = g * (1.0 / (1.0 + term));
+            }
+            if (ta) {
+                const double term = d2(ap0, ap1, ap2, F[4 * npix + q], F[5 * npix + q], F[6 * npix + q]) / P.sa2;
+                g = g * (1.0 / (1.0 + term));
+            }
+            if (tl) {
+                const double dl = lp - ((cq0 + cq1) + cq2);
+                const double term = (dl * dl) / lden;
+                g = g * (1.0 / (1.0 + term));
+            }
+            const double kx = dx == 0 ? 0.375 : (dx == 1 || dx == -1) ? 0.25 : 0.0625;
+            const double ky = dy == 0 ? 0.375 : (dy == 1 || dy == -1) ? 0.25 : 0.0625;
+            const double wt = (kx * ky) * g;
+            n0 = n0 + wt * cq0;
+            n1 = n1 + wt * cq1;
+            n2 = n2 + wt * cq2;
+            den = den + wt;
+            vn = vn + (wt * wt) * vq;
+        }
+    }
+    // the centre tap has g = 1: den >= 9/64
+    P.dst[p] = n0 / den;
+    P.dst[npix + p] = n1 / den;
+    P.dst[2 * npix + p] = n2 / den;
+    P.vdst[p] = vn / (den * den);
+}
+
+// colour planes <- accum / n and variance plane <- the tile check's v_p, n the pixel's own tile's count
+// (adaptive_mean_kernel's and k_tile_check's statements)
+__global__ void k_dn_from_adaptive(const double* __restrict__ accum, const double* __restrict__ mom,
+                                   const int32_t* __restrict__ tile_spp, int w, int h, double* __restrict__ dst,
+                                   double* __restrict__ vdst) {
+    const int64_t npix = (int64_t)w * h;
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= npix) return;
+    const int x = (int)(q / h), y = (int)(q % h);
+    const double n = (double)tile_spp[(y >> 3) * ((w + 7) >> 3) + (x >> 3)];
+    dst[q] = accum[q] / n;
+    dst[npix + q] = accum[npix + q] / n;
+    dst[2 * npix + q] = accum[2 * npix + q] / n;
+    const double s1 = mom[q], s2 = mom[npix + q];
+    const double d = s2 - s1 * s1 / n;
+    vdst[q] = (d > 0.0 ? d : 0.0) / (n * (n - 1.0));
+}
+
 __global__ void k_dn_from_accum(const double* __restrict__ accum, int64_t npix, double n, double* __restrict__ dst) {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= npix) return;
@@ -200,6 +314,18 @@ hipError_t mfx_launch_aov(const AovParams& P, hipStream_t st) {
 
 hipError_t mfx_launch_atrous(const AtrousParams& P, hipStream_t st) {
     hipLaunchKernelGGL(k_atrous, dim3(dn_grid((int64_t)P.width * P.height, 256)), dim3(256), 0, st, P);
+    return hipGetLastError();
+}
+
+hipError_t mfx_launch_atrous_var(const AtrousVarParams& P, hipStream_t st) {
+    hipLaunchKernelGGL(k_atrous_var, dim3(dn_grid((int64_t)P.width * P.height, 256)), dim3(256), 0, st, P);
+    return hipGetLastError();
+}
+
+hipError_t mfx_launch_dn_from_adaptive(const double* accum, const double* mom, const int32_t* tile_spp, int w, int h,
+                                       double* dst, double* vdst, hipStream_t st) {
+    hipLaunchKernelGGL(k_dn_from_adaptive, dim3(dn_grid((int64_t)w * h, 256)), dim3(256), 0, st, accum, mom, tile_spp, w, h,
+                       dst, vdst);
     return hipGetLastError();
 }
 

@@ -1,9 +1,11 @@
 // mfx_denoise_api.cpp — feature buffers and denoising.
 // mfx_aov traces the film's own camera rays once more, per lane (k_aov), into eight FP64 planes that
 // stay on the device; mfx_denoise runs one k_atrous launch per iteration between two colour buffers,
-// guided by those planes (the rule: include/mafrix_rt.h). Both launch on the context's stream and
-// touch nothing the trace calls keep: not the accumulator, the film, the moment planes, the sample
-// counter, the ray counters or held render-ahead frames.
+// guided by those planes (the rule: include/mafrix_rt.h); mfx_denoise_var runs k_atrous_var the same way
+// with a variance plane beside each colour buffer, filled from the host or from the last
+// mfx_sample_adaptive's accumulator, moments and tile counts (read only). All launch on the context's
+// stream and touch nothing the trace calls keep: not the accumulator, the film, the moment planes, the
+// sample counter, the ray counters or held render-ahead frames.
 #include "mfx_ctx.h"
 
 using namespace mfxh;
@@ -112,6 +114,73 @@ extern "C" int mfx_denoise(mfx_ctx* c, const mfx_denoise_cfg* a, const double* c
                                     c->stream));
     HIPCHECK(hipEventRecord(dn.ev1, c->stream));
     if (out) MFX_TRY(host_readback(c, out, c->d_frame, 4 * sizeof(double) * (size_t)c->npix, c->stream));
+    if (rgba) MFX_TRY(host_readback(c, rgba, c->d_rgba, 4 * (size_t)c->npix, c->stream));
+    return dn_finish(c, ms);
+}
+
+extern "C" int mfx_denoise_var(mfx_ctx* c, const mfx_denoise_var_cfg* a, const double* color_in, const double* variance_in,
+                               double* out, double* var_out, uint8_t* rgba, double* ms) {
+    if (!c || !a) return fail(MFX_E_INVALID, "mfx_denoise_var: null argument");
+    if (a->iterations < 1 || a->iterations > 8 || a->reserved[0] != 0 || a->reserved[1] != 0)
+        return fail(MFX_E_INVALID, "mfx_denoise_var: need 1 <= iterations <= 8 and reserved 0");
+    if (a->source != MFX_DN_SRC_HOST && a->source != MFX_DN_SRC_ADAPTIVE)
+        return fail(MFX_E_INVALID, "mfx_denoise_var: unknown source");
+    for (double s : {a->sigma_normal, a->sigma_depth, a->sigma_albedo, a->sigma_luma})
+        if (!(s >= 0.0) || !std::isfinite(s)) return fail(MFX_E_INVALID, "mfx_denoise_var: every sigma must be finite and >= 0");
+    if (!(a->luma_floor > 0.0) || !std::isfinite(a->luma_floor))
+        return fail(MFX_E_INVALID, "mfx_denoise_var: luma_floor must be finite and > 0");
+    const bool host = a->source == MFX_DN_SRC_HOST;
+    if (host && (!color_in || !variance_in))
+        return fail(MFX_E_INVALID, "mfx_denoise_var: MFX_DN_SRC_HOST needs color_in and variance_in");
+    if (!host && (color_in || variance_in))
+        return fail(MFX_E_INVALID, "mfx_denoise_var: MFX_DN_SRC_ADAPTIVE takes no color_in or variance_in");
+    MFX_TRY(whole_film_single_device(c, "mfx_denoise_var"));
+    Denoise& dn = c->dn;
+    if (!dn.ready()) return fail(MFX_E_STATE, "mfx_denoise_var: no feature buffers (call mfx_aov on this context first)");
+    if (!host && !c->adp.accum_valid)
+        return fail(MFX_E_STATE, "mfx_denoise_var: the accumulator does not hold an mfx_sample_adaptive result");
+    HIPCHECK(hipSetDevice(c->device));
+    for (int k = 0; k < 2; ++k) {
+        MFX_TRY(dn_alloc(dn.buf[k], 3 * (size_t)c->npix, "mfx_denoise_var"));
+        MFX_TRY(dn_alloc(dn.var[k], (size_t)c->npix, "mfx_denoise_var"));
+    }
+    MFX_TRY(dn_events(c));
+    const int W = c->host.width, H = c->host.height;
+    if (host) {  // staged before the timed part: the frame through the x-major frame buffer, the variance as the plane it is
+        HIPCHECK(hipMemcpyAsync(c->d_frame, color_in, 4 * sizeof(double) * (size_t)c->npix, hipMemcpyHostToDevice, c->stream));
+        HIPCHECK(hipMemcpyAsync(dn.var[0], variance_in, sizeof(double) * (size_t)c->npix, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHECK(hipEventRecord(dn.ev0, c->stream));
+    if (host) HIPCHECK(mfx_launch_dn_from_frame(c->d_frame, c->npix, dn.buf[0], c->stream));
+    else HIPCHECK(mfx_launch_dn_from_adaptive(c->d_accum, c->adp.mom, c->adp.tile_spp, W, H, dn.buf[0], dn.var[0], c->stream));
+    AtrousVarParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.feat = dn.feat;
+    P.width = W;
+    P.height = H;
+    P.terms = (a->sigma_normal > 0.0 ? 1 : 0) | (a->sigma_depth > 0.0 ? 2 : 0) | (a->sigma_albedo > 0.0 ? 4 : 0) |
+              (a->sigma_luma > 0.0 ? 8 : 0);
+    P.sn2 = a->sigma_normal * a->sigma_normal;
+    P.sz2 = a->sigma_depth * a->sigma_depth;
+    P.sa2 = a->sigma_albedo * a->sigma_albedo;
+    P.sl2 = a->sigma_luma * a->sigma_luma;
+    P.luma_floor = a->luma_floor;
+    int cur = 0;
+    for (int i = 0; i < a->iterations; ++i) {
+        P.src = dn.buf[cur];
+        P.vsrc = dn.var[cur];
+        P.dst = dn.buf[cur ^ 1];
+        P.vdst = dn.var[cur ^ 1];
+        P.step = 1 << i;
+        HIPCHECK(mfx_launch_atrous_var(P, c->stream));
+        cur ^= 1;
+    }
+    if (out || rgba)
+        HIPCHECK(mfx_launch_dn_post(dn.buf[cur], W, H, out ? c->d_frame.get() : nullptr, rgba ? c->d_rgba.get() : nullptr,
+                                    c->stream));
+    HIPCHECK(hipEventRecord(dn.ev1, c->stream));
+    if (out) MFX_TRY(host_readback(c, out, c->d_frame, 4 * sizeof(double) * (size_t)c->npix, c->stream));
+    if (var_out) MFX_TRY(host_readback(c, var_out, dn.var[cur], sizeof(double) * (size_t)c->npix, c->stream));  // x-major as it lies
     if (rgba) MFX_TRY(host_readback(c, rgba, c->d_rgba, 4 * (size_t)c->npix, c->stream));
     return dn_finish(c, ms);
 }

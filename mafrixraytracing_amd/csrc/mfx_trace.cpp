@@ -119,11 +119,12 @@ static void wf_queue_views(mfx_ctx* c, WfParams& P, int d) {
 
 // what the wavefront's and the megakernel's parameters (WfParams, TraceParams) share
 template <typename P>
-static void fill_trace_params(const mfx_ctx* c, P& p, int64_t sample_base) {
+static void fill_trace_params(mfx_ctx* c, P& p, int64_t sample_base) {
     fill_scene_ptrs(c, p);
     p.light = c->host.light;
     p.cam = c->host.camera;
     p.accum = c->d_accum;
+    c->adp.accum_valid = false;  // a trace adds to it (mfx_sample_adaptive sets the flag after its own)
     p.seed = c->seed;
     p.sample_base = sample_base;
     p.part_index = c->part_index;
@@ -555,6 +556,7 @@ int mfx_last_trace_ms(mfx_ctx* c, double* ms) {
 int mfx_accum_clear(mfx_ctx* c) {
     if (!c) return fail(MFX_E_STATE, "null context");
     c->multi.accum_merged = false;
+    c->adp.accum_valid = false;
     for (mfx_ctx* d : devs_of(c)) {
         HIPCHECK(hipSetDevice(d->device));
         HIPCHECK(hipMemsetAsync(d->d_accum, 0, 3 * sizeof(double) * (size_t)d->npix, d->stream));
@@ -571,6 +573,7 @@ int mfx_accum_device_ptr(mfx_ctx* c, void** dptr, int64_t* nbytes) {
 
 int mfx_accum_attach(mfx_ctx* c, void* dptr, int64_t nbytes) {
     if (!c) return fail(MFX_E_STATE, "null context");
+    c->adp.accum_valid = false;
     if (!dptr) {
         c->d_accum = c->d_accum_own;
         return MFX_OK;

@@ -10,9 +10,10 @@ import ctypes as C
 
 import numpy as np
 
-from .abi import (INSTANCING_KEYS, LAUNCH_INFO_KEYS, MFX_DN_SRC_ACCUM, MFX_DN_SRC_HOST, MFX_F_NONE, MFX_F_TWO_LEVEL, MfxAdaptive,
-                  MfxDenoiseCfg, MfxInstance, MfxOptions, SceneArrays, check, dptr, iptr, load_library)
-from .denoise import DenoiseConfig
+from .abi import (INSTANCING_KEYS, LAUNCH_INFO_KEYS, MFX_DN_SRC_ACCUM, MFX_DN_SRC_ADAPTIVE, MFX_DN_SRC_HOST, MFX_F_NONE,
+                  MFX_F_TWO_LEVEL, MfxAdaptive, MfxDenoiseCfg, MfxDenoiseVarCfg, MfxInstance, MfxOptions, SceneArrays, check,
+                  dptr, iptr, load_library)
+from .denoise import DenoiseConfig, DenoiseVarConfig
 
 DEFAULT_SEED = 0x4D414652
 DEFAULT_RENDER_AHEAD = 64  # fsharp/Native.fs DefaultRenderAhead: Scene.Render served from batches of 64 samples
@@ -125,6 +126,37 @@ class NativeContext:
               "mfx_denoise")
         self.last_denoise_ms = ms.value
         return (out, rgba) if want_rgba else out
+
+    def denoise_var(self, frame: np.ndarray | None = None, variance: np.ndarray | None = None,
+                    cfg: DenoiseVarConfig = DenoiseVarConfig(), want_rgba: bool = False, want_variance: bool = False):
+        """mfx_denoise_var: the variance-guided a-trous filter (the rule: include/mafrix_rt.h,
+        mafrixraytracing_amd/denoise.py) of `frame` ((w*h, 4) x-major, alpha ignored) with `variance`
+        ((w*h,) x-major, the variance of each pixel's mean luminance), or with frame=None of the last
+        sample_adaptive's result as it lies on the device (its accumulator, moments and tile counts);
+        guided by the feature buffers of the last aov call. Returns the (w*h, 4) filtered frame, or a
+        tuple of it, the y-major RGBA8 post (want_rgba) and the (w*h,) filtered variance (want_variance)."""
+        c = MfxDenoiseVarCfg(iterations=cfg.iterations, source=MFX_DN_SRC_ADAPTIVE if frame is None else MFX_DN_SRC_HOST,
+                             sigma_normal=cfg.sigma_normal, sigma_depth=cfg.sigma_depth, sigma_albedo=cfg.sigma_albedo,
+                             sigma_luma=cfg.sigma_luma, luma_floor=cfg.luma_floor)
+        src = var = None
+        if frame is not None:
+            src = np.ascontiguousarray(frame, dtype=np.float64)
+            assert src.size == self.w * self.h * 4
+        if variance is not None:
+            var = np.ascontiguousarray(variance, dtype=np.float64)
+            assert var.size == self.w * self.h
+        out = np.empty((self.w * self.h, 4), dtype=np.float64)
+        rgba = np.empty(self.w * self.h * 4, dtype=np.uint8) if want_rgba else None
+        vout = np.empty(self.w * self.h, dtype=np.float64) if want_variance else None
+        ms = C.c_double()
+        check(self.lib.mfx_denoise_var(self._h, C.byref(c), dptr(src) if src is not None else None,
+                                       dptr(var) if var is not None else None, dptr(out),
+                                       dptr(vout) if want_variance else None,
+                                       rgba.ctypes.data_as(C.POINTER(C.c_uint8)) if want_rgba else None, C.byref(ms)),
+              "mfx_denoise_var")
+        self.last_denoise_ms = ms.value
+        res = (out,) + ((rgba,) if want_rgba else ()) + ((vout,) if want_variance else ())
+        return res if len(res) > 1 else out
 
     def render_rgba8(self, spp: int = 1, want_pixels: bool = True, out: np.ndarray | None = None) -> np.ndarray | None:
         """Film.GetFrame(spp) + post into `out` (a uint8 buffer of w*h*4, allocated if None), as

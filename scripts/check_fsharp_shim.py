@@ -338,7 +338,8 @@ class Checker:
 
         for fs, ct in [("MfxPrim", abi.MfxPrim), ("MfxQuadLight", abi.MfxQuadLight), ("MfxPinhole", abi.MfxPinhole),
                        ("MfxSceneDesc", abi.MfxSceneDesc), ("MfxOptions", abi.MfxOptions),
-                       ("MfxAdaptive", abi.MfxAdaptive), ("MfxDenoiseCfg", abi.MfxDenoiseCfg)]:
+                       ("MfxAdaptive", abi.MfxAdaptive), ("MfxDenoiseCfg", abi.MfxDenoiseCfg),
+                       ("MfxDenoiseVarCfg", abi.MfxDenoiseVarCfg)]:
             if self.own_type(fs) is None:
                 self.err(f"Native.fs: struct {fs} missing")
             elif flat_fs(fs) != flat_ct(ct):

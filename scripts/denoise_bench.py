@@ -10,7 +10,11 @@ with the FP64 frame and the RGBA8 post), and this build's uniform 64-spp trace, 
 64-spp image, and the denoised 64-spp image.
 `detail` is what the decision about LDS tiling rests on: the device ms of 1, 2, 3 and 4 iterations (an
 iteration's cost by its step: neighbouring pixels' taps overlap at steps 1 and 2, not at 4 and 8) and of
-three iterations with every sigma 0 (the same colour taps, no feature loads and no divisions per tap)."""
+three iterations with every sigma 0 (the same colour taps, no feature loads and no divisions per tap).
+The variance-guided filter (mfx_denoise_var at the default DenoiseVarConfig): `denoise_var_ms` is the
+fastest warm call from the adaptive sampler's result on the device after sample_adaptive(min = max = 8),
+`denoise_var_vs_denoise_ms` its ratio to `denoise_ms`, `rmse_var8` / `rmse_var64` the RMSE of its image
+of samples 0..7 / 0..63; `detail` has its ms by iterations and with the luminance term off."""
 import argparse
 import ctypes as C
 import json
@@ -29,8 +33,8 @@ def main():
     args = ap.parse_args()
 
     import numpy as np
-    from mafrixraytracing_amd.abi import MFX_DN_SRC_ACCUM, MfxDenoiseCfg, dptr
-    from mafrixraytracing_amd.denoise import DenoiseConfig
+    from mafrixraytracing_amd.abi import MFX_DN_SRC_ACCUM, MFX_DN_SRC_ADAPTIVE, MfxDenoiseCfg, MfxDenoiseVarCfg, dptr
+    from mafrixraytracing_amd.denoise import DenoiseConfig, DenoiseVarConfig
     from mafrixraytracing_amd.native import DEFAULT_SEED, NativeContext
     from mafrixraytracing_amd.scene_io import load_scene_file
 
@@ -92,10 +96,36 @@ def main():
             detail = {"ms_by_iterations": [variant(iterations=n) for n in (1, 2, 3, 4)],
                       "ms_all_sigmas_0": variant(sigma_normal=0.0, sigma_depth=0.0, sigma_albedo=0.0),
                       "ms_normal_only": variant(sigma_depth=0.0, sigma_albedo=0.0)}
+    # the variance-guided filter from the adaptive sampler's result on the device (min = max: uniform
+    # counts, the same samples 0..spp-1 as the images above)
+    dv = DenoiseVarConfig()
+    for spp in (8, 64):
+        with NativeContext(a, seed=DEFAULT_SEED) as ctx:
+            ctx.aov(args.aov_spp)
+            ctx.sample_adaptive(spp, spp, 1, 0.0, 0.0)
+            res[spp]["var_rmse"] = rmse(ctx.denoise_var(None, cfg=dv))
+            if spp != 8:
+                continue
+
+            def var_variant(**kw):
+                d = dict(iterations=dv.iterations, source=MFX_DN_SRC_ADAPTIVE, sigma_normal=dv.sigma_normal,
+                         sigma_depth=dv.sigma_depth, sigma_albedo=dv.sigma_albedo, sigma_luma=dv.sigma_luma,
+                         luma_floor=dv.luma_floor)
+                d.update(kw)
+                v = MfxDenoiseVarCfg(**d)
+                return timed(lambda ms: ctx.lib.mfx_denoise_var(ctx._h, C.byref(v), None, None, None, None, None, ms))
+
+            dnv_ms = var_variant()
+            detail["var_ms_by_iterations"] = [round(var_variant(iterations=n), 3) for n in (1, 2, 3, 4)]
+            detail["var_ms_sigma_luma_0"] = round(var_variant(sigma_luma=0.0), 3)
     out = {"workload": f"C2 spot {w}x{h}", "aov_spp": args.aov_spp, "aov_ms": round(aov_ms, 3),
            "denoise": {"iterations": dc.iterations, "sigma_normal": dc.sigma_normal, "sigma_depth": dc.sigma_depth,
                        "sigma_albedo": dc.sigma_albedo, "sigma_color": dc.sigma_color},
            "denoise_ms": round(dn_ms, 3), "denoise_ms_with_outputs": round(dn_out_ms, 3),
+           "denoise_var": {"iterations": dv.iterations, "sigma_normal": dv.sigma_normal, "sigma_depth": dv.sigma_depth,
+                           "sigma_albedo": dv.sigma_albedo, "sigma_luma": dv.sigma_luma, "luma_floor": dv.luma_floor},
+           "denoise_var_ms": round(dnv_ms, 3), "denoise_var_vs_denoise_ms": round(dnv_ms / dn_ms, 4),
+           "rmse_var8": res[8]["var_rmse"], "rmse_var64": res[64]["var_rmse"],
            "uniform64_trace_ms": round(uniform64_ms, 3),
            "aov_plus_denoise_vs_uniform64": round((aov_ms + dn_ms) / uniform64_ms, 4),
            "reference_spp": args.ref_spp, "hit_fraction": round(hit_fraction, 4),
