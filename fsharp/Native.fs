@@ -127,6 +127,17 @@ type MfxAdaptive =
     val mutable relError : float
     val mutable absFloor : float
 
+/// mfx_adaptive_resume (32 B): the budget (maxSpp >= 2, stepSpp >= 1), the pass limit (maxPasses >= 0, 0: none),
+/// reserved 0 and the threshold of mfx_sample_adaptive_resume (relError, absFloor: finite, >= 0)
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type MfxAdaptiveResume =
+    val mutable maxSpp : int32
+    val mutable stepSpp : int32
+    val mutable maxPasses : int32
+    val mutable reserved : int32
+    val mutable relError : float
+    val mutable absFloor : float
+
 /// mfx_denoise_cfg (56 B): iterations 1..8, source (MFX_DN_SRC_HOST = 0: a host frame, MFX_DN_SRC_ACCUM = 1:
 /// the accumulator / count), reserved 0, and the four sigmas of mfx_denoise (finite, >= 0; 0 switches
 /// the term off)
@@ -143,7 +154,7 @@ type MfxDenoiseCfg =
     val mutable sigmaColor : float
 
 /// mfx_denoise_var_cfg (56 B): iterations 1..8, source (MFX_DN_SRC_HOST = 0: a host frame and variance,
-/// MFX_DN_SRC_ADAPTIVE = 2: the last mfx_sample_adaptive's result on the device), reserved 0, the four
+/// MFX_DN_SRC_ADAPTIVE = 2: the last mfx_sample_adaptive's result, as resumed since, on the device), reserved 0, the four
 /// sigmas of mfx_denoise_var (finite, >= 0; 0 switches the term off) and its luminance floor (finite, > 0)
 [<Struct; StructLayout(LayoutKind.Sequential)>]
 type MfxDenoiseVarCfg =
@@ -168,6 +179,8 @@ module Api =
     extern int mfx_sample(nativeint ctx, int spp, nativeint frameXmajorRgba)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
     extern int mfx_sample_adaptive(nativeint ctx, MfxAdaptive& cfg, nativeint frameXmajorRgba, int[] tileSpp, byte[] rgbaYmajor)
+    [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
+    extern int mfx_sample_adaptive_resume(nativeint ctx, MfxAdaptiveResume& cfg, nativeint frameXmajorRgba, int[] tileSpp, byte[] rgbaYmajor, int& activeOut)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
     extern int mfx_aov(nativeint ctx, int spp, int64 sampleBase, float[] outXmajor, nativeint ms)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
@@ -368,6 +381,28 @@ type NativePixelIntegrator(shapes : IHitable[], light : INewLight, camera : ICam
         finally
             h.Free()
         texture, counts
+    /// Continues the adaptive result the context holds (mfx_sample_adaptive_resume; the rule is stated in
+    /// include/mafrix_rt.h) under this call's threshold and budget: every tile that fails the test at its
+    /// own count gets stepSpp more samples at a time, up to maxSpp, for at most maxPasses passes (0: until
+    /// no tile is active). Returns the integrator's texture, the tiles' current counts and the number of
+    /// tiles that would go on. Needs SampleAdaptive (or this) as the last call that traced; the sample
+    /// counter advances only by what maxSpp adds to the budget reserved so far.
+    member this.SampleAdaptiveResume(maxSpp : int, stepSpp : int, maxPasses : int, relError : float, absFloor : float) =
+        let counts : int[] = Array.zeroCreate (((width + 7) / 8) * ((height + 7) / 8))
+        let mutable rcfg = MfxAdaptiveResume()
+        rcfg.maxSpp <- maxSpp
+        rcfg.stepSpp <- stepSpp
+        rcfg.maxPasses <- maxPasses
+        rcfg.reserved <- 0
+        rcfg.relError <- relError
+        rcfg.absFloor <- absFloor
+        let mutable active = 0
+        let h = GCHandle.Alloc(data, GCHandleType.Pinned)
+        try
+            check (Api.mfx_sample_adaptive_resume(ctx, &rcfg, h.AddrOfPinnedObject(), counts, null, &active)) "mfx_sample_adaptive_resume"
+        finally
+            h.Free()
+        texture, counts, active
     /// First-hit features of the film's own camera rays (mfx_aov), averaged over global samples
     /// sampleBase .. sampleBase + spp - 1: per pixel (i, j) at (i*h + j)*8 the hit normal, hit t, albedo
     /// and hit fraction. They stay on the GPU as the feature buffers Denoise is guided by.

@@ -249,6 +249,49 @@ typedef struct mfx_adaptive {
 int mfx_sample_adaptive(mfx_ctx* ctx, const mfx_adaptive* cfg, double* frame_xmajor_rgba, int32_t* tile_spp,
                         uint8_t* rgba_ymajor);
 
+/* mfx_sample_adaptive_resume: continue the adaptive result the context holds, with this call's
+ * thresholds and budget. Additive in ABI 6. The call clears nothing: it works on the accumulator,
+ * S1 and S2, the tiles' counts n_T, B (the value next_sample had when that result's
+ * mfx_sample_adaptive began) and R (the budget reserved so far: that call's max_spp, raised by every
+ * later resume) as they are. E, M, m and the convergence test are mfx_sample_adaptive's, evaluated
+ * at a tile's own count n_T.
+ *  1. Entry check, no samples: every tile of the film is checked at its n_T under this call's
+ *     rel_error and abs_floor; a tile is active iff it fails the test and n_T < max_spp. A tighter
+ *     threshold re-activates tiles that had stopped; a looser one, or a max_spp at or below a
+ *     tile's count, leaves the tile stopped.
+ *  2. A pass: every active tile T gets cnt_T = min(step_spp, max_spp - n_T) samples, the global
+ *     samples B + n_T .. B + n_T + cnt_T - 1, summed into the pixel's accumulator, S1 and S2 in
+ *     sample order; then n_T += cnt_T and the tile is checked at its new n_T: it goes on iff it
+ *     fails and n_T < max_spp. Tiles of one pass may have different n_T and different cnt_T.
+ *  3. Passes repeat until no tile is active or max_passes passes have run (0: no limit).
+ *     *active_out (may be NULL) is the number of tiles that would go on: always 0 when max_passes is 0.
+ *  4. If max_spp > R, next_sample advances by max_spp - R and R becomes max_spp; otherwise the
+ *     counter does not move. Later calls so draw samples no pixel has used.
+ *  5. frame_xmajor_rgba, tile_spp, rgba_ymajor: as in mfx_sample_adaptive, each may be NULL; tile_spp
+ *     is every tile's current count, active ones included, and a pixel is its samples
+ *     B .. B + n_T - 1 summed in order and divided by n_T. The ray counters, mfx_stats, the trace
+ *     times and the totals are as there: the sum over this call's passes (device time: the checks,
+ *     the passes and the mean). A call that runs no pass reports 0 rays.
+ *  6. Afterwards the context holds a valid adaptive result: mfx_denoise_var filters it
+ *     (MFX_DN_SRC_ADAPTIVE) and another resume continues it.
+ * Equivalence: one mfx_sample_adaptive call with (min, max, step, rel, floor) equals the call with
+ * (min, min, step, rel, floor) followed by a resume with (max, step, max_passes 0, rel, floor): the
+ * frame, the counts, the RGBA8, the moments, next_sample and the summed ray counters agree bit for
+ * bit; so does the resume with max_passes 1 repeated until *active_out is 0 (the entry check of
+ * each call repeats the verdicts of the check that ended the call before it).
+ * Idempotence: a resume with the same thresholds and budget on a result that has none active traces
+ * nothing and returns the same outputs: the check is deterministic for given moments and n.
+ * MFX_E_INVALID: a NULL ctx or cfg, or a bad struct. MFX_E_STATE: whatever mfx_sample_adaptive
+ * refuses (device list, part_count > 1, MFX_F_ROW_PARTITION, MFX_F_MEGAKERNEL); no valid adaptive
+ * result (none yet, or a trace, mfx_accum_clear or mfx_accum_attach since); next_sample != B + R,
+ * i.e. something else drew samples in between, such as a render call served by render-ahead.      */
+typedef struct mfx_adaptive_resume {
+    int32_t max_spp, step_spp, max_passes, reserved; /* max_spp >= 2, step_spp >= 1, max_passes >= 0 (0: no limit), reserved 0 */
+    double rel_error, abs_floor;                     /* finite, >= 0 */
+} mfx_adaptive_resume; /* 32 bytes */
+int mfx_sample_adaptive_resume(mfx_ctx* ctx, const mfx_adaptive_resume* cfg, double* frame_xmajor_rgba,
+                               int32_t* tile_spp, uint8_t* rgba_ymajor, int32_t* active_out);
+
 /* ---- feature buffers and denoising (an extension: the reference shows the raw estimate) --------
  * Additive in ABI 6.
  *
@@ -325,7 +368,7 @@ int mfx_denoise(mfx_ctx* ctx, const mfx_denoise_cfg* cfg, const double* color_in
  * the colour is mfx_denoise's with sigma_color = 0 on the same frame and features, bit for bit; the
  * variance is still propagated. A pixel whose neighbourhood is noisy (large Vf) takes its
  * neighbours' luminance as it comes; one whose samples agree keeps an edge no feature marks.        */
-#define MFX_DN_SRC_ADAPTIVE 2  /* the last mfx_sample_adaptive's result, on the device */
+#define MFX_DN_SRC_ADAPTIVE 2  /* the last mfx_sample_adaptive's result, as resumed since, on the device */
 typedef struct mfx_denoise_var_cfg {
     int32_t iterations;   /* 1..8 */
     int32_t source;       /* MFX_DN_SRC_HOST or MFX_DN_SRC_ADAPTIVE */
@@ -336,7 +379,7 @@ typedef struct mfx_denoise_var_cfg {
 /* MFX_DN_SRC_HOST: color_in is a frame in mfx_sample's layout (alpha ignored), variance_in[x*h + y]
  * w*h doubles (expected >= 0, not validated); both are required. MFX_DN_SRC_ADAPTIVE: both must be
  * NULL; with n = (double)tile_spp[tile of the pixel], C = accum / n (the frame mfx_sample_adaptive
- * returned) and, from the moment planes, d = S2 - (S1*S1)/n, V = (d > 0 ? d : +0.0) / (n*(n - 1.0)):
+ * or the last resume returned) and, from the moment planes, d = S2 - (S1*S1)/n, V = (d > 0 ? d : +0.0) / (n*(n - 1.0)):
  * the tile check's v_p.
  * out_xmajor_rgba, rgba_ymajor and ms are mfx_denoise's; var_out[x*h + y] is the last iteration's V'.
  * Each output may be NULL. The call changes no context state but buffers of its own (allocated at
@@ -345,8 +388,8 @@ typedef struct mfx_denoise_var_cfg {
  * are left untouched.
  * MFX_E_INVALID: a NULL ctx or cfg, a bad struct, pointers that do not fit the source.
  * MFX_E_STATE: as mfx_aov; when mfx_aov has not run on this context; MFX_DN_SRC_ADAPTIVE when the
- * accumulator does not hold an mfx_sample_adaptive result (none yet, or a trace, mfx_accum_clear or
- * mfx_accum_attach since).                                                                        */
+ * accumulator does not hold an mfx_sample_adaptive result or its mfx_sample_adaptive_resume
+ * continuation (none yet, or a trace, mfx_accum_clear or mfx_accum_attach since).       */
 int mfx_denoise_var(mfx_ctx* ctx, const mfx_denoise_var_cfg* cfg, const double* color_in,
                     const double* variance_in, double* out_xmajor_rgba, double* var_out,
                     uint8_t* rgba_ymajor, double* ms);

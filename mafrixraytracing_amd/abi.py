@@ -81,6 +81,12 @@ class MfxAdaptive(C.Structure):
                 ("rel_error", C.c_double), ("abs_floor", C.c_double)]
 
 
+class MfxAdaptiveResume(C.Structure):
+    """mfx_adaptive_resume: the budget, pass limit and threshold of mfx_sample_adaptive_resume."""
+    _fields_ = [("max_spp", C.c_int32), ("step_spp", C.c_int32), ("max_passes", C.c_int32), ("reserved", C.c_int32),
+                ("rel_error", C.c_double), ("abs_floor", C.c_double)]
+
+
 class MfxDenoiseCfg(C.Structure):
     """mfx_denoise_cfg: iterations, source and the four sigmas of mfx_denoise."""
     _fields_ = [("iterations", C.c_int32), ("source", C.c_int32), ("reserved", C.c_int32 * 2),
@@ -98,6 +104,7 @@ class MfxDenoiseVarCfg(C.Structure):
 assert C.sizeof(MfxPrim) == 104
 assert C.sizeof(MfxInstance) == 48
 assert C.sizeof(MfxAdaptive) == 32
+assert C.sizeof(MfxAdaptiveResume) == 32
 assert C.sizeof(MfxDenoiseCfg) == 56
 assert C.sizeof(MfxDenoiseVarCfg) == 56
 
@@ -182,6 +189,7 @@ def _bind(lib, strict: bool = True):
         "mfx_destroy": (None, [C.c_void_p]),
         "mfx_sample": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
         "mfx_sample_adaptive": (C.c_int, [C.c_void_p, _P(MfxAdaptive), _dp, _ip, _P(C.c_uint8)]),
+        "mfx_sample_adaptive_resume": (C.c_int, [C.c_void_p, _P(MfxAdaptiveResume), _dp, _ip, _P(C.c_uint8), _ip]),
         "mfx_aov": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp]),
         "mfx_denoise": (C.c_int, [C.c_void_p, _P(MfxDenoiseCfg), _dp, _dp, _P(C.c_uint8), _dp]),
         "mfx_denoise_var": (C.c_int, [C.c_void_p, _P(MfxDenoiseVarCfg), _dp, _dp, _dp, _dp, _P(C.c_uint8), _dp]),
@@ -225,7 +233,7 @@ def _bind(lib, strict: bool = True):
 
 
 EXPORTED_SYMBOLS = [
-    "mfx_create", "mfx_create_instanced", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
+    "mfx_create", "mfx_create_instanced", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_sample_adaptive_resume", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
     "mfx_film_mean", "mfx_stats",
     "mfx_trace_accumulate", "mfx_accum_clear", "mfx_accum_reduce", "mfx_accum_device_ptr", "mfx_accum_attach", "mfx_accum_read_mean",
     "mfx_sync", "mfx_stream", "mfx_ray_counts", "mfx_last_trace_ms", "mfx_trace_timing", "mfx_ray_counts_total", "mfx_closest_hit", "mfx_any_hit", "mfx_ref_leaves",

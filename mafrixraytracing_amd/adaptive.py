@@ -12,6 +12,9 @@ and FP64: S1 = sum Y, S2 = sum Y*Y. After n samples of every pixel of a tile
 
 Every tile gets min_spp samples and is checked; an unconverged tile gets step_spp more, clipped at
 max_spp, and is checked again; it stops at the first check it passes, or at max_spp.
+
+mfx_sample_adaptive_resume continues such a result (reference_resume): every tile is checked at its
+own count under the call's threshold, and the tiles that fail go on from their own counts.
 """
 from __future__ import annotations
 
@@ -31,6 +34,22 @@ class AdaptiveConfig:
     def __post_init__(self):
         if not (2 <= self.min_spp <= self.max_spp and self.step_spp >= 1):
             raise ValueError("need 2 <= min_spp <= max_spp and step_spp >= 1")
+        if not (np.isfinite(self.rel_error) and self.rel_error >= 0 and np.isfinite(self.abs_floor) and self.abs_floor >= 0):
+            raise ValueError("rel_error and abs_floor must be finite and >= 0")
+
+
+@dataclass(frozen=True)
+class ResumeConfig:
+    """mfx_adaptive_resume: the budget, the pass limit (0: none) and the threshold of a resume."""
+    max_spp: int
+    step_spp: int
+    rel_error: float
+    abs_floor: float
+    max_passes: int = 0
+
+    def __post_init__(self):
+        if not (self.max_spp >= 2 and self.step_spp >= 1 and self.max_passes >= 0):
+            raise ValueError("need max_spp >= 2, step_spp >= 1 and max_passes >= 0")
         if not (np.isfinite(self.rel_error) and self.rel_error >= 0 and np.isfinite(self.abs_floor) and self.abs_floor >= 0):
             raise ValueError("rel_error and abs_floor must be finite and >= 0")
 
@@ -102,8 +121,78 @@ def reference_tile_spp(Y: np.ndarray, w: int, h: int, cfg: AdaptiveConfig) -> tu
     return spp, gap
 
 
+def reference_moments(Y: np.ndarray, w: int, h: int, tile_spp: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """(S1, S2) of every pixel after its tile's count of samples: Y[s] and Y[s]*Y[s] summed in sample
+    order from 0.0, s = 0 .. n - 1 (the moment planes a result with these counts holds)."""
+    Y = np.asarray(Y, dtype=np.float64)
+    ty_n, tx_n = tile_grid(w, h)
+    assert tile_spp.shape == (ty_n, tx_n)
+    S1 = np.zeros(w * h)
+    S2 = np.zeros(w * h)
+    for ty in range(ty_n):
+        for tx in range(tx_n):
+            p = tile_pixels(w, h, tx, ty)
+            for s in range(int(tile_spp[ty, tx])):
+                y = Y[s, p]
+                S1[p] = S1[p] + y
+                S2[p] = S2[p] + y * y
+    return S1, S2
+
+
+def reference_resume(Y: np.ndarray, w: int, h: int, spp_in: np.ndarray, S1: np.ndarray, S2: np.ndarray,
+                     cfg: ResumeConfig) -> tuple[np.ndarray, int, float, np.ndarray, np.ndarray]:
+    """mfx_sample_adaptive_resume's rule (include/mafrix_rt.h) on a result with counts spp_in
+    ((tiles_y, tiles_x)) and moment planes S1, S2 ((w*h,)); Y[s, x*h + y] is the luminance of the
+    sample at offset s from B, the result's first sample (rows up to the largest count reached).
+    Entry check: every tile at its own count n under cfg's threshold, active iff it fails and
+    n < max_spp. A pass: every active tile gets cnt = min(step_spp, max_spp - n) samples, offsets
+    n .. n + cnt - 1, added to S1 and S2 in sample order, then n += cnt and the tile is checked again.
+    Passes repeat until no tile is active or max_passes passes have run.
+    Returns (spp_out, active, gap, S1, S2): the new counts, the number of tiles that would go on
+    (0 without a pass limit), the smallest relative gap between the two sides of the test at any
+    check, the entry check included (as reference_tile_spp's), and the new moment planes (copies)."""
+    Y = np.asarray(Y, dtype=np.float64)
+    ty_n, tx_n = tile_grid(w, h)
+    assert spp_in.shape == (ty_n, tx_n) and S1.shape == (w * h,) and S2.shape == (w * h,)
+    spp = np.array(spp_in, dtype=np.int32)
+    S1 = np.array(S1, dtype=np.float64)
+    S2 = np.array(S2, dtype=np.float64)
+    tiles = [(ty, tx) for ty in range(ty_n) for tx in range(tx_n)]
+    pix = {t: tile_pixels(w, h, t[1], t[0]) for t in tiles}
+    thr = AdaptiveConfig(2, 2, 1, cfg.rel_error, cfg.abs_floor)  # check_sides reads the threshold only
+    gap = float("inf")
+
+    def check(ts):
+        nonlocal gap
+        go_on = []
+        for t in ts:
+            n = int(spp[t])
+            lhs, rhs = check_sides(S1[pix[t]], S2[pix[t]], n, thr)
+            if max(lhs, rhs) > 0.0:
+                gap = min(gap, abs(lhs - rhs) / max(lhs, rhs))
+            if not (lhs <= rhs) and n < cfg.max_spp:
+                go_on.append(t)
+        return go_on
+
+    active = check(tiles)
+    passes = 0
+    while active and (cfg.max_passes == 0 or passes < cfg.max_passes):
+        for t in active:
+            n = int(spp[t])
+            cnt = min(cfg.step_spp, cfg.max_spp - n)
+            p = pix[t]
+            for s in range(n, n + cnt):  # sample order, one rounding per operation
+                y = Y[s, p]
+                S1[p] = S1[p] + y
+                S2[p] = S2[p] + y * y
+            spp[t] = n + cnt
+        active = check(active)
+        passes += 1
+    return spp, len(active), gap, S1, S2
+
+
 def reference_mean(frames: np.ndarray, tile_spp: np.ndarray, w: int, h: int) -> np.ndarray:
-    """The image mfx_sample_adaptive must return for these counts: frames[s] is the one-sample image of
+    """The image mfx_sample_adaptive (or a resume) must return for these counts: frames[s] is the one-sample image of
     global sample s as (w*h, >=3) x-major; a pixel is the sum of its first n samples in sample order
     (from 0.0, a black sample adding nothing) divided once by n, n its tile's count; alpha 1.0."""
     frames = np.asarray(frames, dtype=np.float64)

@@ -153,6 +153,9 @@ struct TileList {
     int32_t ntiles;
     double* mom;           // device: [2][npix] the luminance moments k_resolve adds to
     int64_t gen_paths;     // paths per generation at most (a multiple of 4096)
+    // mfx_sample_adaptive_resume's passes (WfParams tile_n / list_max; null: one sample range for every tile):
+    const int32_t* tile_n = nullptr;  // device: [film tiles] the samples every tile has had, its base in this trace
+    int32_t list_max = 0;             // a tile takes min(ns, list_max - tile_n[T]) samples
 };
 
 using TraceMode = std::variant<std::monostate, FrameMode, ResolveSplit*, TileList>;
@@ -230,18 +233,23 @@ struct Ahead {
     }
 };
 
-// Adaptive sampling (mfx_sample_adaptive); allocated at its first call
+// Adaptive sampling (mfx_sample_adaptive, mfx_sample_adaptive_resume); allocated at mfx_sample_adaptive's first call
 struct Adaptive {
     DevBuf<double> mom;           // [2][npix] per-pixel luminance moments S1, S2
     DevBuf<int32_t> tiles[2];     // [tiles] the active tile list of a pass and the next one's
     DevBuf<int32_t> tile_flags;   // [tiles] the check's verdicts (1: the tile goes on)
     DevBuf<int32_t> tile_spp;     // [tiles] sample count of every tile
-    DevBuf<int32_t> tile_count;   // [1] tiles that go on
+    DevBuf<int32_t> tile_count;   // [0] tiles that go on, [1] the most samples one of them gets in the next pass (resume)
     Event ev0, ev1;               // around a pass (trace, check) and the mean
     bool check = false;           // MFX_ADAPTIVE_CHECK=1: the host validates every pass's tile list
-    bool accum_valid = false;     // the accumulator, mom and tile_spp hold the last mfx_sample_adaptive's result:
-                                  // set when it succeeds, cleared by whatever else writes or swaps the accumulator
-                                  // (a trace's parameters, mfx_accum_clear, mfx_accum_attach); mfx_denoise_var reads it
+    bool accum_valid = false;     // the accumulator, mom and tile_spp hold the last mfx_sample_adaptive's result, as
+                                  // mfx_sample_adaptive_resume continued it: set when either succeeds, cleared by
+                                  // whatever else writes or swaps the accumulator (a trace's parameters,
+                                  // mfx_accum_clear, mfx_accum_attach); mfx_denoise_var and the resume read it
+    // of that result (meaningful while accum_valid):
+    int64_t B = 0;                // next_sample when its mfx_sample_adaptive began: tile T's samples are B .. B + n_T - 1
+    int32_t R = 0;                // the budget reserved so far (that call's max_spp, raised by resumes): next_sample == B + R
+    int64_t gen_paths = 0;        // paths per generation of its passes (the first pass's: the pool is that call's)
     bool ready() const { return ev1 != nullptr; }  // the last one adaptive_alloc creates
 };
 

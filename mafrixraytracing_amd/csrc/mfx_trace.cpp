@@ -158,7 +158,8 @@ static void fill_scene_params(mfx_ctx* c, WfParams& P) {
 // every live path per iteration — then k_resolve adds its finished paths to their pixels. Every
 // launch count is known up front, so the whole call is enqueued without a host round trip.
 // mode (mfx_ctx.h): none, or render-ahead's frames (FrameMode), mfx_sample's banded last resolve
-// (ResolveSplit) or mfx_sample_adaptive's listed tiles (TileList).
+// (ResolveSplit) or the adaptive sampler's listed tiles (TileList: mfx_sample_adaptive, and with per-tile counts
+// mfx_sample_adaptive_resume).
 int mfxh::wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, TraceMode mode) {
     const FrameMode* fm = std::get_if<FrameMode>(&mode);
     ResolveSplit* split = std::holds_alternative<ResolveSplit*>(mode) ? std::get<ResolveSplit*>(mode) : nullptr;
@@ -214,7 +215,8 @@ int mfxh::wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, TraceMode mode) 
     // fetches no longer convoy, so small chunks cut the launches' tails (r04j: C2 fixed cost per
     // frame 1.67 -> 1.24 ms, 8 spp +8 %, 64 spp +1 %)
     P.chunk = c->wf_chunk;
-    P.tile_padding = (W % 8 != 0 || H % 8 != 0) ? 1 : 0;
+    // (per-tile counts: a clipped tile's windows are padding too, whatever the film's size)
+    P.tile_padding = (W % 8 != 0 || H % 8 != 0 || (list && list->tile_n)) ? 1 : 0;
     const int32_t chunk0 = P.chunk;
     P.film = fm ? fm->film : nullptr;
     P.frames = fm ? fm->frames : nullptr;
@@ -222,6 +224,8 @@ int mfxh::wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, TraceMode mode) 
     P.tiles = list ? list->tiles : nullptr;
     P.ntiles = list ? list->ntiles : 0;
     P.mom = list ? list->mom : nullptr;
+    P.tile_n = list ? list->tile_n : nullptr;
+    P.list_max = list ? list->list_max : 0;
     const bool stats = (c->flags & MFX_F_COUNT_STATS) != 0;
     P.cam_grid = c->host.inst.empty() ? c->wf_cam_grid : 0;
     if (own_events) c->cam_last = P.cam_grid > 0;

@@ -185,6 +185,13 @@ struct WfParams {
     // it adds Y = (fx + fy) + fz of every folded path to mom[pixel] and Y * Y to mom[npix + pixel], in
     // sample order (the per-pixel sums S1 and S2 of the convergence rule, include/mafrix_rt.h)
     double* mom;
+    // Per-tile counts of a listed trace (mfx_sample_adaptive_resume's passes; null: every listed tile
+    // takes the trace's sample range as it is). tile_n[T], indexed by film tile, is the number of samples
+    // tile T has had: its sample d of this trace is global sample sample_base + tile_n[T] + d, and the
+    // tile takes only the d < list_max - tile_n[T] (the rest of its windows are padding: no path). The
+    // counts are constant through a trace. Such a trace sets tile_padding whatever the film's size.
+    const int32_t* tile_n;
+    int32_t list_max;
 };
 
 // The adaptive sampler's tile check (k_tile_check: one wave per active tile) and the compaction of the
@@ -201,7 +208,12 @@ struct TileCheckParams {
     int32_t* tile_spp;      // [tiles_y * tiles_x] a stopped tile's sample count
     int32_t* flags;         // [ntiles] 1: the tile goes on
     int32_t* next;          // [ntiles] the tiles that go on, ascending (k_tile_compact)
-    int32_t* next_count;    // [1]
+    int32_t* next_count;    // [1]; per_tile: [2], [1] the largest sample count of a tile that goes on in the next pass
+    // per_tile != 0 (mfx_sample_adaptive_resume): `n` is unused, every tile is checked at its own count,
+    // tile_spp[T] + min(pass_spp, max_spp - tile_spp[T]), and gets that count written, stopping or not
+    int32_t per_tile;
+    int32_t pass_spp;       // samples per tile of the pass before the check, at most (0: none, the entry check)
+    int32_t step_spp;       // and of the next pass
 };
 hipError_t mfx_wf_tile_check(const TileCheckParams& C, hipStream_t st);
 

@@ -294,13 +294,21 @@ __device__ __forceinline__ bool trav_step(Trav& T, const SceneView& S, const ST&
 // list's tiles: per_sample = ntiles * 64 and tile k is film tile P.tiles[k] (list_tile_xy,
 // mfx_device.h). LIST is a template parameter of the kernels, so the band instances carry none of
 // it (as a run-time branch it moved the scratch size of five k_extend / k_shadow instances).
+// WF_LIST_TILE_N (mfx_sample_adaptive_resume's passes): every listed tile continues from its own
+// count. The trace's sample d of tile T = P.tiles[k] is the tile's sample P.tile_n[T] + d, which is
+// what `smp` returns, and the window is padding (no path, like an edge tile's padding pixels: x =
+// P.width) when d >= P.list_max - P.tile_n[T], the tile's clipped share of the pass. It has a
+// template value of its own for the reason above: mfx_sample_adaptive's instances are the ones they were.
 // PP: WfParams, or k_shadow's LDS copy of the fields it needs (PixParams)
-template <bool LIST, typename PP>
+#define WF_LIST_NONE 0
+#define WF_LIST_TILES 1
+#define WF_LIST_TILE_N 2
+template <int LIST, typename PP>
 __device__ __forceinline__ bool path_pixel(const PP& P, int64_t p, int& x, int& y, int64_t& smp) {
     // p = path_base + s: the 64-bit split of path_base is done once per generation on the host
     // (base_smp, base_q), so only 32-bit divisions remain here (base_q + s < 2^32)
     const unsigned tiles_x = (unsigned)(P.width + 7) >> 3;
-    constexpr bool list = LIST;
+    constexpr bool list = LIST != WF_LIST_NONE;
     const unsigned per_sample = (list ? (unsigned)P.ntiles : tiles_x * (unsigned)P.band_rows) * 64;  // < 2^31 (film limit)
     const unsigned qs = (unsigned)P.base_q + (unsigned)(p - P.path_base);
     const unsigned ds = qs / per_sample;
@@ -309,10 +317,20 @@ __device__ __forceinline__ bool path_pixel(const PP& P, int64_t p, int& x, int& 
     const unsigned tile = q >> 6, within = q & 63;
     unsigned tx, ty;
     if (list) {
-        if (!list_tile_xy((unsigned)P.tiles[tile], tiles_x, (unsigned)(P.height + 7) >> 3, tx, ty)) {
+        const unsigned T = (unsigned)P.tiles[tile];
+        if (!list_tile_xy(T, tiles_x, (unsigned)(P.height + 7) >> 3, tx, ty)) {
             x = P.width;  // outside the film: no path
             y = 0;
             return false;
+        }
+        if (LIST == WF_LIST_TILE_N) {  // (T is a tile of the film, so tile_n[T] exists)
+            const int tn = P.tile_n[T];
+            if (smp >= (int64_t)P.list_max - tn) {
+                x = P.width;  // past the tile's share of the pass: no path
+                y = 0;
+                return false;
+            }
+            smp += tn;
         }
     } else {
         const unsigned tyl = tile / tiles_x;
@@ -322,6 +340,13 @@ __device__ __forceinline__ bool path_pixel(const PP& P, int64_t p, int& x, int& 
     x = (int)(tx * 8 + (within & 7));
     y = (int)(ty * 8 + (within >> 3));
     return x < P.width && y < P.height;
+}
+// the global sample index of path_pixel's `smp` (a listed trace is whole-film and unpartitioned:
+// whole_film_single_device; k_shadow's PixParams keeps a per-tile trace's fields in the partition's words)
+template <int LIST, typename PP>
+__device__ __forceinline__ int64_t path_gsample(const PP& P, int64_t smp) {
+    if (LIST == WF_LIST_TILE_N) return P.sample_base + smp;
+    return P.sample_base + P.part_index + smp * P.part_count;
 }
 
 #define WF_EXT_PEND 128  // k_extend per-wave pending list: slot indices (sign bit: camera ray)
@@ -510,11 +535,12 @@ __device__ __forceinline__ VertexSample sample_vertex(const MfxLight& LT, bool o
 // START: the instance for a generation's first iteration when k_camera does not take its camera
 // rays (two-level scenes, MFX_CAMERA_PACKETS=0); only it carries the camera-ray code (GetRay, the
 // path key, the camera's fields), so the bounce instances hold fewer live scalar registers
-// LIST: a START instance for a listed trace (adaptive sampling: path_pixel's tile list)
+// LIST: a START instance for a listed trace (adaptive sampling: path_pixel's tile list, WF_LIST_TILES; with
+// per-tile counts WF_LIST_TILE_N, whose clipped windows the scan takes as padding: P.tile_padding is set)
 // NF: the node format (node_step): the instances a flat scene's default path launches (the bounce and
 // queue ones, wf_nf) are built for one format each, so their node loop holds one step and none of the
 // other's registers; the rest (STATS, START, LIST, the other scene kinds) take either (MFX_NF_ANY)
-template <bool STATS, bool SPILL, int SK, bool Q, bool START = false, bool LIST = false, int NF = MFX_NF_ANY>
+template <bool STATS, bool SPILL, int SK, bool Q, bool START = false, int LIST = WF_LIST_NONE, int NF = MFX_NF_ANY>
 __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
     constexpr bool INST = SK == WF_SK_INST, SLDS = SK == WF_SK_SLDS;
     extern __shared__ int lds_all[];
@@ -575,7 +601,7 @@ __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
             int64_t smp;
             path_pixel<LIST>(P, P.path_base + s, x, y, smp);
             const int64_t pixel = (int64_t)x * P.height + y;  // Color[w,h] x-major
-            const int64_t gsample = P.sample_base + P.part_index + smp * P.part_count;
+            const int64_t gsample = path_gsample<LIST>(P, smp);
             const uint64_t key = path_key(P.seed, (uint64_t)pixel, (uint64_t)gsample);
             uint32_t rn = 0;
             const double u = ((double)x + rng_next(key, rn)) / (double)P.width;
@@ -707,8 +733,9 @@ __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
 // loads more than it issues, and the fifth wave fills those waits
 #define MFX_CAM_WAVES 5
 #endif
-// LIST: the instance for a listed trace (adaptive sampling): a window's tile is one scalar load
-template <bool STATS, bool LIST = false>
+// LIST: the instance for a listed trace (adaptive sampling): a window's tile is one scalar load, and with
+// per-tile counts (WF_LIST_TILE_N) so is its count; a window past the tile's share has no active lane
+template <bool STATS, int LIST = WF_LIST_NONE>
 __global__ void __launch_bounds__(256, MFX_CAM_WAVES) k_camera(WfParams P) {
     extern __shared__ int lds_all[];
     const int lane = lane_id();
@@ -766,7 +793,7 @@ __global__ void __launch_bounds__(256, MFX_CAM_WAVES) k_camera(WfParams P) {
         DV o = dv(0, 0, 0), d = dv(0, 0, 1);
         if (act) {  // PixelIntegrator.Sample (Integrators.fs:167-169) + GetRay (Camera.fs:134-139)
             const int64_t pixel = (int64_t)x * P.height + y;  // Color[w,h] x-major
-            const int64_t gsample = P.sample_base + P.part_index + smp * P.part_count;
+            const int64_t gsample = path_gsample<LIST>(P, smp);
             const uint64_t key = path_key(P.seed, (uint64_t)pixel, (uint64_t)gsample);
             uint32_t rn = 0;
             const double u = ((double)x + rng_next(key, rn)) / (double)P.width;
@@ -833,7 +860,17 @@ struct PixParams {
         struct { int32_t band_index, band_count; };
         const int32_t* tiles;  // ntiles > 0
     };
-    int32_t band_rows, part_index, part_count, ntiles;
+    // (a per-tile listed trace, WF_LIST_TILE_N, is unpartitioned: its counts and their bound take the
+    // partition's words, path_gsample reads neither)
+    union {
+        struct { int32_t band_rows, part_index; };
+        const int32_t* tile_n;
+    };
+    union {
+        int32_t part_count;
+        int32_t list_max;
+    };
+    int32_t ntiles;
 };
 static_assert(sizeof(PixParams) == 72, "PixParams: k_shadow's LDS layout");
 // k_shadow's array pointers in its LDS (after the light)
@@ -858,9 +895,9 @@ struct ShdPtrs {
 // k_shadow: shade HIT slots (listed at scan time), trace the vertex's shadow ray, continue or finish
 // ------------------------------------------------------------------------------------------------
 // Q: the instance that reads a ray queue (P.qslot) or writes the next one (P.ncount), MFX_RAY_QUEUE
-// LIST: the instances for a listed trace (adaptive sampling: path_pixel's tile list)
+// LIST: the instances for a listed trace (adaptive sampling: path_pixel's tile list, and WF_LIST_TILE_N's counts)
 // NF: the node format, as k_extend's
-template <bool STATS, bool SPILL, int WAVES, int SK, bool Q, bool LIST = false, int NF = MFX_NF_ANY>
+template <bool STATS, bool SPILL, int WAVES, int SK, bool Q, int LIST = WF_LIST_NONE, int NF = MFX_NF_ANY>
 __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
     constexpr bool INST = SK == WF_SK_INST, SLDS = SK == WF_SK_SLDS;
     extern __shared__ int lds_all[];
@@ -896,7 +933,11 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
         } else {
             px.band_index = P.band_index; px.band_count = P.band_count;
         }
-        px.band_rows = P.band_rows; px.part_index = P.part_index; px.part_count = P.part_count;
+        if (LIST == WF_LIST_TILE_N) {
+            px.tile_n = P.tile_n; px.list_max = P.list_max;
+        } else {
+            px.band_rows = P.band_rows; px.part_index = P.part_index; px.part_count = P.part_count;
+        }
         px.ntiles = LIST ? P.ntiles : 0;
         *(PixParams*)((ShdPtrs*)(light_lds + 1) + 1) = px;
     }
@@ -1007,7 +1048,7 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
                         int64_t smp;
                         path_pixel<LIST>(PX, PX.path_base + jr, x, y, smp);
                         const int64_t pixel = (int64_t)x * PX.height + y;
-                        key = path_key(PX.seed, (uint64_t)pixel, (uint64_t)(PX.sample_base + PX.part_index + smp * PX.part_count));
+                        key = path_key(PX.seed, (uint64_t)pixel, (uint64_t)path_gsample<LIST>(PX, smp));
                     }
                     rn = first ? 2u : C.rn[j];  // the camera ray drew u, v
                 }
@@ -1413,7 +1454,7 @@ static int scene_kind(bool inst, int nslot) { return inst ? WF_SK_INST : (nslot 
 // The node format of the instance launched for scene kind SK (k_extend / k_shadow NF): a flat scene's
 // in-place and queue instances without STATS, START or LIST are built per format, FP16 nodes when the
 // context has them (fp16: WfParams::nodes_h), FP32 under MFX_NODE_F32; every other instance takes either
-template <int SK, bool STATS, bool START, bool LIST>
+template <int SK, bool STATS, bool START, int LIST>
 static constexpr bool wf_nf_fixed() { return SK == WF_SK_FLAT && !STATS && !START && !LIST; }
 static bool wf_fp16(const WfParams& P) {
 #if MFX_NODE_F16
@@ -1429,11 +1470,11 @@ static bool wf_fp16(const WfParams& P) {
 template <int SK, int NF>
 static const void* occ_kernel(bool shadow, bool spill) {
     if (shadow)
-        return spill ? (const void*)k_shadow<false, true, 4, SK, false, false, NF>
-                     : (const void*)k_shadow<false, false, 4, SK, false, false, NF>;
+        return spill ? (const void*)k_shadow<false, true, 4, SK, false, WF_LIST_NONE, NF>
+                     : (const void*)k_shadow<false, false, 4, SK, false, WF_LIST_NONE, NF>;
     constexpr bool START = NF == MFX_NF_ANY;
-    return spill ? (const void*)k_extend<false, true, SK, false, START, false, NF>
-                 : (const void*)k_extend<false, false, SK, false, START, false, NF>;
+    return spill ? (const void*)k_extend<false, true, SK, false, START, WF_LIST_NONE, NF>
+                 : (const void*)k_extend<false, false, SK, false, START, WF_LIST_NONE, NF>;
 }
 
 hipError_t mfx_wf_kernel_occupancy(bool shadow, int stack_lds, bool spill, int ntop, int ninst, int* blocks_per_cu,
@@ -1451,7 +1492,7 @@ hipError_t mfx_wf_kernel_occupancy(bool shadow, int stack_lds, bool spill, int n
     return e;
 }
 
-template <bool SPILL, int SK, bool Q, bool START = false, bool LIST = false>
+template <bool SPILL, int SK, bool Q, bool START = false, int LIST = WF_LIST_NONE>
 static void launch_extend_q(const WfParams& P, int grid, bool stats, hipStream_t st, size_t lds) {
     if (stats) {
         hipLaunchKernelGGL((k_extend<true, SPILL, SK, Q, START, LIST>), dim3(grid), dim3(256), lds, st, P);
@@ -1469,28 +1510,36 @@ static void launch_extend_q(const WfParams& P, int grid, bool stats, hipStream_t
 template <bool SPILL, int SK>
 static void launch_extend(const WfParams& P, int grid, bool stats, hipStream_t st, size_t lds) {
     if (P.qcount) launch_extend_q<SPILL, SK, true>(P, grid, stats, st, lds);
-    else if (P.start && P.ntiles > 0) launch_extend_q<SPILL, SK, false, true, true>(P, grid, stats, st, lds);
+    else if (P.start && P.ntiles > 0 && P.tile_n) launch_extend_q<SPILL, SK, false, true, WF_LIST_TILE_N>(P, grid, stats, st, lds);
+    else if (P.start && P.ntiles > 0) launch_extend_q<SPILL, SK, false, true, WF_LIST_TILES>(P, grid, stats, st, lds);
     else if (P.start) launch_extend_q<SPILL, SK, false, true>(P, grid, stats, st, lds);
     else launch_extend_q<SPILL, SK, false>(P, grid, stats, st, lds);
 }
 template <bool SPILL, int WAVES, int SK, bool Q>
 static void launch_shadow_q(const WfParams& P, int grid, bool stats, hipStream_t st, size_t lds) {
+    if (P.ntiles > 0 && P.tile_n) {  // a listed trace with per-tile counts (mfx_sample_adaptive_resume)
+        if (stats)
+            hipLaunchKernelGGL((k_shadow<true, SPILL, WAVES, SK, Q, WF_LIST_TILE_N>), dim3(grid), dim3(256), lds, st, P);
+        else
+            hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q, WF_LIST_TILE_N>), dim3(grid), dim3(256), lds, st, P);
+        return;
+    }
     if (P.ntiles > 0) {  // a listed trace (adaptive sampling)
         if (stats)
-            hipLaunchKernelGGL((k_shadow<true, SPILL, WAVES, SK, Q, true>), dim3(grid), dim3(256), lds, st, P);
+            hipLaunchKernelGGL((k_shadow<true, SPILL, WAVES, SK, Q, WF_LIST_TILES>), dim3(grid), dim3(256), lds, st, P);
         else
-            hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q, true>), dim3(grid), dim3(256), lds, st, P);
+            hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q, WF_LIST_TILES>), dim3(grid), dim3(256), lds, st, P);
         return;
     }
     if (stats) {
         hipLaunchKernelGGL((k_shadow<true, SPILL, WAVES, SK, Q>), dim3(grid), dim3(256), lds, st, P);
-    } else if constexpr (wf_nf_fixed<SK, false, false, false>()) {
+    } else if constexpr (wf_nf_fixed<SK, false, false, WF_LIST_NONE>()) {
 #if MFX_NODE_F16
         if (wf_fp16(P))
-            hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q, false, MFX_NF_H>), dim3(grid), dim3(256), lds, st, P);
+            hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q, WF_LIST_NONE, MFX_NF_H>), dim3(grid), dim3(256), lds, st, P);
         else
 #endif
-            hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q, false, MFX_NF_F32>), dim3(grid), dim3(256), lds, st, P);
+            hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q, WF_LIST_NONE, MFX_NF_F32>), dim3(grid), dim3(256), lds, st, P);
     } else {
         hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q>), dim3(grid), dim3(256), lds, st, P);
     }
@@ -1541,9 +1590,12 @@ static hipError_t launch_iteration(const WfParams& P, int ext_grid, int shd_grid
     const bool inst = P.inst != nullptr;
     if (!inst && P.start && P.cam_grid > 0) {  // camera rays as packets
         const size_t lds_c = cam_lds_bytes(P.stack_size);
-        if (P.ntiles > 0) {  // a listed trace (adaptive sampling)
-            if (stats) hipLaunchKernelGGL((k_camera<true, true>), dim3(P.cam_grid), dim3(256), lds_c, st, P);
-            else hipLaunchKernelGGL((k_camera<false, true>), dim3(P.cam_grid), dim3(256), lds_c, st, P);
+        if (P.ntiles > 0 && P.tile_n) {  // a listed trace with per-tile counts (mfx_sample_adaptive_resume)
+            if (stats) hipLaunchKernelGGL((k_camera<true, WF_LIST_TILE_N>), dim3(P.cam_grid), dim3(256), lds_c, st, P);
+            else hipLaunchKernelGGL((k_camera<false, WF_LIST_TILE_N>), dim3(P.cam_grid), dim3(256), lds_c, st, P);
+        } else if (P.ntiles > 0) {  // a listed trace (adaptive sampling)
+            if (stats) hipLaunchKernelGGL((k_camera<true, WF_LIST_TILES>), dim3(P.cam_grid), dim3(256), lds_c, st, P);
+            else hipLaunchKernelGGL((k_camera<false, WF_LIST_TILES>), dim3(P.cam_grid), dim3(256), lds_c, st, P);
         } else if (stats) hipLaunchKernelGGL(k_camera<true>, dim3(P.cam_grid), dim3(256), lds_c, st, P);
         else hipLaunchKernelGGL(k_camera<false>, dim3(P.cam_grid), dim3(256), lds_c, st, P);
     } else {
@@ -1607,19 +1659,16 @@ __device__ __forceinline__ double wave_sum(double v) {
 
 // One wave per active tile, a lane per pixel of the tile: v_p = max(0, S2 - S1 * S1 / n) / (n (n - 1))
 // and S1 / n from the lane's moments, E and M summed over the wave, m counted from the valid lanes'
-// ballot; lane 0 decides E m <= rel^2 (|M| + abs_floor m)^2. A tile that stops (converged, or at
-// max_spp) gets its count; flags[k] tells k_tile_compact which entries go on.
-__global__ void __launch_bounds__(256) k_tile_check(TileCheckParams C) {
-    const int k = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    if (k >= C.ntiles) return;
+// ballot; E m <= rel^2 (|M| + abs_floor m)^2 is the test. True: the tile has converged after ni
+// samples (wave-uniform; m: its valid pixels, 0 for an index outside the film).
+__device__ __forceinline__ bool tile_converged(const TileCheckParams& C, int T, int ni, int& m) {
     const int lane = lane_id();
     const unsigned tiles_x = (unsigned)(C.width + 7) >> 3, tiles_y = (unsigned)(C.height + 7) >> 3;
-    const int T = C.tiles[k];  // wave-uniform: one scalar load
     unsigned tx, ty;
     const bool in_film = list_tile_xy((unsigned)T, tiles_x, tiles_y, tx, ty);
     const int x = (int)tx * 8 + (lane & 7), y = (int)ty * 8 + (lane >> 3);
     const bool valid = in_film && x < C.width && y < C.height;
-    const double n = (double)C.n;
+    const double n = (double)ni;
     double v = 0.0, mean = 0.0;
     if (valid) {
         const int64_t npix = (int64_t)C.width * C.height;
@@ -1630,12 +1679,49 @@ __global__ void __launch_bounds__(256) k_tile_check(TileCheckParams C) {
         mean = s1 / n;
     }
     const double E = wave_sum(v), M = wave_sum(mean);
-    const int m = __popcll(__ballot(valid));
-    if (lane == 0) {
-        const double md = (double)m;
-        const double t = fabs(M) + C.abs_floor * md;
-        const bool stop = m == 0 || C.n >= C.max_spp || E * md <= C.rel2 * (t * t);
+    m = __popcll(__ballot(valid));
+    const double md = (double)m;
+    const double t = fabs(M) + C.abs_floor * md;
+    return E * md <= C.rel2 * (t * t);
+}
+
+// mfx_sample_adaptive's check: every listed tile has had C.n samples. A tile that stops (converged, or
+// at max_spp) gets its count; flags[k] tells k_tile_compact which entries go on.
+__global__ void __launch_bounds__(256) k_tile_check(TileCheckParams C) {
+    const int k = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    if (k >= C.ntiles) return;
+    const int T = C.tiles[k];  // wave-uniform: one scalar load
+    int m;
+    const bool conv = tile_converged(C, T, C.n, m);
+    if (lane_id() == 0) {
+        const bool stop = m == 0 || C.n >= C.max_spp || conv;
         if (stop && m > 0) C.tile_spp[T] = C.n;  // (m > 0: T is a tile of the film)
+        C.flags[k] = stop ? 0 : 1;
+    }
+}
+
+// mfx_sample_adaptive_resume's check: every listed tile T has its own count. The pass before it gave
+// the tile min(C.pass_spp, max_spp - tile_spp[T]) samples (pass_spp 0: the entry check, no pass), so
+// n is tile_spp[T] plus that. Every checked tile gets its new count, stopping or not: the next pass
+// reads it as the tile's base (WfParams::tile_n), and k_tile_compact takes from it the largest share of
+// that pass.
+__global__ void __launch_bounds__(256) k_tile_check_n(TileCheckParams C) {
+    const int k = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    if (k >= C.ntiles) return;
+    const int T = C.tiles[k];
+    const unsigned nt = (((unsigned)C.width + 7) >> 3) * (((unsigned)C.height + 7) >> 3);
+    if ((unsigned)T >= nt) {  // not a tile of the film: no count to read
+        if (lane_id() == 0) C.flags[k] = 0;
+        return;
+    }
+    const int n0 = C.tile_spp[T];
+    const int left = C.max_spp - n0;
+    const int n = n0 + (left < C.pass_spp ? (left > 0 ? left : 0) : C.pass_spp);
+    int m;
+    const bool conv = tile_converged(C, T, n, m);
+    if (lane_id() == 0) {
+        const bool stop = n >= C.max_spp || conv;
+        C.tile_spp[T] = n;
         C.flags[k] = stop ? 0 : 1;
     }
 }
@@ -1643,9 +1729,14 @@ __global__ void __launch_bounds__(256) k_tile_check(TileCheckParams C) {
 // The tiles that go on, in list order (ascending: the camera packets and the resolve's coalescing rely
 // on tile-row coherence). One block; each wave owns a contiguous run of whole 64-entry rounds, counts
 // its flags by ballot, and after the waves' counts are known writes its survivors at their ranks.
+// per_tile (mfx_sample_adaptive_resume): next_count[1] gets the largest number of samples a survivor
+// takes in the next pass, min(step_spp, max_spp - tile_spp[T]), by which the host sizes that pass (here,
+// over the list it walks anyway: one atomic per tile on that word cost 0.23 ms per C2 pass, 88 per us).
 #define WF_COMPACT_WAVES 16
 __global__ void __launch_bounds__(64 * WF_COMPACT_WAVES) k_tile_compact(TileCheckParams C) {
     __shared__ int wcount[WF_COMPACT_WAVES];
+    __shared__ int wshare[WF_COMPACT_WAVES];
+    int share = 0;
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     const int per = ((C.ntiles + WF_COMPACT_WAVES - 1) / WF_COMPACT_WAVES + 63) / 64 * 64;
     const int lo = min(wave * per, C.ntiles), hi = min(lo + per, C.ntiles);
@@ -1658,13 +1749,32 @@ __global__ void __launch_bounds__(64 * WF_COMPACT_WAVES) k_tile_compact(TileChec
     for (int i = lo; i < hi; i += 64) {
         const bool f = i + lane < hi && C.flags[i + lane] != 0;
         const uint64_t b = __ballot(f);
-        if (f) C.next[base + __popcll(b & lanes_below())] = C.tiles[i + lane];
+        if (f) {
+            const int T = C.tiles[i + lane];
+            C.next[base + __popcll(b & lanes_below())] = T;
+            if (C.per_tile) share = max(share, min(C.step_spp, C.max_spp - C.tile_spp[T]));
+        }
         base += __popcll(b);
+    }
+    if (C.per_tile) {
+        for (int off = 32; off > 0; off >>= 1) share = max(share, __shfl_xor(share, off));
+        if (lane == 0) wshare[wave] = share;
+        __syncthreads();
+        if (threadIdx.x == 64 * WF_COMPACT_WAVES - 1) {
+            for (int w = 0; w < WF_COMPACT_WAVES; ++w) share = max(share, wshare[w]);
+            C.next_count[1] = share;
+        }
     }
     if (threadIdx.x == 64 * WF_COMPACT_WAVES - 1) *C.next_count = base;  // the last wave ends at the total
 }
 
 hipError_t mfx_wf_tile_check(const TileCheckParams& C, hipStream_t st) {
+    if (C.per_tile) {
+        if (C.ntiles <= 0 || C.pass_spp < 0 || C.step_spp < 1 || C.max_spp < 2) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_tile_check_n, dim3((unsigned)((C.ntiles + 3) / 4)), dim3(256), 0, st, C);
+        hipLaunchKernelGGL(k_tile_compact, dim3(1), dim3(64 * WF_COMPACT_WAVES), 0, st, C);
+        return hipGetLastError();
+    }
     if (C.ntiles <= 0 || C.n < 2) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_tile_check, dim3((unsigned)((C.ntiles + 3) / 4)), dim3(256), 0, st, C);
     hipLaunchKernelGGL(k_tile_compact, dim3(1), dim3(64 * WF_COMPACT_WAVES), 0, st, C);

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from .abi import (INSTANCING_KEYS, LAUNCH_INFO_KEYS, MFX_DN_SRC_ACCUM, MFX_DN_SRC_ADAPTIVE, MFX_DN_SRC_HOST, MFX_F_NONE,
-                  MFX_F_TWO_LEVEL, MfxAdaptive, MfxDenoiseCfg, MfxDenoiseVarCfg, MfxInstance, MfxOptions, SceneArrays, check,
+                  MFX_F_TWO_LEVEL, MfxAdaptive, MfxAdaptiveResume, MfxDenoiseCfg, MfxDenoiseVarCfg, MfxInstance, MfxOptions, SceneArrays, check,
                   dptr, iptr, load_library)
 from .denoise import DenoiseConfig, DenoiseVarConfig
 
@@ -95,6 +95,25 @@ class NativeContext:
               "mfx_sample_adaptive")
         return (frame, tiles, rgba) if want_rgba else (frame, tiles)
 
+    def sample_adaptive_resume(self, max_spp: int, step_spp: int, rel_error: float, abs_floor: float,
+                               max_passes: int = 0, want_rgba: bool = False):
+        """mfx_sample_adaptive_resume: continue the adaptive result the context holds under this call's
+        threshold and budget, every tile from its own count, for at most max_passes passes (0: until no
+        tile is active; the rule: include/mafrix_rt.h, adaptive.py reference_resume). Returns
+        (frame, tile_spp, active) or (frame, tile_spp, rgba, active): sample_adaptive's outputs for the
+        tiles' current counts, and the number of tiles that would go on."""
+        cfg = MfxAdaptiveResume(max_spp=max_spp, step_spp=step_spp, max_passes=max_passes, reserved=0,
+                                rel_error=rel_error, abs_floor=abs_floor)
+        frame = np.empty((self.w * self.h, 4), dtype=np.float64)
+        tiles = np.zeros(((self.h + 7) // 8, (self.w + 7) // 8), dtype=np.int32)
+        rgba = np.empty(self.w * self.h * 4, dtype=np.uint8) if want_rgba else None
+        active = C.c_int32(-1)
+        check(self.lib.mfx_sample_adaptive_resume(self._h, C.byref(cfg), dptr(frame), iptr(tiles),
+                                                  rgba.ctypes.data_as(C.POINTER(C.c_uint8)) if want_rgba else None,
+                                                  C.byref(active)),
+              "mfx_sample_adaptive_resume")
+        return (frame, tiles, rgba, active.value) if want_rgba else (frame, tiles, active.value)
+
     def aov(self, spp: int, sample_base: int = 0) -> np.ndarray:
         """mfx_aov: the (w*h, 8) x-major first-hit features of the film's own camera rays, averaged over
         global samples sample_base .. sample_base + spp - 1: normal xyz, hit t, albedo rgb, hit fraction.
@@ -132,7 +151,7 @@ class NativeContext:
         """mfx_denoise_var: the variance-guided a-trous filter (the rule: include/mafrix_rt.h,
         mafrixraytracing_amd/denoise.py) of `frame` ((w*h, 4) x-major, alpha ignored) with `variance`
         ((w*h,) x-major, the variance of each pixel's mean luminance), or with frame=None of the last
-        sample_adaptive's result as it lies on the device (its accumulator, moments and tile counts);
+        sample_adaptive's result (as resumed since) as it lies on the device (its accumulator, moments and tile counts);
         guided by the feature buffers of the last aov call. Returns the (w*h, 4) filtered frame, or a
         tuple of it, the y-major RGBA8 post (want_rgba) and the (w*h,) filtered variance (want_variance)."""
         c = MfxDenoiseVarCfg(iterations=cfg.iterations, source=MFX_DN_SRC_ADAPTIVE if frame is None else MFX_DN_SRC_HOST,
@@ -351,6 +370,10 @@ class NativePixelIntegrator:
     def SampleAdaptive(self, minSpp: int, maxSpp: int, stepSpp: int, relError: float, absFloor: float):
         """fsharp/Native.fs SampleAdaptive: (Color[w,h] x-major, the tiles' sample counts)."""
         return self._ctx.sample_adaptive(minSpp, maxSpp, stepSpp, relError, absFloor)
+
+    def SampleAdaptiveResume(self, maxSpp: int, stepSpp: int, maxPasses: int, relError: float, absFloor: float):
+        """fsharp/Native.fs SampleAdaptiveResume: (Color[w,h] x-major, the tiles' sample counts, tiles still active)."""
+        return self._ctx.sample_adaptive_resume(maxSpp, stepSpp, relError, absFloor, max_passes=maxPasses)
 
 
 class Scene:
