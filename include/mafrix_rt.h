@@ -339,6 +339,9 @@ typedef struct mfx_denoise_cfg {
     int32_t reserved[2];       /* 0 */
     double count;              /* SRC_ACCUM: > 0; SRC_HOST: ignored */
     double sigma_normal, sigma_depth, sigma_albedo, sigma_color; /* finite, >= 0; 0 switches the term off */
+    /* A sigma > 0 must leave its term's divisor non-zero in FP64: sn*sn, sz*sz and sa*sa != 0 (a sigma
+     * below about 1.5e-162 squares to 0), and (sc*sc) * 0.25^i != 0 for every i < iterations, 0.25^i by
+     * repeated multiplication from 1.0. Otherwise the centre tap's term is 0/0: MFX_E_INVALID. */
 } mfx_denoise_cfg; /* 56 bytes */
 /* out_xmajor_rgba (mfx_sample's layout, alpha 1.0), rgba_ymajor (ACES -> sqrt -> RGBA8 of it,
  * mfx_render_rgba8's layout), ms (device time from HIP events): each may be NULL. Changes no context
@@ -374,6 +377,8 @@ typedef struct mfx_denoise_var_cfg {
     int32_t source;       /* MFX_DN_SRC_HOST or MFX_DN_SRC_ADAPTIVE */
     int32_t reserved[2];  /* 0 */
     double sigma_normal, sigma_depth, sigma_albedo, sigma_luma; /* finite, >= 0; 0 switches the term off */
+    /* sigma_normal, sigma_depth, sigma_albedo > 0 must have a non-zero square in FP64, as for
+     * mfx_denoise: MFX_E_INVALID otherwise. sigma_luma needs no such rule: lden >= luma_floor. */
     double luma_floor;    /* finite, > 0 */
 } mfx_denoise_var_cfg;    /* 56 bytes */
 /* MFX_DN_SRC_HOST: color_in is a frame in mfx_sample's layout (alpha ignored), variance_in[x*h + y]

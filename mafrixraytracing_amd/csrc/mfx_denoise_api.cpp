@@ -34,6 +34,10 @@ static int dn_alloc(DevBuf<double>& p, size_t doubles, const char* who) {
     return MFX_OK;
 }
 
+// a sigma > 0 whose square, the divisor the kernels use, has underflowed to 0: the centre tap's term
+// would be 0/0 and every pixel NaN
+static bool zero_square(double s) { return s > 0.0 && s * s == 0.0; }
+
 extern "C" int mfx_aov(mfx_ctx* c, int32_t spp, int64_t sample_base, double* out, double* ms) {
     if (!c) return fail(MFX_E_INVALID, "mfx_aov: null context");
     if (spp < 1) return fail(MFX_E_INVALID, "mfx_aov: spp must be >= 1");
@@ -71,6 +75,17 @@ extern "C" int mfx_denoise(mfx_ctx* c, const mfx_denoise_cfg* a, const double* c
         return fail(MFX_E_INVALID, "mfx_denoise: unknown source");
     for (double s : {a->sigma_normal, a->sigma_depth, a->sigma_albedo, a->sigma_color})
         if (!(s >= 0.0) || !std::isfinite(s)) return fail(MFX_E_INVALID, "mfx_denoise: every sigma must be finite and >= 0");
+    for (double s : {a->sigma_normal, a->sigma_depth, a->sigma_albedo})
+        if (zero_square(s)) return fail(MFX_E_INVALID, "mfx_denoise: a sigma > 0 must have a non-zero square");
+    if (a->sigma_color > 0.0) {  // the colour term divides by sc2 * 0.25^i: the loop's own products, below
+        const double sc2 = a->sigma_color * a->sigma_color;
+        double quarter = 1.0;
+        for (int i = 0; i < a->iterations; ++i) {
+            if (sc2 * quarter == 0.0)
+                return fail(MFX_E_INVALID, "mfx_denoise: sigma_color > 0 must keep (sigma_color^2) * 0.25^i non-zero at every iteration");
+            quarter = quarter * 0.25;
+        }
+    }
     if (a->source == MFX_DN_SRC_HOST && !color_in)
         return fail(MFX_E_INVALID, "mfx_denoise: MFX_DN_SRC_HOST needs color_in");
     if (a->source == MFX_DN_SRC_ACCUM && !(a->count > 0.0))
@@ -127,6 +142,8 @@ extern "C" int mfx_denoise_var(mfx_ctx* c, const mfx_denoise_var_cfg* a, const d
         return fail(MFX_E_INVALID, "mfx_denoise_var: unknown source");
     for (double s : {a->sigma_normal, a->sigma_depth, a->sigma_albedo, a->sigma_luma})
         if (!(s >= 0.0) || !std::isfinite(s)) return fail(MFX_E_INVALID, "mfx_denoise_var: every sigma must be finite and >= 0");
+    for (double s : {a->sigma_normal, a->sigma_depth, a->sigma_albedo})  // (sigma_luma's square is added to luma_floor > 0)
+        if (zero_square(s)) return fail(MFX_E_INVALID, "mfx_denoise_var: a sigma > 0 must have a non-zero square");
     if (!(a->luma_floor > 0.0) || !std::isfinite(a->luma_floor))
         return fail(MFX_E_INVALID, "mfx_denoise_var: luma_floor must be finite and > 0");
     const bool host = a->source == MFX_DN_SRC_HOST;

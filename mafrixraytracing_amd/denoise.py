@@ -17,7 +17,9 @@ this order, for each term whose sigma is > 0, g = g * (1.0 / (1.0 + term)):
 
 wt = (k[|dx|] * k[|dy|]) * g; num_c = num_c + wt * C_q[c], den = den + wt, both from +0.0 in tap order;
 out_c = num_c / den. The next iteration reads this output. FP64, one rounding per operation; the
-weights are rational, so numpy and the GPU agree to the bit.
+weights are rational, so numpy and the GPU agree to the bit. A sigma > 0 whose divisor is 0 in FP64
+(sn*sn, sz*sz or sa*sa, or (sc*sc) * 0.25^i at an iteration that runs) is refused, here with ValueError
+and by the library with MFX_E_INVALID: the centre tap's term would be 0/0.
 
 The variance-guided rule (mfx_denoise_var, reference_denoise_var) carries a plane V, the variance of
 the pixel's mean luminance, beside the colour; L(c) = (c0 + c1) + c2, k3 = [1/2, 1/4]. Per iteration and
@@ -43,6 +45,13 @@ import numpy as np
 K = (0.375, 0.25, 0.0625)  # the B3 spline's taps 3/8, 1/4, 1/16 at |d| = 0, 1, 2
 
 
+def _zero_square(s: float) -> bool:
+    """A sigma > 0 whose square, the divisor of its term, has underflowed to 0 (below about 1.5e-162):
+    the centre tap's term would be 0/0 and every pixel NaN. mfx_denoise and mfx_denoise_var refuse it."""
+    s = float(s)
+    return s > 0.0 and s * s == 0.0
+
+
 @dataclass(frozen=True)
 class DenoiseConfig:
     iterations: int = 3
@@ -57,6 +66,16 @@ class DenoiseConfig:
         for s in (self.sigma_normal, self.sigma_depth, self.sigma_albedo, self.sigma_color):
             if not (np.isfinite(s) and s >= 0):
                 raise ValueError("every sigma must be finite and >= 0")
+        for s in (self.sigma_normal, self.sigma_depth, self.sigma_albedo):
+            if _zero_square(s):
+                raise ValueError("a sigma > 0 must have a non-zero square")
+        if self.sigma_color > 0:  # the colour term divides by sc2 * 0.25^i: the loop's own products
+            sc2 = float(self.sigma_color) * float(self.sigma_color)
+            quarter = 1.0
+            for _ in range(self.iterations):
+                if sc2 * quarter == 0.0:
+                    raise ValueError("sigma_color > 0 must keep (sigma_color^2) * 0.25^i non-zero at every iteration")
+                quarter = quarter * 0.25
 
 
 def _d2(a, b):
@@ -79,7 +98,7 @@ def reference_denoise(color: np.ndarray, features: np.ndarray, w: int, h: int,
     sc2 = cfg.sigma_color * cfg.sigma_color
     X, Y = np.meshgrid(np.arange(w), np.arange(h), indexing="ij")
     quarter = 1.0  # 0.25^i
-    with np.errstate(divide="ignore", invalid="ignore"):
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         for i in range(cfg.iterations):
             s = 1 << i
             num = np.zeros((w, h, 3))
@@ -134,6 +153,9 @@ class DenoiseVarConfig:
         for s in (self.sigma_normal, self.sigma_depth, self.sigma_albedo, self.sigma_luma):
             if not (np.isfinite(s) and s >= 0):
                 raise ValueError("every sigma must be finite and >= 0")
+        for s in (self.sigma_normal, self.sigma_depth, self.sigma_albedo):  # (sigma_luma's square is added to luma_floor > 0)
+            if _zero_square(s):
+                raise ValueError("a sigma > 0 must have a non-zero square")
         if not (np.isfinite(self.luma_floor) and self.luma_floor > 0):
             raise ValueError("luma_floor must be finite and > 0")
 

@@ -101,3 +101,18 @@ def scalar_denoise(color, features, w, h, cfg):
     r = np.ones((w * h, 4))
     r[:, :3] = np.array(C)
     return r
+
+
+def smallest_with_a_square():
+    """The smallest double s > 0 with s*s != 0.0 (about 1.5e-162), by bisection over the bit patterns."""
+    lo, hi = np.array([1e-170]).view(np.int64)[0], np.array([1e-150]).view(np.int64)[0]
+    while hi - lo > 1:
+        mid = lo + (hi - lo) // 2
+        s = float(np.array([mid]).view(np.float64)[0])
+        if s * s != 0.0:
+            hi = mid
+        else:
+            lo = mid
+    s, below = (float(np.array([b]).view(np.float64)[0]) for b in (hi, lo))
+    assert s * s != 0.0 and below * below == 0.0 and 1e-163 < s < 1e-161
+    return s, below

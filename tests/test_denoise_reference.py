@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from denoise_helpers import oracle_features, oracle_frame, scalar_denoise
+from denoise_helpers import oracle_features, oracle_frame, scalar_denoise, smallest_with_a_square
 
 HEADER = os.path.join(ROOT, "include", "mafrix_rt.h")
 
@@ -28,6 +28,32 @@ def test_defaults():
                 dict(sigma_depth=float("inf"))):
         with pytest.raises(ValueError):
             DenoiseConfig(**bad)
+
+
+def test_sigmas_whose_divisor_is_zero_are_refused():
+    """A sigma > 0 whose square is 0 in FP64, or a sigma_color whose (sc*sc) * 0.25^i is 0 at an iteration
+    that runs, would make the centre tap's term 0/0 and every pixel NaN: ValueError, as the library's
+    MFX_E_INVALID. The smallest sigma with a non-zero square is accepted and gives a finite image."""
+    from mafrixraytracing_amd.denoise import DenoiseConfig, reference_denoise
+    s_min, s_below = smallest_with_a_square()
+    w, h = 7, 5
+    rng = np.random.default_rng(8)
+    f, color = _features(rng, w * h), rng.uniform(0.0, 2.0, (w * h, 4))
+    for name in ("sigma_normal", "sigma_depth", "sigma_albedo", "sigma_color"):
+        it = 1 if name == "sigma_color" else 3
+        for bad in (1e-163, 1e-170, 5e-324, s_below):
+            with pytest.raises(ValueError):
+                DenoiseConfig(iterations=it, **{name: bad})
+        out = reference_denoise(color, f, w, h, DenoiseConfig(iterations=it, **{name: s_min}))
+        assert np.isfinite(out).all(), name
+    DenoiseConfig(iterations=1, sigma_color=1e-160)  # sc2 = 1e-320, a subnormal
+    with pytest.raises(ValueError):
+        DenoiseConfig(iterations=8, sigma_color=1e-160)  # ... which 0.25^6 takes to 0
+    with pytest.raises(ValueError):
+        DenoiseConfig(iterations=2, sigma_color=s_min)
+    assert np.isfinite(reference_denoise(color, f, w, h, DenoiseConfig(iterations=6, sigma_color=1e-160))).all()
+    with pytest.raises(ValueError):
+        DenoiseConfig(iterations=7, sigma_color=1e-160)
 
 
 def test_constant_image_stays_constant():

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from denoise_helpers import oracle_features, oracle_frame
+from denoise_helpers import oracle_features, oracle_frame, smallest_with_a_square
 from denoise_var_helpers import mean_and_moments, oracle_sample_frames, scalar_denoise_var
 
 HEADER = os.path.join(ROOT, "include", "mafrix_rt.h")
@@ -45,6 +45,25 @@ def test_defaults():
                 dict(luma_floor=float("nan")), dict(luma_floor=float("inf"))):
         with pytest.raises(ValueError):
             DenoiseVarConfig(**bad)
+
+
+def test_sigmas_whose_square_is_zero_are_refused():
+    """sigma_normal, sigma_depth or sigma_albedo > 0 with a square of 0 in FP64 would make the centre tap's
+    term 0/0: ValueError, as the library's MFX_E_INVALID. sigma_luma needs no such rule: its square is
+    added to luma_floor > 0."""
+    from mafrixraytracing_amd.denoise import DenoiseVarConfig, reference_denoise_var
+    s_min, s_below = smallest_with_a_square()
+    w, h = 7, 5
+    color, var, f = _inputs(w, h)
+    for name in ("sigma_normal", "sigma_depth", "sigma_albedo"):
+        for bad in (1e-163, 1e-170, 5e-324, s_below):
+            with pytest.raises(ValueError):
+                DenoiseVarConfig(**{name: bad})
+        out, v = reference_denoise_var(color, var, f, w, h, DenoiseVarConfig(**{name: s_min}))
+        assert np.isfinite(out).all() and np.isfinite(v).all(), name
+    for luma in (1e-170, 5e-324, s_below):
+        out, v = reference_denoise_var(color, var, f, w, h, DenoiseVarConfig(sigma_luma=luma))
+        assert np.isfinite(out).all() and np.isfinite(v).all(), luma
 
 
 def test_variance_of_mean():

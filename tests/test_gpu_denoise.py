@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import SEED, scene
-from denoise_helpers import oracle_features
+from denoise_helpers import oracle_features, smallest_with_a_square
 
 pytestmark = pytest.mark.gpu
 
@@ -164,3 +164,52 @@ def test_refusals(gpu):
             assert rc == -4 and b"mfx_aov" in err, kw  # MFX_E_STATE
             rc, err = denoise(ctx)
             assert rc == -4 and b"mfx_denoise" in err, kw
+
+
+def test_refusals_of_sigmas_whose_divisor_is_zero(gpu):
+    """A sigma > 0 whose square is 0 in FP64, or a sigma_color whose (sc*sc) * 0.25^i reaches 0 at an
+    iteration that runs, made every pixel NaN (the centre tap's term was 0/0): MFX_E_INVALID now. Just
+    above the limit the call is accepted, finite, and the reference's bits."""
+    from mafrixraytracing_amd.abi import MfxDenoiseCfg, dptr
+    from mafrixraytracing_amd.denoise import reference_denoise
+    w = h = 16
+    s_min, s_below = smallest_with_a_square()
+
+    def rc_of(ctx, frame, **kw):
+        d = dict(iterations=3, source=0, count=0.0, sigma_normal=0.1, sigma_depth=0.02, sigma_albedo=0.05, sigma_color=0.0)
+        d.update(kw)
+        cfg = MfxDenoiseCfg(**d)
+        out = np.full((w * h, 4), -1.0)
+        rc = ctx.lib.mfx_denoise(ctx._h, C.byref(cfg), dptr(frame), dptr(out), None, None)
+        return rc, ctx.lib.mfx_last_error(), out
+
+    with _ctx(scene("cornell", w, h)) as ctx:
+        feat = ctx.aov(4)
+        frame = ctx.sample(4)
+        for name in ("sigma_normal", "sigma_depth", "sigma_albedo", "sigma_color"):
+            it = 1 if name == "sigma_color" else 3  # (a later iteration's 0.25^i would take sc2 to 0)
+            for bad in (1e-163, 1e-170, 5e-324, s_below):
+                rc, err, out = rc_of(ctx, frame, iterations=it, **{name: bad})
+                assert rc == -1 and b"mfx_denoise" in err, (name, bad)  # MFX_E_INVALID
+                assert (out == -1.0).all()  # nothing was written
+            rc, err, out = rc_of(ctx, frame, iterations=it, **{name: s_min})
+            assert rc == 0, (name, err)
+            assert np.isfinite(out).all(), name
+            cfg = _cfg(iterations=it, **{name: s_min})
+            assert np.array_equal(out, reference_denoise(frame, feat, w, h, cfg)), name
+            assert np.array_equal(ctx.denoise(frame, cfg=cfg), out)
+        # sc2 = 1e-320 survives the first iteration's 0.25^0 and is 0 by the seventh
+        assert rc_of(ctx, frame, iterations=8, sigma_color=1e-160)[0] == -1
+        rc, err, out = rc_of(ctx, frame, iterations=1, sigma_color=1e-160)
+        assert rc == 0 and np.isfinite(out).all()
+        assert np.array_equal(out, reference_denoise(frame, feat, w, h, _cfg(iterations=1, sigma_color=1e-160)))
+        # the last iteration at which it is still non-zero, found as the library finds it
+        sc2, quarter, last = 1e-160 * 1e-160, 1.0, 0
+        while sc2 * quarter != 0.0:
+            last += 1
+            quarter = quarter * 0.25
+        assert 1 < last < 8
+        assert rc_of(ctx, frame, iterations=last + 1, sigma_color=1e-160)[0] == -1
+        rc, err, out = rc_of(ctx, frame, iterations=last, sigma_color=1e-160)
+        assert rc == 0 and np.isfinite(out).all()
+        assert np.array_equal(out, reference_denoise(frame, feat, w, h, _cfg(iterations=last, sigma_color=1e-160)))

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import SEED, scene
+from denoise_helpers import smallest_with_a_square
 from denoise_var_helpers import mean_and_moments, oracle_sample_frames, pixel_counts
 
 pytestmark = pytest.mark.gpu
@@ -175,3 +176,46 @@ def test_refusals(gpu):
             for src in (HOST, DEV):
                 rc, err = denoise_var(ctx, **src)
                 assert rc == -4 and b"mfx_denoise_var" in err, (kw, src)  # MFX_E_STATE
+
+
+def test_refusals_of_sigmas_whose_square_is_zero(gpu):
+    """sigma_normal, sigma_depth or sigma_albedo > 0 with a square of 0 in FP64 made every pixel of the
+    colour and the variance NaN (the centre tap's term was 0/0): MFX_E_INVALID now. The smallest sigma
+    with a non-zero square is accepted, finite, and the reference's bits; sigma_luma needs no such rule
+    (lden = 0 * Vf + luma_floor > 0)."""
+    from mafrixraytracing_amd.abi import MfxDenoiseVarCfg, dptr
+    from mafrixraytracing_amd.denoise import reference_denoise_var
+    w = h = 16
+    s_min, s_below = smallest_with_a_square()
+
+    def rc_of(ctx, frame, variance, **kw):
+        d = dict(iterations=3, source=0, sigma_normal=0.1, sigma_depth=0.02, sigma_albedo=0.05, sigma_luma=4.0,
+                 luma_floor=1e-6)
+        d.update(kw)
+        cfg = MfxDenoiseVarCfg(**d)
+        out, vout = np.full((w * h, 4), -1.0), np.full(w * h, -1.0)
+        rc = ctx.lib.mfx_denoise_var(ctx._h, C.byref(cfg), dptr(frame), dptr(variance), dptr(out), dptr(vout), None, None)
+        return rc, ctx.lib.mfx_last_error(), out, vout
+
+    with _ctx(scene("cornell", w, h)) as ctx:
+        feat = ctx.aov(4)
+        frame = ctx.sample(4)
+        var = np.random.default_rng(11).uniform(0.0, 0.05, w * h)
+        var[::7] = 0.0
+        for name in ("sigma_normal", "sigma_depth", "sigma_albedo"):
+            for bad in (1e-163, 1e-170, 5e-324, s_below):
+                rc, err, out, vout = rc_of(ctx, frame, var, **{name: bad})
+                assert rc == -1 and b"mfx_denoise_var" in err, (name, bad)  # MFX_E_INVALID
+                assert (out == -1.0).all() and (vout == -1.0).all()  # nothing was written
+            for ok in ({name: s_min}, {name: s_min, "sigma_luma": 1e-170}):
+                rc, err, out, vout = rc_of(ctx, frame, var, **ok)
+                assert rc == 0, (ok, err)
+                assert np.isfinite(out).all() and np.isfinite(vout).all(), ok
+                ref, rvar = reference_denoise_var(frame, var, feat, w, h, _cfg(**ok))
+                assert np.array_equal(out, ref) and np.array_equal(vout, rvar), ok
+        for luma in (1e-170, 5e-324, s_below, s_min):
+            rc, err, out, vout = rc_of(ctx, frame, var, sigma_luma=luma)
+            assert rc == 0, (luma, err)
+            ref, rvar = reference_denoise_var(frame, var, feat, w, h, _cfg(sigma_luma=luma))
+            assert np.isfinite(ref).all() and np.isfinite(rvar).all()
+            assert np.array_equal(out, ref) and np.array_equal(vout, rvar), luma

@@ -101,6 +101,48 @@ def test_fp64_device_math_bit_exact(gpu):
     assert np.array_equal(sq, np.sqrt(a))
 
 
+def test_fp64_device_math_bit_exact_on_subnormals(gpu):
+    """Division and sqrt where the test above never goes: subnormal operands (5e-324, 1e-310, k * 2^-1074),
+    quotients that land in the subnormal range or underflow to 0, and sqrt of subnormals. (The denoiser
+    divides by subnormals: a sigma_color of 1e-160 has the square 1e-320.)"""
+    from mafrixraytracing_amd.native import fp64_selftest
+    rng = np.random.default_rng(4)
+    n = 20000
+    tiny = np.finfo(np.float64).tiny  # the smallest normal double, 2^-1022
+    sub = np.ldexp(rng.integers(1, 1 << 52, n).astype(np.float64), -1074)  # k * 2^-1074 over the whole subnormal range
+    low = np.ldexp(rng.integers(1, 1 << 12, n).astype(np.float64), -1074)  # its few-bit end
+    normal = rng.uniform(0.5, 4.0, n) * rng.choice([-1.0, 1.0], n)
+    a = np.concatenate([
+        [5e-324, 1e-310, 5e-324, 1e-310, 5e-324, 1e-310, 1.0, tiny, tiny, np.nextafter(tiny, 0.0)],
+        sub,                                # subnormal / normal: a subnormal quotient, rounded at its last bits
+        low,
+        sub,                                # subnormal / subnormal: a normal quotient
+        rng.uniform(0.5, 4.0, n),           # normal / subnormal: up to overflow
+        10.0 ** rng.uniform(-300, -290, n),  # normal / large: the quotient lands in the subnormal range
+        10.0 ** rng.uniform(-300, -290, n),  # ... or underflows to 0
+        tiny * rng.uniform(1.0, 4.0, n),    # just above the subnormal range, divided down into it
+    ])
+    b = np.concatenate([
+        [1.0, 1.0, 3.0, -7.0, 5e-324, 5e-324, 5e-324, 2.0, 3.0, -1.0],
+        normal,
+        normal,
+        np.ldexp(rng.integers(1, 1 << 52, n).astype(np.float64), -1074) * rng.choice([-1.0, 1.0], n),
+        np.ldexp(rng.integers(1, 1 << 52, n).astype(np.float64), -1074),
+        10.0 ** rng.uniform(8, 30, n),
+        10.0 ** rng.uniform(30, 300, n),
+        rng.uniform(1.0, 1e6, n),
+    ])
+    assert len(a) == len(b) and (a > 0).all()
+    with np.errstate(all="ignore"):
+        want_dv, want_sq = a / b, np.sqrt(a)
+    nonzero_sub = (want_dv != 0) & (np.abs(want_dv) < tiny)
+    assert nonzero_sub.sum() > 3 * n and (want_dv == 0).sum() > n // 2 and np.isinf(want_dv).any()
+    assert ((a < tiny).sum() > 3 * n) and not np.isnan(want_dv).any()
+    dv, sq = fp64_selftest(a, b)
+    assert np.array_equal(dv, want_dv), int((dv != want_dv).sum())
+    assert np.array_equal(sq, want_sq), int((sq != want_sq).sum())
+
+
 @pytest.mark.parametrize("name,w,h,spp", [
     ("two_spheres_plane", 64, 64, 8),
     ("cornell", 48, 48, 8),
