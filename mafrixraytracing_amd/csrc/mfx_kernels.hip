@@ -523,7 +523,8 @@ __global__ void fp64_selftest_kernel(const double* a, const double* b, int64_t n
 // IHitable.fs:18-54): rec = 24 doubles per case (lo, hi, o, d, tMin, tMax, then a triangle v0, e1,
 // e2 whose vertex box lies in [lo, hi], one pad); out = 3 per case: the FP64 test's answer (0/1),
 // aabb_screen32's (1, 0 or -1 when it leaves the case to the FP64 test) and tri_box_pass's (1
-// proved to pass, 0 not proved)
+// proved to pass, 0 not proved; 2 added if the plain statement of the proof, tri_box_pass<false>,
+// decides otherwise than the folded one the kernels run: never, tests/test_gpu_box_proof_fold.py)
 __global__ void aabb_selftest_kernel(const double* rec, int64_t n, int32_t* out) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
@@ -531,7 +532,9 @@ __global__ void aabb_selftest_kernel(const double* rec, int64_t n, int32_t* out)
     const DV o = ld3(r + 6), d = ld3(r + 9);
     out[3 * k] = aabb_hit64(r, r + 3, o, d, r[12], r[13]) ? 1 : 0;
     out[3 * k + 1] = aabb_screen32(r, r + 3, o, d, r[12], r[13]);
-    out[3 * k + 2] = tri_box_pass(ld3(r + 14), ld3(r + 17), ld3(r + 20), o, d, r[12], r[13]) ? 1 : 0;
+    const bool fold = tri_box_pass<true>(ld3(r + 14), ld3(r + 17), ld3(r + 20), o, d, r[12], r[13]);
+    const bool plain = tri_box_pass<false>(ld3(r + 14), ld3(r + 17), ld3(r + 20), o, d, r[12], r[13]);
+    out[3 * k + 2] = (fold ? 1 : 0) | (fold != plain ? 2 : 0);
 }
 
 // ----------------------------------------------------------------------------------------------

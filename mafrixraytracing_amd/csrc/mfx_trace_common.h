@@ -183,7 +183,17 @@ __device__ __forceinline__ int aabb_screen32(const double* lo, const double* hi,
     }
     return res;
 }
+#ifndef MFX_AABB_SIGN_LOCAL
+#define MFX_AABB_SIGN_LOCAL 1  // A/B knob: the box test's direction compares made where it runs (below)
+#endif
 __device__ __forceinline__ bool aabb_hit(const double* lo, const double* hi, DV o, DV d, double tMin, double tMax) {
+#if MFX_AABB_SIGN_LOCAL
+    // The box test runs for the few candidates tri_box_pass does not prove, but its compares of the
+    // direction (d >= 0 per axis, the FP32 range checks) are loop invariant: hoisted, they are lane masks
+    // computed and spilled at every leaf visit. Through an empty asm the direction is a new value here, so
+    // they are computed in this branch, when it runs.
+    asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z));
+#endif
 #if MFX_AABB_SCREEN
     const int r = aabb_screen32(lo, hi, o, d, tMin, tMax);
     if (r >= 0) return r == 1;
@@ -475,11 +485,31 @@ __device__ __forceinline__ bool sphere_hit64(const SlotR& s, DV o, DV d, double 
 // |v0 - o| + |e1| + |e2| per axis; each comparison needs a gap of 2^-18 of that on both sides.
 // false: not proved (grazing rays, hits within ~1e-5 of the vertex box's faces, zero or tiny
 // direction components, t next to tMin/tMax): the caller runs the FP64 test on the loaded box.
+// FOLD: the same decision from fewer lane masks. The test runs once per slot of a leaf, and every
+// per-ray condition in it (the direction components' range checks and signs: six compares) is loop
+// invariant: the compiler computes them before the slot loop as lane masks in scalar register pairs,
+// which the kernels at their register limits spill to VGPR lanes — 12 v_readlane per slot and 12
+// v_writelane per leaf visit in k_extend, k_shadow and k_camera alike (scripts/isa_spills.py). Here
+//  - a range check x in [2^-60, 2^60] of a non-negative float is bits(x) - bits(2^-60) <= bits(2^60) -
+//    bits(2^-60) as unsigned integers (non-negative floats order as their bits; NaN and inf lie above,
+//    zero and denormals wrap around: all out of range either way), and six checks are one compare of
+//    the largest difference: the per-ray part is a value in a vector register, not a mask;
+//  - mn <= mx, so the products with 1 / d are ordered by d's sign: the entry bound is their minimum
+//    and the exit bound their maximum, the values the two selects on d >= 0 picked (they differ only
+//    where the checks above have failed already, and in the sign of a zero, which no comparison sees).
+#ifndef MFX_BOX_PROOF_FOLD
+// which leaf tests run the folded form: bit 0 closest-hit leaves (k_extend), bit 1 shadow rays (k_shadow),
+// bit 2 packets (k_camera). Shadow rays keep the plain form: folded, k_shadow's slot loop loses its lane
+// ops too (12 -> 2), but its launches were no faster on C2 (DESIGN.md "Round-8 results")
+#define MFX_BOX_PROOF_FOLD 5
+#endif
+template <bool FOLD = true>
 __device__ __forceinline__ bool tri_box_pass(DV a, DV e1, DV e2, DV o, DV d, double tMin, double tMax) {
     const double aa[3] = {a.x, a.y, a.z}, b1[3] = {e1.x, e1.y, e1.z}, b2[3] = {e2.x, e2.y, e2.z};
     const double oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
     float U[3], L[3], E[3];
     bool ok = true;
+    uint32_t span = 0;  // FOLD: the largest bits(x) - bits(2^-60) over the six range-checked values
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float A = (float)(aa[k] - oo[k]), p = (float)b1[k], q = (float)b2[k];
@@ -487,13 +517,15 @@ __device__ __forceinline__ bool tri_box_pass(DV a, DV e1, DV e2, DV o, DV d, dou
         const float mn = fminf(A, fminf(x1, x2)), mx = fmaxf(A, fmaxf(x1, x2));
         const float R = fabsf(A) + fabsf(p) + fabsf(q);
         const float df = (float)dd[k], adf = fabsf(df);
-        ok = ok && adf >= 0x1p-60f && adf <= 0x1p60f && R >= 0x1p-60f && R <= 0x1p60f;
+        if (FOLD) span = max(span, max(__float_as_uint(adf) - 0x21800000u, __float_as_uint(R) - 0x21800000u));
+        else ok = ok && adf >= 0x1p-60f && adf <= 0x1p60f && R >= 0x1p-60f && R <= 0x1p60f;
         const float rc = __builtin_amdgcn_rcpf(df);
         const float qm = mn * rc, qM = mx * rc;
-        U[k] = dd[k] >= 0. ? qm : qM;  // entry <= the vertex box's entry value
-        L[k] = dd[k] >= 0. ? qM : qm;  // exit >= the vertex box's exit value
+        U[k] = FOLD ? fminf(qm, qM) : (dd[k] >= 0. ? qm : qM);  // entry <= the vertex box's entry value
+        L[k] = FOLD ? fmaxf(qm, qM) : (dd[k] >= 0. ? qM : qm);  // exit >= the vertex box's exit value
         E[k] = (R * fabsf(rc) + fmaxf(fabsf(qm), fabsf(qM))) * 0x1p-18f;
     }
+    if (FOLD) ok = span <= 0x5d800000u - 0x21800000u;
     if (!ok) return false;
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -602,7 +634,8 @@ __device__ __forceinline__ bool leaf_hit(const SceneView& S, int code, DV o, DV 
         if (!shd && B.found && t > B.t) continue;  // cannot win: skip the box test
         if (!shd && !beats(B, t, first, info)) continue;
 #if MFX_TRI_BOX_PROOF && MFX_LEAF_PRELOAD
-        if (kind != MFX_KIND_SPHERE && tri_box_pass(r.a, r.b, r.c, o, d, tMin, tMax)) {
+        if (kind != MFX_KIND_SPHERE &&
+            tri_box_pass<((MFX_BOX_PROOF_FOLD >> (UNI ? 2 : (SHADOW ? 1 : 0))) & 1) != 0>(r.a, r.b, r.c, o, d, tMin, tMax)) {
             // the reference leaf's box test passes (proved; its box is not read)
         } else
 #endif

@@ -334,7 +334,8 @@ def fp64_selftest(a: np.ndarray, b: np.ndarray, device: int = 0):
 
 def aabb_selftest(rec: np.ndarray, device: int = 0):
     """(FP64 AABB.hit answers, FP32-screen answers: 1, 0 or -1 = left to FP64, vertex-box proofs:
-    1 or 0) for n x 24 records (mfx_aabb_selftest)."""
+    1 or 0, plus 2 where the proof's folded and plain forms disagree: never) for n x 24 records
+    (mfx_aabb_selftest)."""
     lib = load_library()
     rec = np.ascontiguousarray(rec, dtype=np.float64).reshape(-1, 24)
     out = np.zeros((len(rec), 3), dtype=np.int32)
