@@ -194,6 +194,45 @@ int mfx_instancing_info(mfx_ctx* ctx, double out[8]);
 int mfx_build_instanced_info(const mfx_scene_desc* scene, const mfx_instance* instances, int32_t ninstances,
                              int32_t flags, double out[8], int32_t* stack_entries);
 
+/* ---- the camera (an extension of the ABI: the reference's PinholeCamera has mutable position /
+ * topleft / coord, Camera.fs:122-133, and Film.Reset exists for a camera move). Additive in ABI 6. ---- */
+
+/* Host-only (no device needed): the constructor mfx_create runs on mfx_scene_desc.camera (with
+ * derived != 0 the fields as they are). out = position, topleft, right, down (3 doubles each).
+ * MFX_E_INVALID: a NULL argument.                                                              */
+int mfx_pinhole_derive(const mfx_pinhole* cam, double out[12]);
+/* out[0..11] = the context's current derived camera (position, topleft, right, down), out[12] = the
+ * camera epoch: 0 after create, +1 per mfx_set_camera that changed the camera, out[13] = the widening
+ * eps the traversal images were built with, out[14] = the eps the current camera needs
+ * ((float)ldexp(R + T, -19), DESIGN.md §3: out[14] <= out[13] always), out[15] = the number of times
+ * mfx_set_camera had to build the images again.                                                 */
+int mfx_camera_info(mfx_ctx* ctx, double out[16]);
+/* Makes `cam` the camera of every later call, on every device of a device list. Waits for the
+ * context's work first, a render-ahead batch traced in the background included.
+ * In place: when the widening the new position needs is at most the one the images were built with
+ * (two-level scenes: the template BVHs' too), only the camera changes: the boxes stay conservative
+ * for every ray the new camera starts, and every result is what a context created with `cam` gives.
+ * Rebuild: otherwise the scene is prepared again for the new camera from the description the context
+ * has kept since creation (host memory: 104 B per primitive, plus the material and instance tables),
+ * by mfx_create's own code: afterwards mfx_build_info's digest, the launch shapes and every result
+ * are those of a fresh mfx_create with `cam` (an instanced scene keeps the flat / two-level choice of
+ * its creation). The seed, the options, next_sample, the film and its frame count and the
+ * accumulator's contents are kept. A failed rebuild leaves the old camera and images in place and
+ * returns the error.
+ * What it invalidates: frames held by render-ahead are never served afterwards (the next one-sample
+ * call traces a new batch from the film as it then is); an adaptive result (mfx_sample_adaptive_resume
+ * and MFX_DN_SRC_ADAPTIVE return MFX_E_STATE until mfx_sample_adaptive runs again: a resume must not
+ * mix cameras); the feature buffers (mfx_denoise, mfx_denoise_var and mfx_temporal return MFX_E_STATE
+ * until mfx_aov runs again). The temporal history is kept: mfx_temporal reprojects it.
+ * What it leaves alone: the film, the accumulator, next_sample and the ray counters. As in the
+ * reference, where moving the camera and Film.Reset are separate, the caller decides whether the film
+ * starts over: call mfx_reset (and mfx_accum_clear) after the move, or the film mixes both views.
+ * A camera whose derived fields are bit-equal to the current ones is a successful no-op: no wait, no
+ * new epoch. MFX_E_INVALID: a NULL argument, a non-finite field (direction, fov and aspect count only
+ * with derived == 0, topleft, right and down only with derived != 0) or a non-finite derived camera,
+ * a zero direction with derived == 0.                                                           */
+int mfx_set_camera(mfx_ctx* ctx, const mfx_pinhole* cam);
+
 /* ---- the reference's render API --------------------------------------------------------- */
 
 /* == IPixelIntegrator.Sample(spp) (IIntegrator.fs:35-40, Integrators.fs:161-172):
@@ -347,7 +386,8 @@ typedef struct mfx_denoise_cfg {
  * mfx_render_rgba8's layout), ms (device time from HIP events): each may be NULL. Changes no context
  * state but its own two ping-pong colour buffers (allocated at the first call).
  * MFX_E_INVALID: a NULL ctx or cfg, a bad struct, SRC_HOST with NULL color_in, SRC_ACCUM with
- * count <= 0. MFX_E_STATE: as mfx_aov, and additionally when mfx_aov has not run on this context. */
+ * count <= 0. MFX_E_STATE: as mfx_aov, and additionally when mfx_aov has not run on this context, or
+ * not since the last mfx_set_camera (the features are another view's: run mfx_aov again).          */
 int mfx_denoise(mfx_ctx* ctx, const mfx_denoise_cfg* cfg, const double* color_in,
                 double* out_xmajor_rgba, uint8_t* rgba_ymajor, double* ms);
 
@@ -374,7 +414,7 @@ int mfx_denoise(mfx_ctx* ctx, const mfx_denoise_cfg* cfg, const double* color_in
 #define MFX_DN_SRC_ADAPTIVE 2  /* the last mfx_sample_adaptive's result, as resumed since, on the device */
 typedef struct mfx_denoise_var_cfg {
     int32_t iterations;   /* 1..8 */
-    int32_t source;       /* MFX_DN_SRC_HOST or MFX_DN_SRC_ADAPTIVE */
+    int32_t source;       /* MFX_DN_SRC_HOST, MFX_DN_SRC_ADAPTIVE or MFX_DN_SRC_TEMPORAL (below: mfx_temporal) */
     int32_t reserved[2];  /* 0 */
     double sigma_normal, sigma_depth, sigma_albedo, sigma_luma; /* finite, >= 0; 0 switches the term off */
     /* sigma_normal, sigma_depth, sigma_albedo > 0 must have a non-zero square in FP64, as for
@@ -394,10 +434,64 @@ typedef struct mfx_denoise_var_cfg {
  * MFX_E_INVALID: a NULL ctx or cfg, a bad struct, pointers that do not fit the source.
  * MFX_E_STATE: as mfx_aov; when mfx_aov has not run on this context; MFX_DN_SRC_ADAPTIVE when the
  * accumulator does not hold an mfx_sample_adaptive result or its mfx_sample_adaptive_resume
- * continuation (none yet, or a trace, mfx_accum_clear or mfx_accum_attach since).       */
+ * continuation (none yet, or a trace, mfx_accum_clear, mfx_accum_attach or mfx_set_camera since);
+ * feature buffers traced before the last mfx_set_camera (run mfx_aov again).                 */
 int mfx_denoise_var(mfx_ctx* ctx, const mfx_denoise_var_cfg* cfg, const double* color_in,
                     const double* variance_in, double* out_xmajor_rgba, double* var_out,
                     uint8_t* rgba_ymajor, double* ms);
+
+/* mfx_temporal: reproject the previous result into the current view and merge it with this frame's
+ * samples (the temporal third of SVGF; the variance estimate and the a-trous filter are
+ * mfx_denoise_var). Additive in ABI 6. Every material is traced as LambertianBrdf (Material.fs:52,
+ * 68,121): a surface point's outgoing radiance does not depend on the view direction, so history
+ * reprojected onto the same surface point estimates the same quantity.
+ * Per pixel p = (x, y), q = x*h + y: this frame's colour C, variance of the mean luminance V and
+ * sample count n (a double); the current feature planes N (normal), Z (depth), F (hit fraction) and
+ * camera (o, tl, r, d); the history the context owns: colour HC, variance HV, effective count HN, its
+ * view's features HNm, HZ, HF and camera (o', tl', r', d'). FP64, one rounding per operation, no
+ * contraction; dot(a,b) = (a0*b0 + a1*b1) + a2*b2, cross by components a1*b2 - a2*b1, ..., d2 as above.
+ *  1. No history (the first call, or restart != 0), or F != 1.0: reject.
+ *  2. u = (x + 0.5)/w, v = (y + 0.5)/h; target = (tl + r*u) + d*v; dir = normalize(target - o) as
+ *     mfx_aov normalizes its camera ray (l = sqrt(dot), each component / l); P = o + dir*Z.
+ *  3. e = P - o', a = tl' - o', nn = cross(r', d'); den = dot(e, nn), num = dot(a, nn); reject unless
+ *     num*den > 0. s = num/den, g = e*s - a; u' = dot(g, r')/dot(r', r'), v' = dot(g, d')/dot(d', d');
+ *     reject unless 0 <= u' < 1 and 0 <= v' < 1. x' = min(w-1, (int)floor(u'*w)), y' likewise,
+ *     q' = x'*h + y': the nearest history pixel. (u', v') is exactly the point's image for orthogonal
+ *     r', d', which the constructor gives; with skewed `derived` axes it is the same arithmetic and only
+ *     approximately the same point.
+ *  4. At q': reject unless HF == 1.0; ze = sqrt(dot(e, e)), dz = ze - HZ; reject unless
+ *     dz*dz <= (tol_depth*tol_depth)*(ze*ze); reject unless d2(N_p, HNm_q') <= tol_normal2.
+ *  5. Accept: nh = HN_q' < max_history ? HN_q' : max_history, nt = n + nh, wc = n/nt, wh = nh/nt;
+ *     C'_c = wc*C_c + wh*HC_c, V' = (wc*wc)*V + (wh*wh)*HV, N' = nt. On a reject C' = C, V' = V, N' = n.
+ *  6. Afterwards the history is (C', V', N') with the current features and camera (two buffers that
+ *     swap by pointer: the gather reads q' while q is written).
+ * The host statement of the rule is mafrixraytracing_amd/temporal.py, reference_temporal: the same bits. */
+#define MFX_DN_SRC_TEMPORAL 3  /* mfx_denoise_var: the temporal history's C' and V', where they lie on the device */
+typedef struct mfx_temporal_cfg {
+    int32_t source;        /* MFX_DN_SRC_HOST or MFX_DN_SRC_ADAPTIVE */
+    int32_t restart;       /* != 0: ignore and replace the history */
+    int32_t reserved[2];   /* 0 */
+    double tol_depth;      /* finite, >= 0: relative depth tolerance (0 accepts only dz == 0) */
+    double tol_normal2;    /* finite, >= 0: bound on d2 of the normals */
+    double max_history;    /* finite, > 0: cap on the history's weight, in samples */
+} mfx_temporal_cfg;        /* 40 bytes */
+/* MFX_DN_SRC_HOST: color_in is a frame in mfx_sample's layout (alpha ignored), variance_in[x*h + y]
+ * and count_in[x*h + y] w*h doubles each; all three are required; count_in must be finite and is
+ * expected > 0, variance_in >= 0 (neither validated). MFX_DN_SRC_ADAPTIVE: all three must be NULL; C and
+ * V are exactly mfx_denoise_var's reading of the adaptive result and n = (double)tile_spp[tile].
+ * out_xmajor_rgba, rgba_ymajor and ms are mfx_denoise_var's, of C'; var_out[x*h + y] = V',
+ * count_out[x*h + y] = N', *accepted = the pixels that took history. Each output may be NULL.
+ * mfx_denoise_var with source MFX_DN_SRC_TEMPORAL then filters C' and V' (host pointers NULL);
+ * it returns MFX_E_STATE without a history, or with one merged under another camera epoch than the
+ * feature buffers'. The history is kept across mfx_set_camera: that is its purpose.
+ * The call changes nothing but its own buffers (two history buffers of 10 planes, one count plane,
+ * allocated at the first call; mfx_denoise_var's first colour and variance buffers as staging).
+ * MFX_E_INVALID: a NULL ctx or cfg, a bad struct, pointers that do not fit the source. MFX_E_STATE:
+ * whatever mfx_aov refuses: a device list, partitions; no mfx_aov yet, or none since the last mfx_set_camera;
+ * MFX_DN_SRC_ADAPTIVE without a valid adaptive result.                                             */
+int mfx_temporal(mfx_ctx* ctx, const mfx_temporal_cfg* cfg, const double* color_in, const double* variance_in,
+                 const double* count_in, double* out_xmajor_rgba, double* var_out, double* count_out,
+                 uint8_t* rgba_ymajor, int64_t* accepted, double* ms);
 
 /* == Film.GetFrame(integrator, spp) + Scene.PostProcessAndToScreenBuffer
  * (Film.fs:18-34, Scene.fs:315-333): adds spp samples per pixel to the film, then writes the

@@ -7,6 +7,7 @@ Product layout:
   abi.py                       ctypes mirror of the header (stands in for the F# P/Invoke layer)
   native.py                    Scene / NativePixelIntegrator / Film over the ABI
   scene_io.py                  Scene XML v0.1 + OBJ/MTL loading with the reference's semantics
+  denoise.py / temporal.py     numpy statements of mfx_denoise, mfx_denoise_var and mfx_temporal
   distributed.py               one-process-per-GPU sample partitioning + RCCL reduce
 """
 from .abi import SceneArrays, load_library  # noqa: F401

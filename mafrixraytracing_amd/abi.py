@@ -30,6 +30,7 @@ MFX_MAX_DEVICES = 64
 MFX_DN_SRC_HOST = 0
 MFX_DN_SRC_ACCUM = 1
 MFX_DN_SRC_ADAPTIVE = 2
+MFX_DN_SRC_TEMPORAL = 3
 MFX_ABI_VERSION = 6
 # mfx_launch_info's entries, in order (MFX_LAUNCH_INFO_N of them)
 LAUNCH_INFO_KEYS = ("stack_size", "stack_lds_ext", "stack_lds_shd", "spill_ext", "spill_shd", "ntop_ext", "ntop_shd",
@@ -101,12 +102,19 @@ class MfxDenoiseVarCfg(C.Structure):
                 ("sigma_luma", C.c_double), ("luma_floor", C.c_double)]
 
 
+class MfxTemporalCfg(C.Structure):
+    """mfx_temporal_cfg: source, restart, the two tolerances and the history cap of mfx_temporal."""
+    _fields_ = [("source", C.c_int32), ("restart", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("tol_depth", C.c_double), ("tol_normal2", C.c_double), ("max_history", C.c_double)]
+
+
 assert C.sizeof(MfxPrim) == 104
 assert C.sizeof(MfxInstance) == 48
 assert C.sizeof(MfxAdaptive) == 32
 assert C.sizeof(MfxAdaptiveResume) == 32
 assert C.sizeof(MfxDenoiseCfg) == 56
 assert C.sizeof(MfxDenoiseVarCfg) == 56
+assert C.sizeof(MfxTemporalCfg) == 40
 
 # numpy structured dtype with the same layout as mfx_prim (for building big prim arrays fast)
 PRIM_DTYPE = np.dtype([("kind", "<i4"), ("material", "<i4"), ("p", "<f8", (4, 3))], align=True)
@@ -193,6 +201,11 @@ def _bind(lib, strict: bool = True):
         "mfx_aov": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _dp, _dp]),
         "mfx_denoise": (C.c_int, [C.c_void_p, _P(MfxDenoiseCfg), _dp, _dp, _P(C.c_uint8), _dp]),
         "mfx_denoise_var": (C.c_int, [C.c_void_p, _P(MfxDenoiseVarCfg), _dp, _dp, _dp, _dp, _P(C.c_uint8), _dp]),
+        "mfx_temporal": (C.c_int, [C.c_void_p, _P(MfxTemporalCfg), _dp, _dp, _dp, _dp, _dp, _dp, _P(C.c_uint8),
+                                   _P(C.c_int64), _dp]),
+        "mfx_pinhole_derive": (C.c_int, [_P(MfxPinhole), _dp]),
+        "mfx_camera_info": (C.c_int, [C.c_void_p, _dp]),
+        "mfx_set_camera": (C.c_int, [C.c_void_p, _P(MfxPinhole)]),
         "mfx_render_rgba8": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint8)]),
         "mfx_accumulate_render_rgba8": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint8)]),
         "mfx_stats": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -233,7 +246,7 @@ def _bind(lib, strict: bool = True):
 
 
 EXPORTED_SYMBOLS = [
-    "mfx_create", "mfx_create_instanced", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_sample_adaptive_resume", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
+    "mfx_create", "mfx_create_instanced", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_sample_adaptive_resume", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_temporal", "mfx_pinhole_derive", "mfx_camera_info", "mfx_set_camera", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
     "mfx_film_mean", "mfx_stats",
     "mfx_trace_accumulate", "mfx_accum_clear", "mfx_accum_reduce", "mfx_accum_device_ptr", "mfx_accum_attach", "mfx_accum_read_mean",
     "mfx_sync", "mfx_stream", "mfx_ray_counts", "mfx_last_trace_ms", "mfx_trace_timing", "mfx_ray_counts_total", "mfx_closest_hit", "mfx_any_hit", "mfx_ref_leaves",
@@ -276,6 +289,39 @@ def dptr(a: np.ndarray):
 
 def iptr(a: np.ndarray):
     return a.ctypes.data_as(_ip)
+
+
+def pinhole_struct(camera) -> MfxPinhole:
+    """An MfxPinhole from a camera dict: position, direction, fov, aspect as scene files give them (the
+    library runs the constructor), or position, topleft, right, down (derived: taken as they are). An
+    MfxPinhole passes through."""
+    if isinstance(camera, MfxPinhole):
+        return camera
+    p = MfxPinhole()
+    derived = "topleft" in camera
+    for c in range(3):
+        p.position[c] = float(camera["position"][c])
+        if derived:
+            p.topleft[c] = float(camera["topleft"][c])
+            p.right[c] = float(camera["right"][c])
+            p.down[c] = float(camera["down"][c])
+        else:
+            p.direction[c] = float(camera["direction"][c])
+    if not derived:
+        p.fov = float(camera["fov"])
+        p.aspect = float(camera["aspect"])
+    p.derived = 1 if derived else 0
+    return p
+
+
+def pinhole_derive(camera) -> dict:
+    """Host-only: the derived camera the library makes of `camera` (mfx_pinhole_derive): a dict of
+    position, topleft, right, down, each a (3,) float64 array."""
+    lib = load_library()
+    p = pinhole_struct(camera)
+    out = np.zeros(12)
+    check(lib.mfx_pinhole_derive(C.byref(p), dptr(out)), "mfx_pinhole_derive")
+    return {"position": out[0:3].copy(), "topleft": out[3:6].copy(), "right": out[6:9].copy(), "down": out[9:12].copy()}
 
 
 def build_leaves(arrays: SceneArrays):

@@ -135,25 +135,13 @@ static hipError_t process_stream(int device, int k, hipStream_t* out) {
     return hipSuccess;
 }
 
-// Device resources of a context whose host scene, device, seed, flags and partition are set:
-// stream, events, the scene images in HBM, accumulators, occupancy-derived launch shapes. On
-// failure the caller destroys the context, which releases whatever was allocated.
-static int ctx_setup(mfx_ctx* c) {
-    c->npix = (int64_t)c->host.width * c->host.height;
+#define CK(expr) HIP_TRY(expr, _e == hipErrorOutOfMemory ? MFX_E_NOMEM : MFX_E_DEVICE, #expr ": ")
+
+// The scene images of c->host in HBM, with the context's device current (ctx_setup at creation;
+// mfx_set_camera when the images are built again)
+static int scene_upload(mfx_ctx* c) {
     c->stack_size = std::max(1, c->host.stack_entries);
     if (c->stack_size > 96) return fail(MFX_E_INVALID, "mfx_create: BVH too deep for the LDS traversal stack");
-#define CK(expr) HIP_TRY(expr, _e == hipErrorOutOfMemory ? MFX_E_NOMEM : MFX_E_DEVICE, #expr ": ")
-    CK(hipSetDevice(c->device));
-    if (const int k = stream_pool_size()) {  // MFX_STREAM_POOL (see process_stream)
-        hipStream_t s = nullptr;
-        CK(process_stream(c->device, k, &s));
-        c->stream.borrow(s);
-    } else {
-        CK(c->stream.create());
-    }
-    CK(c->h_counters.alloc(WF_NCTR * WF_SHARDS));
-    CK(c->ev0.create());
-    CK(c->ev1.create());
     CK(upload(c->d_nodes, c->host.nodes));
     CK(upload(c->d_slots, c->host.slots));
     if (MFX_NODE_F16 && !getenv("MFX_NODE_F32")) {  // (MFX_NODE_F32=1: the F16 build on FP32 nodes)
@@ -168,45 +156,16 @@ static int ctx_setup(mfx_ctx* c) {
     CK(upload(c->d_light, std::vector<MfxLight>{c->host.light}));
     CK(upload(c->d_cam, std::vector<MfxCamera>{c->host.camera}));
     CK(upload(c->d_refs, std::vector<const void*>{c->d_slot_ref.get(), c->d_ref_blob.get()}));
+    if (!c->host.inst.empty()) CK(upload(c->d_inst, c->host.inst));
+    else c->d_inst.reset();
+    return MFX_OK;
+}
+
+// Occupancy-derived launch shapes of the scene in c->host (its stack bound, node and slot counts,
+// instances), and the buffers sized by them; with the context's device current
+static int scene_shapes(mfx_ctx* c) {
     const bool inst = !c->host.inst.empty();
     const int ninst = (int)c->host.inst.size();
-    if (inst) CK(upload(c->d_inst, c->host.inst));
-    const size_t npix = (size_t)c->npix, plane = sizeof(double) * npix;
-    CK(c->d_accum_own.alloc(3 * npix));
-    c->d_accum = c->d_accum_own;
-    CK(c->d_film.alloc(3 * npix));
-    CK(c->d_frame.alloc(4 * npix));
-    CK(c->d_rgba.alloc(4 * npix));
-    CK(c->d_work.alloc(8));
-    CK(c->d_counters.alloc(WF_NCTR * WF_SHARDS));
-    CK(c->d_counters_total.alloc(WF_NCTR * WF_SHARDS));
-    CK(hipMemset(c->d_counters_total, 0, kCounterBytes));
-    CK(c->pool.ctl.alloc(WF_CTL_ALLOC));
-    size_t mfree = 0, mtotal = 0;
-    if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree > 0)
-        c->pool.max = std::max<int64_t>(1 << 20, std::min<int64_t>(c->pool.max, (int64_t)(mfree / 4 / pool_slot_bytes(c))));
-    // (at most 2^28 slots: k_extend's pending entries keep a slot index in 28 bits)
-    c->pool.fail_once = getenv("MFX_POOL_FAIL_ONCE") && atoi(getenv("MFX_POOL_FAIL_ONCE")) != 0;
-    if (const char* pm = getenv("MFX_POOL")) c->pool.max = std::max<int64_t>(2048, std::min<int64_t>(1 << 28, atoll(pm)));
-    c->diag_iter = getenv("MFX_DIAG_ITER") != nullptr;
-    c->adp.check = getenv("MFX_ADAPTIVE_CHECK") && atoi(getenv("MFX_ADAPTIVE_CHECK")) != 0;
-    if (const char* e = getenv("MFX_ITER_EVENTS")) c->iter_events = atoi(e) != 0 || c->diag_iter;
-    if (const char* qf = getenv("MFX_QUEUE_FROM")) c->pool.queue_from = MFX_RAY_QUEUE ? std::max(-2, atoi(qf)) : -1;
-    if (const char* qc = getenv("MFX_QCHUNK")) c->pool.qchunk = std::max(64, std::min(WF_CHUNK_MAX, atoi(qc) / 64 * 64));
-    if (getenv("MFX_RAY_QUEUE") && atoi(getenv("MFX_RAY_QUEUE")) == 0) c->pool.queue_from = -1;
-    if (const char* ck = getenv("MFX_MEGA_CHUNK")) c->mega_chunk = std::max(1, atoi(ck));
-    // MFX_F_IN_FLIGHT: the caller alternates frames over several contexts of this device, so each
-    // launch's ramp-down runs beside another frame's launches: larger chunk fetches and whole ones
-    // for k_shadow (r05s, C2's 1/8 share over 3 contexts: 4.44 -> 4.37 ms, the 1/4 share 8.78 -> 8.63)
-    if (c->flags & MFX_F_IN_FLIGHT) {
-        c->wf_chunk = 512;
-        c->wf_shd_half = false;
-    }
-    if (const char* e = getenv("MFX_SHD_HALF")) c->wf_shd_half = atoi(e) != 0;
-    if (const char* ck = getenv("MFX_CHUNK")) c->wf_chunk = std::max(64, std::min(WF_CHUNK_MAX, atoi(ck) / 64 * 64));
-    CK(hipMemset(c->d_accum, 0, 3 * plane));
-    CK(hipMemset(c->d_film, 0, 3 * plane));
-    CK(hipMemset(c->d_counters, 0, kCounterBytes));
     hipDeviceProp_t prop;
     CK(hipGetDeviceProperties(&prop, c->device));
     int bpc = 0;
@@ -320,9 +279,65 @@ static int ctx_setup(mfx_ctx* c) {
         c->spill_lanes = (int)lanes;
     }
     CK(c->d_vscratch.alloc(6 * (size_t)(c->host.max_depth + 1) * c->grid * 256));
-#undef CK
     return MFX_OK;
 }
+
+// Device resources of a context whose host scene, device, seed, flags and partition are set:
+// stream, events, the scene images in HBM, accumulators, occupancy-derived launch shapes. On
+// failure the caller destroys the context, which releases whatever was allocated.
+static int ctx_setup(mfx_ctx* c) {
+    c->npix = (int64_t)c->host.width * c->host.height;
+    CK(hipSetDevice(c->device));
+    if (const int k = stream_pool_size()) {  // MFX_STREAM_POOL (see process_stream)
+        hipStream_t s = nullptr;
+        CK(process_stream(c->device, k, &s));
+        c->stream.borrow(s);
+    } else {
+        CK(c->stream.create());
+    }
+    CK(c->h_counters.alloc(WF_NCTR * WF_SHARDS));
+    CK(c->ev0.create());
+    CK(c->ev1.create());
+    MFX_TRY(scene_upload(c));
+    const size_t npix = (size_t)c->npix, plane = sizeof(double) * npix;
+    CK(c->d_accum_own.alloc(3 * npix));
+    c->d_accum = c->d_accum_own;
+    CK(c->d_film.alloc(3 * npix));
+    CK(c->d_frame.alloc(4 * npix));
+    CK(c->d_rgba.alloc(4 * npix));
+    CK(c->d_work.alloc(8));
+    CK(c->d_counters.alloc(WF_NCTR * WF_SHARDS));
+    CK(c->d_counters_total.alloc(WF_NCTR * WF_SHARDS));
+    CK(hipMemset(c->d_counters_total, 0, kCounterBytes));
+    CK(c->pool.ctl.alloc(WF_CTL_ALLOC));
+    size_t mfree = 0, mtotal = 0;
+    if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree > 0)
+        c->pool.max = std::max<int64_t>(1 << 20, std::min<int64_t>(c->pool.max, (int64_t)(mfree / 4 / pool_slot_bytes(c))));
+    // (at most 2^28 slots: k_extend's pending entries keep a slot index in 28 bits)
+    c->pool.fail_once = getenv("MFX_POOL_FAIL_ONCE") && atoi(getenv("MFX_POOL_FAIL_ONCE")) != 0;
+    if (const char* pm = getenv("MFX_POOL")) c->pool.max = std::max<int64_t>(2048, std::min<int64_t>(1 << 28, atoll(pm)));
+    c->diag_iter = getenv("MFX_DIAG_ITER") != nullptr;
+    c->adp.check = getenv("MFX_ADAPTIVE_CHECK") && atoi(getenv("MFX_ADAPTIVE_CHECK")) != 0;
+    if (const char* e = getenv("MFX_ITER_EVENTS")) c->iter_events = atoi(e) != 0 || c->diag_iter;
+    if (const char* qf = getenv("MFX_QUEUE_FROM")) c->pool.queue_from = MFX_RAY_QUEUE ? std::max(-2, atoi(qf)) : -1;
+    if (const char* qc = getenv("MFX_QCHUNK")) c->pool.qchunk = std::max(64, std::min(WF_CHUNK_MAX, atoi(qc) / 64 * 64));
+    if (getenv("MFX_RAY_QUEUE") && atoi(getenv("MFX_RAY_QUEUE")) == 0) c->pool.queue_from = -1;
+    if (const char* ck = getenv("MFX_MEGA_CHUNK")) c->mega_chunk = std::max(1, atoi(ck));
+    // MFX_F_IN_FLIGHT: the caller alternates frames over several contexts of this device, so each
+    // launch's ramp-down runs beside another frame's launches: larger chunk fetches and whole ones
+    // for k_shadow (r05s, C2's 1/8 share over 3 contexts: 4.44 -> 4.37 ms, the 1/4 share 8.78 -> 8.63)
+    if (c->flags & MFX_F_IN_FLIGHT) {
+        c->wf_chunk = 512;
+        c->wf_shd_half = false;
+    }
+    if (const char* e = getenv("MFX_SHD_HALF")) c->wf_shd_half = atoi(e) != 0;
+    if (const char* ck = getenv("MFX_CHUNK")) c->wf_chunk = std::max(64, std::min(WF_CHUNK_MAX, atoi(ck) / 64 * 64));
+    CK(hipMemset(c->d_accum, 0, 3 * plane));
+    CK(hipMemset(c->d_film, 0, 3 * plane));
+    CK(hipMemset(c->d_counters, 0, kCounterBytes));
+    return scene_shapes(c);
+}
+#undef CK
 
 // Two-level or flat for an instanced scene. The flat image (one BVH over the expansion) is the faster
 // search (C5: 5,088 vs 4,729 Mrays/s, r02bt) and exactly the same results, so it is taken whenever it
@@ -390,10 +405,22 @@ static int create_impl(const mfx_scene_desc* scene, const mfx_instance* instance
     std::string err;
     // the traversal BVH is built on the first device unless the caller asks for the host build
     // (the same tree either way: tests/test_gpu_build.py); the other devices get copies
-    if (!mfx_build_scene(scene, c->host, err, (opt->flags & MFX_F_HOST_BVH) == 0, instances, ninstances,
-                         flatten_instances(scene, instances, ninstances, opt->flags, dev_free))) {
+    const bool flatten = flatten_instances(scene, instances, ninstances, opt->flags, dev_free);
+    if (!mfx_build_scene(scene, c->host, err, (opt->flags & MFX_F_HOST_BVH) == 0, instances, ninstances, flatten)) {
         const bool dev = err.rfind("GPU BVH build", 0) == 0;
         return fail(dev ? MFX_E_DEVICE : MFX_E_INVALID, "mfx_create: " + err);
+    }
+    {  // the description stays with the context: mfx_set_camera may have to build the images again
+        KeptScene& k = c->kept;
+        k.prims.assign(scene->prims, scene->prims + scene->nprims);
+        k.albedo.assign(scene->albedo, scene->albedo + 3 * (size_t)scene->nmat);
+        if (instances) k.instances.assign(instances, instances + ninstances);
+        k.desc = *scene;
+        k.desc.prims = nullptr;
+        k.desc.albedo = nullptr;
+        k.instanced = instances != nullptr;
+        k.flatten = flatten;
+        k.gpu_bvh = (opt->flags & MFX_F_HOST_BVH) == 0;
     }
     // Image partition: device g of G traces the film's tile rows of band g of G, every sample of the
     // caller's partition, so every per-pixel operation (the sample-order sum, the film add, the post)
@@ -470,7 +497,160 @@ static void instancing_info(const MfxHostScene& h, double out[8]) {
                       h.inst.size() * sizeof(MfxInstance));
 }
 
+// ---- mfx_set_camera -------------------------------------------------------------------------------
+// What scene_upload and scene_shapes write: a device context's scene images and the launch shapes
+// derived from them. A rebuild parks the old ones here; taking them back undoes it.
+struct SceneState {
+    MfxHostScene host;
+    DevBuf<MfxNode> d_nodes;
+    DevBuf<MfxSlot> d_slots;
+    DevBuf<MfxNodeH> d_nodes_h;
+    DevBuf<int32_t> d_slot_ref;
+    DevBuf<uint8_t> d_ref_blob;
+    DevBuf<MfxShade> d_shade;
+    DevBuf<MfxInstance> d_inst;
+    DevBuf<double> d_albedo;
+    DevBuf<MfxLight> d_light;
+    DevBuf<MfxCamera> d_cam;
+    DevBuf<const void*> d_refs;
+    DevBuf<int32_t> d_spill;
+    DevBuf<double> d_vscratch;
+    WfParams params{};
+    int stack_size = 1, grid = 0, mega_waves = 1, wf_ext_grid = 0, wf_shd_grid = 0, wf_cam_grid = 0;
+    int spill_deep = 0, spill_lanes = 0;
+};
+static void swap_scene_state(mfx_ctx* c, SceneState& s) {
+    std::swap(c->host, s.host);
+    std::swap(c->d_nodes, s.d_nodes);
+    std::swap(c->d_slots, s.d_slots);
+    std::swap(c->d_nodes_h, s.d_nodes_h);
+    std::swap(c->d_slot_ref, s.d_slot_ref);
+    std::swap(c->d_ref_blob, s.d_ref_blob);
+    std::swap(c->d_shade, s.d_shade);
+    std::swap(c->d_inst, s.d_inst);
+    std::swap(c->d_albedo, s.d_albedo);
+    std::swap(c->d_light, s.d_light);
+    std::swap(c->d_cam, s.d_cam);
+    std::swap(c->d_refs, s.d_refs);
+    std::swap(c->d_spill, s.d_spill);
+    std::swap(c->d_vscratch, s.d_vscratch);
+    std::swap(c->pool.params, s.params);
+    std::swap(c->stack_size, s.stack_size);
+    std::swap(c->grid, s.grid);
+    std::swap(c->mega_waves, s.mega_waves);
+    std::swap(c->wf_ext_grid, s.wf_ext_grid);
+    std::swap(c->wf_shd_grid, s.wf_shd_grid);
+    std::swap(c->wf_cam_grid, s.wf_cam_grid);
+    std::swap(c->spill_deep, s.spill_deep);
+    std::swap(c->spill_lanes, s.spill_lanes);
+}
+
+// Prepare the kept scene again for `cam` and install it on every device of the context, by creation's
+// own steps (mfx_build_scene, scene_upload, scene_shapes). On failure every device has its old images back.
+static int rebuild_for_camera(mfx_ctx* c, const mfx_pinhole* cam) {
+    const KeptScene& k = c->kept;
+    mfx_scene_desc d = k.desc;
+    d.prims = k.prims.data();
+    d.albedo = k.albedo.data();
+    d.camera = *cam;
+    HIPCHECK(hipSetDevice(c->device));
+    MfxHostScene h;
+    std::string err;
+    if (!mfx_build_scene(&d, h, err, k.gpu_bvh, k.instanced ? k.instances.data() : nullptr, (int)k.instances.size(), k.flatten)) {
+        const bool dev = err.rfind("GPU BVH build", 0) == 0;
+        return fail(dev ? MFX_E_DEVICE : MFX_E_INVALID, "mfx_set_camera: " + err);
+    }
+    const std::vector<mfx_ctx*> ds = devs_of(c);
+    std::vector<SceneState> old(ds.size());
+    int rc = MFX_OK;
+    size_t done = 0;
+    for (; done < ds.size() && rc == MFX_OK; ++done) {
+        mfx_ctx* dv = ds[done];
+        SceneState& o = old[done];
+        o.params = dv->pool.params;  // the pool's arrays stay; the launch shapes are written over
+        swap_scene_state(dv, o);
+        dv->host = h;  // (the shapes start from a fresh context's defaults: SceneState's)
+        rc = hipSetDevice(dv->device) == hipSuccess ? MFX_OK : fail(MFX_E_DEVICE, "mfx_set_camera: hipSetDevice failed");
+        if (rc == MFX_OK) rc = scene_upload(dv);
+        if (rc == MFX_OK) rc = scene_shapes(dv);
+    }
+    if (rc != MFX_OK) {
+        const std::string msg = mfx_last_error();
+        (void)hipGetLastError();
+        for (size_t g = 0; g < done; ++g) swap_scene_state(ds[g], old[g]);  // the failed images go with `old`
+        (void)hipSetDevice(c->device);
+        return fail(rc, msg);
+    }
+    HIPCHECK(hipSetDevice(c->device));
+    c->kept.desc.camera = *cam;
+    return MFX_OK;
+}
+
 extern "C" {
+int mfx_pinhole_derive(const mfx_pinhole* cam, double out[12]) {
+    if (!cam || !out) return fail(MFX_E_INVALID, "mfx_pinhole_derive: null argument");
+    MfxCamera m;
+    mfx_derive_camera(*cam, m);
+    std::memcpy(out, &m, sizeof(m));
+    return MFX_OK;
+}
+
+int mfx_camera_info(mfx_ctx* c, double out[16]) {
+    if (!c || !out) return fail(MFX_E_INVALID, "mfx_camera_info: null argument");
+    static_assert(sizeof(MfxCamera) == 12 * sizeof(double), "MfxCamera is position, topleft, right, down");
+    std::memcpy(out, &c->host.camera, sizeof(MfxCamera));
+    float eps = 0.f, eps_t = 0.f;
+    mfx_camera_eps(c->host, c->host.camera.position, &eps, &eps_t);
+    out[12] = (double)c->cam_epoch;
+    out[13] = (double)c->host.eps;
+    out[14] = (double)eps;
+    out[15] = (double)c->cam_rebuilds;
+    return MFX_OK;
+}
+
+int mfx_set_camera(mfx_ctx* c, const mfx_pinhole* cam) {
+    if (!c || !cam) return fail(MFX_E_INVALID, "mfx_set_camera: null argument");
+    bool finite = true, zero_dir = true;
+    for (int a = 0; a < 3; ++a) {
+        finite = finite && std::isfinite(cam->position[a]);
+        if (cam->derived) finite = finite && std::isfinite(cam->topleft[a]) && std::isfinite(cam->right[a]) && std::isfinite(cam->down[a]);
+        else finite = finite && std::isfinite(cam->direction[a]);
+        zero_dir = zero_dir && cam->direction[a] == 0.0;
+    }
+    if (!cam->derived) finite = finite && std::isfinite(cam->fov) && std::isfinite(cam->aspect);
+    if (!finite) return fail(MFX_E_INVALID, "mfx_set_camera: a camera field is not finite");
+    if (!cam->derived && zero_dir) return fail(MFX_E_INVALID, "mfx_set_camera: direction is zero");
+    MfxCamera m;
+    mfx_derive_camera(*cam, m);
+    for (const double* v : {m.position, m.topleft, m.right, m.down})
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(v[a])) return fail(MFX_E_INVALID, "mfx_set_camera: the derived camera is not finite");
+    if (std::memcmp(&m, &c->host.camera, sizeof(m)) == 0) return MFX_OK;  // the current camera: nothing to do
+    // held render-ahead frames are the old camera's: the film comes back to d_film under the old camera, and
+    // the frames' epoch ends; then everything the context has enqueued, a background batch included, finishes
+    MFX_TRY(ahead_break(c));
+    MFX_TRY(mfx_sync(c));
+    float eps = 0.f, eps_t = 0.f;
+    mfx_camera_eps(c->host, m.position, &eps, &eps_t);
+    if (eps <= c->host.eps && eps_t <= c->host.eps_templates) {
+        // in place: the boxes stay conservative for every ray this camera can start
+        for (mfx_ctx* d : devs_of(c)) {
+            HIPCHECK(hipSetDevice(d->device));
+            HIPCHECK(hipMemcpy(d->d_cam, &m, sizeof(m), hipMemcpyHostToDevice));
+            d->host.camera = m;
+        }
+        HIPCHECK(hipSetDevice(c->device));
+        c->kept.desc.camera = *cam;
+    } else {
+        MFX_TRY(rebuild_for_camera(c, cam));
+        c->cam_rebuilds += 1;
+    }
+    c->cam_epoch += 1;
+    c->adp.accum_valid = false;  // a resume must not mix cameras
+    c->ahead.dfilm_buf = -1;
+    return MFX_OK;
+}
+
 const char* mfx_last_error(void) { return g_err.c_str(); }
 int mfx_abi_version(void) { return MFX_ABI_VERSION; }
 

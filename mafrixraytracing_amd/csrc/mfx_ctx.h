@@ -260,7 +260,34 @@ struct Denoise {
     DevBuf<double> buf[2];        // [3][npix] each: the filter's ping-pong colour buffers
     DevBuf<double> var[2];        // [npix] each: mfx_denoise_var's ping-pong variance planes
     Event ev0, ev1;               // around either call's kernels
+    uint64_t feat_epoch = 0;      // the camera epoch (mfx_ctx::cam_epoch) the feature planes were traced in
     bool ready() const { return feat != nullptr; }  // mfx_aov has run
+};
+
+// Temporal reuse (mfx_temporal); allocated at its first call. A history buffer holds the merged result
+// and the features of the view it belongs to, plane-major, x-major pixels (MFX_TP_* in mfx_denoise.h):
+// the kernel gathers from hist[cur] and writes hist[cur ^ 1], then cur flips (no copy).
+struct Temporal {
+    DevBuf<double> hist[2];             // [MFX_TP_PLANES][npix] each
+    DevBuf<double> count_in;            // [npix] staging of MFX_DN_SRC_HOST's counts
+    DevBuf<unsigned long long> accepted;  // [1] pixels that took history
+    int cur = -1;                       // the buffer that holds the history (-1: none yet)
+    MfxCamera cam{};                    // the camera of the history's view
+    uint64_t epoch = 0;                 // and its camera epoch
+    bool ready() const { return accepted != nullptr; }  // the last one mfx_temporal allocates
+};
+
+// The scene description a context keeps from creation on (host memory only: 104 B per primitive, 24 B
+// per material, 48 B per instance entry): what mfx_set_camera builds the images from again when the new
+// camera needs wider boxes. Primary context only.
+struct KeptScene {
+    std::vector<mfx_prim> prims;
+    std::vector<double> albedo;
+    std::vector<mfx_instance> instances;
+    mfx_scene_desc desc{};   // prims / albedo point nowhere: set from the vectors at use
+    bool instanced = false;  // created by mfx_create_instanced
+    bool flatten = false;    // the choice creation made for an instanced scene
+    bool gpu_bvh = false;
 };
 
 // Readback to the caller's host memory (mfx_readback.cpp); each allocated by the first call that needs it
@@ -323,6 +350,9 @@ struct __attribute__((visibility("hidden"))) mfx_ctx {
     int band_index = 0, band_count = 1;
     int64_t next_sample = 0;
     double frame_count = 0.0;
+    uint64_t cam_epoch = 0;    // 0 after create, +1 per mfx_set_camera that changed the camera (primary)
+    int64_t cam_rebuilds = 0;  // of which had to build the images again
+    mfxh::KeptScene kept;      // (primary)
     int grid = 0;
     int stack_size = 1;
     int64_t npix = 0;
@@ -360,6 +390,7 @@ struct __attribute__((visibility("hidden"))) mfx_ctx {
     mfxh::Ahead ahead;
     mfxh::Adaptive adp;
     mfxh::Denoise dn;
+    mfxh::Temporal tp;
     mfxh::Readback rb;
     mfxh::Multi multi;
 

@@ -57,7 +57,36 @@ struct AtrousVarParams {
     double luma_floor;
 };
 
+// A temporal history buffer's planes ([MFX_TP_PLANES][w*h], x-major pixels): the merged colour, the
+// variance of its mean luminance, its effective sample count, and the features of the view it was
+// merged in (normal, depth, hit fraction). Colour first, so the three planes are an a-trous source.
+#define MFX_TP_COLOR 0
+#define MFX_TP_VAR 3
+#define MFX_TP_COUNT 4
+#define MFX_TP_NORMAL 5
+#define MFX_TP_DEPTH 8
+#define MFX_TP_HIT 9
+#define MFX_TP_PLANES 10
+
+// k_temporal: reproject the history into the current view and merge (mfx_temporal; the rule: include/mafrix_rt.h)
+struct TemporalParams {
+    const double* color;      // [3][w*h] this frame's colour
+    const double* var;        // [w*h] the variance of its mean luminance
+    const double* count;      // [w*h] its sample counts, or null: tile_spp
+    const int32_t* tile_spp;  // [tiles] the adaptive sampler's counts (count == null)
+    const double* feat;       // [MFX_AOV_PLANES][w*h] the current view's features
+    const double* hist;       // [MFX_TP_PLANES][w*h] the history, or null: none (every pixel passes through)
+    double* hist_out;         // [MFX_TP_PLANES][w*h] the history after the call
+    unsigned long long* accepted;  // [1] += pixels that took history
+    MfxCamera cam, hcam;      // the current view's and the history's, by value: scalar-loaded
+    int32_t width, height;
+    double tol_depth2;        // tol_depth * tol_depth
+    double tol_normal2;
+    double max_history;
+};
+
 hipError_t mfx_launch_aov(const AovParams& P, hipStream_t st);
+hipError_t mfx_launch_temporal(const TemporalParams& P, hipStream_t st);
 hipError_t mfx_launch_atrous(const AtrousParams& P, hipStream_t st);
 hipError_t mfx_launch_atrous_var(const AtrousVarParams& P, hipStream_t st);
 // colour planes <- accum / n, variance plane <- max(0, S2 - S1*S1/n) / (n (n - 1)), n = tile_spp[the pixel's tile]

@@ -1,7 +1,8 @@
 // mfx_denoise.hip — gfx950 kernels of mfx_aov (first-hit feature buffers of the film's own camera
 // rays), mfx_denoise (the edge-avoiding a-trous filter they guide) and mfx_denoise_var (that filter
-// with a variance-guided luminance term, fed by the adaptive sampler's moments). The rule of each is
-// stated in include/mafrix_rt.h and, in numpy, in mafrixraytracing_amd/denoise.py.
+// with a variance-guided luminance term, fed by the adaptive sampler's moments) and mfx_temporal (the
+// previous result reprojected into the current view and merged by sample counts). The rule of each is
+// stated in include/mafrix_rt.h and, in numpy, in mafrixraytracing_amd/denoise.py and temporal.py.
 //
 // Compiled with -ffp-contract=off like the rest of the library: every FP64 expression below has one
 // rounding per operation in the order written, so the device gives the host statement's bits. The
@@ -243,6 +244,93 @@ __global__ void __launch_bounds__(256) k_atrous_var(AtrousVarParams P) {
     P.vdst[p] = vn / (den * den);
 }
 
+// ----------------------------------------------------------------------------------------------
+// k_temporal: one thread per pixel, x-major planes as k_atrous (mfx_temporal; the rule, step by step:
+// include/mafrix_rt.h). The pixel's world point from the current view's depth is projected into the
+// history's view; the nearest history pixel is taken if it shows the same surface (hit fraction 1 on
+// both sides, depth and normal within the tolerances) and merged by sample counts. Both cameras come
+// in the kernel arguments (scalar loads); a wave reads its own pixels' planes as coalesced runs of 64
+// doubles and gathers the history nearly so: neighbours reproject to neighbours. The history's view
+// features are written beside the merged result, so the two history buffers swap by pointer. A wave
+// counts its accepted pixels by ballot and adds them with one vector atomic. No lane leaves before the
+// ballot: a lane past the film only loads and stores nothing.
+// ----------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_temporal(TemporalParams P) {
+    const int W = P.width, H = P.height;
+    const int64_t npix = (int64_t)W * H;
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool inside = p < npix;
+    bool accept = false;
+    if (inside) {
+        const int x = (int)(p / H), y = (int)(p - (int64_t)x * H);
+        const double* __restrict__ F = P.feat;
+        const double* __restrict__ HB = P.hist;
+        const double c0 = P.color[p], c1 = P.color[npix + p], c2 = P.color[2 * npix + p];
+        const double vp = P.var[p];
+        const double n = P.count ? P.count[p] : (double)P.tile_spp[(y >> 3) * ((W + 7) >> 3) + (x >> 3)];
+        const double np0 = F[p], np1 = F[npix + p], np2 = F[2 * npix + p];
+        const double zp = F[3 * npix + p], fp = F[7 * npix + p];
+        double o0 = c0, o1 = c1, o2 = c2, ov = vp, on = n;
+        if (HB && fp == 1.0) {
+            // the pixel centre's camera ray (k_aov's operations) and its world point at the view's depth
+            const double u = ((double)x + 0.5) / (double)W;
+            const double v = ((double)y + 0.5) / (double)H;
+            const DV o = ld3(P.cam.position);
+            const DV target = vadd(vadd(ld3(P.cam.topleft), vmul(ld3(P.cam.right), u)), vmul(ld3(P.cam.down), v));
+            const DV dir = vnormalize(vsub(target, o));
+            const DV wp = vadd(o, vmul(dir, zp));
+            // into the history's view: the ray from its eye through the point meets its image plane at a + g
+            const DV ho = ld3(P.hcam.position), hr = ld3(P.hcam.right), hd = ld3(P.hcam.down);
+            const DV e = vsub(wp, ho);
+            const DV a = vsub(ld3(P.hcam.topleft), ho);
+            const DV nn = vcross(hr, hd);
+            const double den = vdot(e, nn), num = vdot(a, nn);
+            if (num * den > 0.0) {
+                const double s = num / den;
+                const DV g = vsub(vmul(e, s), a);
+                const double hu = vdot(g, hr) / vdot(hr, hr);
+                const double hv = vdot(g, hd) / vdot(hd, hd);
+                if (hu >= 0.0 && hu < 1.0 && hv >= 0.0 && hv < 1.0) {
+                    const int hx = min(W - 1, (int)floor(hu * (double)W));
+                    const int hy = min(H - 1, (int)floor(hv * (double)H));
+                    const int64_t q = (int64_t)hx * H + hy;  // inside the film: 0 <= q < npix
+                    if (HB[MFX_TP_HIT * npix + q] == 1.0) {
+                        const double ze = sqrt(vdot(e, e));
+                        const double dz = ze - HB[MFX_TP_DEPTH * npix + q];
+                        const double nd = d2(np0, np1, np2, HB[MFX_TP_NORMAL * npix + q], HB[(MFX_TP_NORMAL + 1) * npix + q],
+                                             HB[(MFX_TP_NORMAL + 2) * npix + q]);
+                        if (dz * dz <= P.tol_depth2 * (ze * ze) && nd <= P.tol_normal2) {
+                            accept = true;
+                            const double hn = HB[MFX_TP_COUNT * npix + q];
+                            const double nh = hn < P.max_history ? hn : P.max_history;
+                            const double nt = n + nh;
+                            const double wc = n / nt, wh = nh / nt;
+                            o0 = wc * c0 + wh * HB[q];
+                            o1 = wc * c1 + wh * HB[npix + q];
+                            o2 = wc * c2 + wh * HB[2 * npix + q];
+                            ov = (wc * wc) * vp + (wh * wh) * HB[MFX_TP_VAR * npix + q];
+                            on = nt;
+                        }
+                    }
+                }
+            }
+        }
+        double* __restrict__ O = P.hist_out;
+        O[p] = o0;
+        O[npix + p] = o1;
+        O[2 * npix + p] = o2;
+        O[MFX_TP_VAR * npix + p] = ov;
+        O[MFX_TP_COUNT * npix + p] = on;
+        O[MFX_TP_NORMAL * npix + p] = np0;
+        O[(MFX_TP_NORMAL + 1) * npix + p] = np1;
+        O[(MFX_TP_NORMAL + 2) * npix + p] = np2;
+        O[MFX_TP_DEPTH * npix + p] = zp;
+        O[MFX_TP_HIT * npix + p] = fp;
+    }
+    const unsigned long long took = __ballot(accept);
+    if ((threadIdx.x & 63) == 0 && took) atomicAdd(P.accepted, (unsigned long long)__popcll(took));
+}
+
 // colour planes <- accum / n and variance plane <- the tile check's v_p, n the pixel's own tile's count
 // (adaptive_mean_kernel's and k_tile_check's statements)
 __global__ void k_dn_from_adaptive(const double* __restrict__ accum, const double* __restrict__ mom,
@@ -309,6 +397,11 @@ hipError_t mfx_launch_aov(const AovParams& P, hipStream_t st) {
     const dim3 g(dn_grid((int64_t)P.width * P.height, 256));
     if (P.inst) hipLaunchKernelGGL(k_aov<true>, g, dim3(256), lds, st, P);
     else hipLaunchKernelGGL(k_aov<false>, g, dim3(256), lds, st, P);
+    return hipGetLastError();
+}
+
+hipError_t mfx_launch_temporal(const TemporalParams& P, hipStream_t st) {
+    hipLaunchKernelGGL(k_temporal, dim3(dn_grid((int64_t)P.width * P.height, 256)), dim3(256), 0, st, P);
     return hipGetLastError();
 }
 

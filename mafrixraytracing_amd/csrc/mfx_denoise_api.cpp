@@ -1,4 +1,5 @@
-// mfx_denoise_api.cpp — feature buffers and denoising.
+// mfx_denoise_api.cpp — feature buffers, denoising and temporal reuse (mfx_temporal: k_temporal merges the
+// reprojected history with the frame between two history buffers the context owns).
 // mfx_aov traces the film's own camera rays once more, per lane (k_aov), into eight FP64 planes that
 // stay on the device; mfx_denoise runs one k_atrous launch per iteration between two colour buffers,
 // guided by those planes (the rule: include/mafrix_rt.h); mfx_denoise_var runs k_atrous_var the same way
@@ -38,6 +39,13 @@ static int dn_alloc(DevBuf<double>& p, size_t doubles, const char* who) {
 // would be 0/0 and every pixel NaN
 static bool zero_square(double s) { return s > 0.0 && s * s == 0.0; }
 
+// the feature planes belong to the current camera (mfx_set_camera leaves them as they are: stale)
+static int features_current(const mfx_ctx* c, const char* who) {
+    if (c->dn.feat_epoch != c->cam_epoch)
+        return fail(MFX_E_STATE, std::string(who) + ": the feature buffers are another camera's (run mfx_aov again after mfx_set_camera)");
+    return MFX_OK;
+}
+
 extern "C" int mfx_aov(mfx_ctx* c, int32_t spp, int64_t sample_base, double* out, double* ms) {
     if (!c) return fail(MFX_E_INVALID, "mfx_aov: null context");
     if (spp < 1) return fail(MFX_E_INVALID, "mfx_aov: spp must be >= 1");
@@ -63,6 +71,7 @@ extern "C" int mfx_aov(mfx_ctx* c, int32_t spp, int64_t sample_base, double* out
     HIPCHECK(hipEventRecord(dn.ev0, c->stream));
     HIPCHECK(mfx_launch_aov(P, c->stream));
     HIPCHECK(hipEventRecord(dn.ev1, c->stream));
+    dn.feat_epoch = c->cam_epoch;
     if (out) MFX_TRY(host_readback(c, out, dn.feat_out, sizeof(double) * MFX_AOV_PLANES * (size_t)c->npix, c->stream));
     return dn_finish(c, ms);
 }
@@ -93,6 +102,7 @@ extern "C" int mfx_denoise(mfx_ctx* c, const mfx_denoise_cfg* a, const double* c
     MFX_TRY(whole_film_single_device(c, "mfx_denoise"));
     Denoise& dn = c->dn;
     if (!dn.ready()) return fail(MFX_E_STATE, "mfx_denoise: no feature buffers (call mfx_aov on this context first)");
+    MFX_TRY(features_current(c, "mfx_denoise"));
     HIPCHECK(hipSetDevice(c->device));
     for (int k = 0; k < 2; ++k) MFX_TRY(dn_alloc(dn.buf[k], 3 * (size_t)c->npix, "mfx_denoise"));
     MFX_TRY(dn_events(c));
@@ -138,7 +148,7 @@ extern "C" int mfx_denoise_var(mfx_ctx* c, const mfx_denoise_var_cfg* a, const d
     if (!c || !a) return fail(MFX_E_INVALID, "mfx_denoise_var: null argument");
     if (a->iterations < 1 || a->iterations > 8 || a->reserved[0] != 0 || a->reserved[1] != 0)
         return fail(MFX_E_INVALID, "mfx_denoise_var: need 1 <= iterations <= 8 and reserved 0");
-    if (a->source != MFX_DN_SRC_HOST && a->source != MFX_DN_SRC_ADAPTIVE)
+    if (a->source != MFX_DN_SRC_HOST && a->source != MFX_DN_SRC_ADAPTIVE && a->source != MFX_DN_SRC_TEMPORAL)
         return fail(MFX_E_INVALID, "mfx_denoise_var: unknown source");
     for (double s : {a->sigma_normal, a->sigma_depth, a->sigma_albedo, a->sigma_luma})
         if (!(s >= 0.0) || !std::isfinite(s)) return fail(MFX_E_INVALID, "mfx_denoise_var: every sigma must be finite and >= 0");
@@ -149,12 +159,17 @@ extern "C" int mfx_denoise_var(mfx_ctx* c, const mfx_denoise_var_cfg* a, const d
     const bool host = a->source == MFX_DN_SRC_HOST;
     if (host && (!color_in || !variance_in))
         return fail(MFX_E_INVALID, "mfx_denoise_var: MFX_DN_SRC_HOST needs color_in and variance_in");
+    const bool temporal = a->source == MFX_DN_SRC_TEMPORAL;
     if (!host && (color_in || variance_in))
-        return fail(MFX_E_INVALID, "mfx_denoise_var: MFX_DN_SRC_ADAPTIVE takes no color_in or variance_in");
+        return fail(MFX_E_INVALID, "mfx_denoise_var: MFX_DN_SRC_ADAPTIVE and MFX_DN_SRC_TEMPORAL take no color_in or variance_in");
     MFX_TRY(whole_film_single_device(c, "mfx_denoise_var"));
     Denoise& dn = c->dn;
     if (!dn.ready()) return fail(MFX_E_STATE, "mfx_denoise_var: no feature buffers (call mfx_aov on this context first)");
-    if (!host && !c->adp.accum_valid)
+    MFX_TRY(features_current(c, "mfx_denoise_var"));
+    if (temporal && c->tp.cur < 0) return fail(MFX_E_STATE, "mfx_denoise_var: no temporal history (call mfx_temporal first)");
+    if (temporal && c->tp.epoch != dn.feat_epoch)
+        return fail(MFX_E_STATE, "mfx_denoise_var: the temporal history is another camera's than the feature buffers (call mfx_temporal again)");
+    if (!host && !temporal && !c->adp.accum_valid)
         return fail(MFX_E_STATE, "mfx_denoise_var: the accumulator does not hold an mfx_sample_adaptive result");
     HIPCHECK(hipSetDevice(c->device));
     for (int k = 0; k < 2; ++k) {
@@ -169,7 +184,7 @@ extern "C" int mfx_denoise_var(mfx_ctx* c, const mfx_denoise_var_cfg* a, const d
     }
     HIPCHECK(hipEventRecord(dn.ev0, c->stream));
     if (host) HIPCHECK(mfx_launch_dn_from_frame(c->d_frame, c->npix, dn.buf[0], c->stream));
-    else HIPCHECK(mfx_launch_dn_from_adaptive(c->d_accum, c->adp.mom, c->adp.tile_spp, W, H, dn.buf[0], dn.var[0], c->stream));
+    else if (!temporal) HIPCHECK(mfx_launch_dn_from_adaptive(c->d_accum, c->adp.mom, c->adp.tile_spp, W, H, dn.buf[0], dn.var[0], c->stream));
     AtrousVarParams P;
     std::memset(&P, 0, sizeof(P));
     P.feat = dn.feat;
@@ -182,15 +197,19 @@ extern "C" int mfx_denoise_var(mfx_ctx* c, const mfx_denoise_var_cfg* a, const d
     P.sa2 = a->sigma_albedo * a->sigma_albedo;
     P.sl2 = a->sigma_luma * a->sigma_luma;
     P.luma_floor = a->luma_floor;
-    int cur = 0;
+    // the first iteration reads the source where it lies: buffer 0, or the temporal history's colour and variance planes
+    const double* hist = temporal ? c->tp.hist[c->tp.cur].get() : nullptr;
+    P.src = temporal ? hist + MFX_TP_COLOR * (size_t)c->npix : dn.buf[0].get();
+    P.vsrc = temporal ? hist + MFX_TP_VAR * (size_t)c->npix : dn.var[0].get();
+    int cur = temporal ? 1 : 0;  // the buffer an iteration leaves its output in is cur ^ 1
     for (int i = 0; i < a->iterations; ++i) {
-        P.src = dn.buf[cur];
-        P.vsrc = dn.var[cur];
         P.dst = dn.buf[cur ^ 1];
         P.vdst = dn.var[cur ^ 1];
         P.step = 1 << i;
         HIPCHECK(mfx_launch_atrous_var(P, c->stream));
         cur ^= 1;
+        P.src = dn.buf[cur];
+        P.vsrc = dn.var[cur];
     }
     if (out || rgba)
         HIPCHECK(mfx_launch_dn_post(dn.buf[cur], W, H, out ? c->d_frame.get() : nullptr, rgba ? c->d_rgba.get() : nullptr,
@@ -200,4 +219,91 @@ extern "C" int mfx_denoise_var(mfx_ctx* c, const mfx_denoise_var_cfg* a, const d
     if (var_out) MFX_TRY(host_readback(c, var_out, dn.var[cur], sizeof(double) * (size_t)c->npix, c->stream));  // x-major as it lies
     if (rgba) MFX_TRY(host_readback(c, rgba, c->d_rgba, 4 * (size_t)c->npix, c->stream));
     return dn_finish(c, ms);
+}
+
+extern "C" int mfx_temporal(mfx_ctx* c, const mfx_temporal_cfg* a, const double* color_in, const double* variance_in,
+                            const double* count_in, double* out, double* var_out, double* count_out, uint8_t* rgba,
+                            int64_t* accepted, double* ms) {
+    if (!c || !a) return fail(MFX_E_INVALID, "mfx_temporal: null argument");
+    if (a->reserved[0] != 0 || a->reserved[1] != 0) return fail(MFX_E_INVALID, "mfx_temporal: reserved must be 0");
+    if (a->source != MFX_DN_SRC_HOST && a->source != MFX_DN_SRC_ADAPTIVE)
+        return fail(MFX_E_INVALID, "mfx_temporal: unknown source");
+    if (!(a->tol_depth >= 0.0) || !std::isfinite(a->tol_depth) || !(a->tol_normal2 >= 0.0) || !std::isfinite(a->tol_normal2))
+        return fail(MFX_E_INVALID, "mfx_temporal: tol_depth and tol_normal2 must be finite and >= 0");
+    if (!(a->max_history > 0.0) || !std::isfinite(a->max_history))
+        return fail(MFX_E_INVALID, "mfx_temporal: max_history must be finite and > 0");
+    const bool host = a->source == MFX_DN_SRC_HOST;
+    if (host && (!color_in || !variance_in || !count_in))
+        return fail(MFX_E_INVALID, "mfx_temporal: MFX_DN_SRC_HOST needs color_in, variance_in and count_in");
+    if (!host && (color_in || variance_in || count_in))
+        return fail(MFX_E_INVALID, "mfx_temporal: MFX_DN_SRC_ADAPTIVE takes no color_in, variance_in or count_in");
+    if (host)
+        for (int64_t q = 0; q < c->npix; ++q)
+            if (!std::isfinite(count_in[q])) return fail(MFX_E_INVALID, "mfx_temporal: count_in must be finite");
+    MFX_TRY(whole_film_single_device(c, "mfx_temporal"));
+    Denoise& dn = c->dn;
+    Temporal& tp = c->tp;
+    if (!dn.ready()) return fail(MFX_E_STATE, "mfx_temporal: no feature buffers (call mfx_aov on this context first)");
+    MFX_TRY(features_current(c, "mfx_temporal"));
+    if (!host && !c->adp.accum_valid)
+        return fail(MFX_E_STATE, "mfx_temporal: the accumulator does not hold an mfx_sample_adaptive result");
+    HIPCHECK(hipSetDevice(c->device));
+    const size_t npix = (size_t)c->npix;
+    MFX_TRY(dn_alloc(dn.buf[0], 3 * npix, "mfx_temporal"));
+    MFX_TRY(dn_alloc(dn.var[0], npix, "mfx_temporal"));
+    for (int k = 0; k < 2; ++k) MFX_TRY(dn_alloc(tp.hist[k], (size_t)MFX_TP_PLANES * npix, "mfx_temporal"));
+    MFX_TRY(dn_alloc(tp.count_in, npix, "mfx_temporal"));
+    if (!tp.accepted && tp.accepted.alloc(1) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MFX_E_NOMEM, "mfx_temporal: its device buffers could not be allocated");
+    }
+    MFX_TRY(dn_events(c));
+    const int W = c->host.width, H = c->host.height;
+    if (host) {  // staged before the timed part, as mfx_denoise_var's
+        HIPCHECK(hipMemcpyAsync(c->d_frame, color_in, 4 * sizeof(double) * npix, hipMemcpyHostToDevice, c->stream));
+        HIPCHECK(hipMemcpyAsync(dn.var[0], variance_in, sizeof(double) * npix, hipMemcpyHostToDevice, c->stream));
+        HIPCHECK(hipMemcpyAsync(tp.count_in, count_in, sizeof(double) * npix, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHECK(hipMemsetAsync(tp.accepted, 0, sizeof(unsigned long long), c->stream));
+    HIPCHECK(hipEventRecord(dn.ev0, c->stream));
+    if (host) HIPCHECK(mfx_launch_dn_from_frame(c->d_frame, c->npix, dn.buf[0], c->stream));
+    else HIPCHECK(mfx_launch_dn_from_adaptive(c->d_accum, c->adp.mom, c->adp.tile_spp, W, H, dn.buf[0], dn.var[0], c->stream));
+    const bool have = tp.cur >= 0 && a->restart == 0;
+    const int dst = tp.cur >= 0 ? tp.cur ^ 1 : 0;
+    TemporalParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.color = dn.buf[0];
+    P.var = dn.var[0];
+    P.count = host ? tp.count_in.get() : nullptr;
+    P.tile_spp = host ? nullptr : c->adp.tile_spp.get();
+    P.feat = dn.feat;
+    P.hist = have ? tp.hist[tp.cur].get() : nullptr;
+    P.hist_out = tp.hist[dst];
+    P.accepted = tp.accepted;
+    P.cam = c->host.camera;
+    P.hcam = have ? tp.cam : c->host.camera;
+    P.width = W;
+    P.height = H;
+    P.tol_depth2 = a->tol_depth * a->tol_depth;
+    P.tol_normal2 = a->tol_normal2;
+    P.max_history = a->max_history;
+    HIPCHECK(mfx_launch_temporal(P, c->stream));
+    // the history is now the merged result in the current view (the buffers swap by index: no copy)
+    tp.cur = dst;
+    tp.cam = c->host.camera;
+    tp.epoch = c->cam_epoch;
+    const double* hist = tp.hist[dst];
+    if (out || rgba)
+        HIPCHECK(mfx_launch_dn_post(hist + MFX_TP_COLOR * npix, W, H, out ? c->d_frame.get() : nullptr,
+                                    rgba ? c->d_rgba.get() : nullptr, c->stream));
+    HIPCHECK(hipEventRecord(dn.ev1, c->stream));
+    if (out) MFX_TRY(host_readback(c, out, c->d_frame, 4 * sizeof(double) * npix, c->stream));
+    if (var_out) MFX_TRY(host_readback(c, var_out, hist + MFX_TP_VAR * npix, sizeof(double) * npix, c->stream));
+    if (count_out) MFX_TRY(host_readback(c, count_out, hist + MFX_TP_COUNT * npix, sizeof(double) * npix, c->stream));
+    if (rgba) MFX_TRY(host_readback(c, rgba, c->d_rgba, 4 * npix, c->stream));
+    unsigned long long took = 0;
+    if (accepted) HIPCHECK(hipMemcpyAsync(&took, tp.accepted, sizeof(took), hipMemcpyDeviceToHost, c->stream));
+    MFX_TRY(dn_finish(c, ms));
+    if (accepted) *accepted = (int64_t)took;
+    return MFX_OK;
 }

@@ -269,9 +269,11 @@ int32_t slot_info(const PrimRecords& r, const RefGrouping& g, int p, int j, int3
            (j == 1 ? MFX_INFO_RECT2 : 0);
 }
 
-// ---- camera (Camera.fs:96-133) and light (Light.fs:31-40) --------------------------------------
-void set_camera_light(const mfx_scene_desc& d, MfxHostScene& s) {
-    const mfx_pinhole& c = d.camera;
+}  // namespace
+
+// ---- camera (Camera.fs:96-133): the one copy of the constructor (mfx_create, mfx_set_camera,
+//      mfx_pinhole_derive) ---------------------------------------------------------------------------
+void mfx_derive_camera(const mfx_pinhole& c, MfxCamera& cam) {
     D3 fwd = normalize(d3(c.direction));
     D3 up0 = normalize(D3{0, 1, 0});
     D3 hori0 = cross(fwd, normalize(up0));
@@ -281,15 +283,22 @@ void set_camera_light(const mfx_scene_desc& d, MfxHostScene& s) {
     D3 up = scale(vert0, vert), right = scale(hori0, hori);
     D3 pos = d3(c.position);
     D3 tl = add(sub(add(pos, scale(fwd, 0.5)), scale(right, 0.5)), scale(up, 0.5));
-    put(s.camera.position, pos);
-    put(s.camera.topleft, tl);
-    put(s.camera.right, right);
-    put(s.camera.down, D3{-up.x, -up.y, -up.z});
+    put(cam.position, pos);
+    put(cam.topleft, tl);
+    put(cam.right, right);
+    put(cam.down, D3{-up.x, -up.y, -up.z});
     if (c.derived) {  // an existing PinholeCamera's fields, taken as they are
-        put(s.camera.topleft, d3(c.topleft));
-        put(s.camera.right, d3(c.right));
-        put(s.camera.down, d3(c.down));
+        put(cam.topleft, d3(c.topleft));
+        put(cam.right, d3(c.right));
+        put(cam.down, d3(c.down));
     }
+}
+
+namespace {
+
+// ---- camera and light (Light.fs:31-40) ----------------------------------------------------------
+void set_camera_light(const mfx_scene_desc& d, MfxHostScene& s) {
+    mfx_derive_camera(d.camera, s.camera);
 
     const mfx_quad_light& L = d.light;
     D3 q[4] = {d3(L.p[0]), d3(L.p[1]), d3(L.p[2]), d3(L.p[3])};
@@ -315,16 +324,28 @@ void set_camera_light(const mfx_scene_desc& d, MfxHostScene& s) {
 struct Extent {
     double R = 0, T = 0;
 };
-Extent scene_extent(const mfx_scene_desc& d, const std::vector<Box>& pb) {
+// the camera's share (R is a maximum: the order its terms are taken in does not matter)
+Extent extent_with_camera(const MfxHostScene& s, const double* pos) {
     Extent x;
+    x.R = s.extent_R0;
+    for (int a = 0; a < 3; ++a) x.R = std::max(x.R, std::fabs(pos[a]));
+    const D3 lo = d3(s.box_lo), hi = d3(s.box_hi);
+    x.T = len(sub(hi, lo)) + len(sub(d3(pos), scale(add(lo, hi), 0.5)));
+    return x;
+}
+// records what does not depend on the camera (the scene box, R of the primitives and the light) in s:
+// mfx_set_camera sizes eps for another position from them (mfx_camera_eps)
+Extent scene_extent(const mfx_scene_desc& d, const std::vector<Box>& pb, MfxHostScene& s) {
     Box all = pb[0];
     for (size_t i = 1; i < pb.size(); ++i) all = join(all, pb[i]);
-    for (double v : {all.lo.x, all.lo.y, all.lo.z, all.hi.x, all.hi.y, all.hi.z}) x.R = std::max(x.R, std::fabs(v));
-    for (int a = 0; a < 3; ++a) x.R = std::max(x.R, std::fabs(d.camera.position[a]));
-    x.T = len(sub(all.hi, all.lo)) + len(sub(d3(d.camera.position), scale(add(all.lo, all.hi), 0.5)));
+    double R0 = 0;
+    for (double v : {all.lo.x, all.lo.y, all.lo.z, all.hi.x, all.hi.y, all.hi.z}) R0 = std::max(R0, std::fabs(v));
     for (int k = 0; k < 4; ++k)
-        for (int a = 0; a < 3; ++a) x.R = std::max(x.R, std::fabs(d.light.p[k][a]));
-    return x;
+        for (int a = 0; a < 3; ++a) R0 = std::max(R0, std::fabs(d.light.p[k][a]));
+    s.extent_R0 = R0;
+    put(s.box_lo, all.lo);
+    put(s.box_hi, all.hi);
+    return extent_with_camera(s, d.camera.position);
 }
 
 struct SahParams {
@@ -625,6 +646,8 @@ bool build_two_level(const mfx_prim* tprims, const InstancePlan& plan, const Ext
         for (int a = 0; a < 3; ++a) offmax = std::max(offmax, std::fabs(u.off[a]));
     // template frame: coordinates and ray origins up to R + |off| in magnitude
     const float eps_t = (float)std::ldexp(ext.R + offmax + ext.T, -19);
+    s.inst_offmax = offmax;
+    s.eps_templates = eps_t;
     // top level: loose primitives (items 0 .. nl-1), then the instances (solo leaves)
     std::vector<int> loose;
     for (int i = 0; i < n; ++i)
@@ -781,6 +804,12 @@ bool mfx_expand(const mfx_prim* prims, int64_t nprims, const mfx_instance* inst,
     return true;
 }
 
+void mfx_camera_eps(const MfxHostScene& s, const double* pos, float* eps, float* eps_templates) {
+    const Extent ext = extent_with_camera(s, pos);
+    *eps = (float)std::ldexp(ext.R + ext.T, -19);
+    *eps_templates = s.inst.empty() ? 0.f : (float)std::ldexp(ext.R + s.inst_offmax + ext.T, -19);
+}
+
 uint64_t mfx_scene_digest(const MfxHostScene& s) {
     uint64_t x = 1469598103934665603ULL;
     auto mix = [&](const void* p, size_t n) {
@@ -820,8 +849,10 @@ bool mfx_build_scene(const mfx_scene_desc* d0, MfxHostScene& s, std::string& err
     RefGrouping grp;
     if (!group_reference_leaves(rec, s, grp, err)) return false;
     set_camera_light(*d, s);
-    const Extent ext = scene_extent(*d, rec.pb);
+    const Extent ext = scene_extent(*d, rec.pb, s);
     s.eps = (float)std::ldexp(ext.R + ext.T, -19);
+    s.inst_offmax = 0.0;
+    s.eps_templates = 0.f;
     const SahParams sah = read_sah_params();
 
     const auto t_bvh = Clock::now();

@@ -30,6 +30,10 @@ struct MfxHostScene {
     int32_t bvh_depth = 0;     // longest root-to-leaf path in nodes[]
     int32_t stack_entries = 1; // traversal stack bound: pushes along any root-to-node path
     float eps = 0.f;           // conservative box widening
+    float eps_templates = 0.f; // two-level scenes: the widening of the template BVHs' boxes (0: a flat image)
+    // what eps is sized by, less the camera (mfx_camera_eps): R over the primitives and the light, the
+    // scene box, and the largest |offset| coordinate of the traced instances
+    double extent_R0 = 0.0, box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0}, inst_offmax = 0.0;
     // How far beyond tMax a query's node tests must still enter boxes until its first hit.
     // A reference leaf whose box is entered before tMax and whose primitives are all hit beyond tMax is
     // a hit (Triangle.Hit ignores tMax; the leaf's minBy then has no miss key), and the traversal finds
@@ -51,6 +55,12 @@ struct MfxHostScene {
 // flatten: trace it through one flat BVH instead of two levels.
 bool mfx_build_scene(const mfx_scene_desc* d, MfxHostScene& s, std::string& err, bool gpu_bvh = false,
                      const mfx_instance* instances = nullptr, int ninstances = 0, bool flatten = false);
+// PinholeCamera's constructor (Camera.fs:122-133), or with c.derived the fields as they are.
+void mfx_derive_camera(const mfx_pinhole& c, MfxCamera& cam);
+// The widening mfx_build_scene would give s's boxes with the camera at pos: (float)ldexp(R + T, -19), and
+// for a two-level image its template BVHs' (0 for a flat one). Boxes built with at least these stay
+// conservative for every ray that camera starts.
+void mfx_camera_eps(const MfxHostScene& s, const double* pos, float* eps, float* eps_templates);
 // The world primitive list of an instanced scene (mfx_instance: template + offset, FP64).
 bool mfx_expand(const mfx_prim* prims, int64_t nprims, const mfx_instance* inst, int ninst,
                 std::vector<mfx_prim>& world, std::string& err);

@@ -10,10 +10,12 @@ import ctypes as C
 
 import numpy as np
 
-from .abi import (INSTANCING_KEYS, LAUNCH_INFO_KEYS, MFX_DN_SRC_ACCUM, MFX_DN_SRC_ADAPTIVE, MFX_DN_SRC_HOST, MFX_F_NONE,
-                  MFX_F_TWO_LEVEL, MfxAdaptive, MfxAdaptiveResume, MfxDenoiseCfg, MfxDenoiseVarCfg, MfxInstance, MfxOptions, SceneArrays, check,
-                  dptr, iptr, load_library)
+from .abi import (INSTANCING_KEYS, LAUNCH_INFO_KEYS, MFX_DN_SRC_ACCUM, MFX_DN_SRC_ADAPTIVE, MFX_DN_SRC_HOST,
+                  MFX_DN_SRC_TEMPORAL, MFX_F_NONE, MFX_F_TWO_LEVEL, MfxAdaptive, MfxAdaptiveResume, MfxDenoiseCfg,
+                  MfxDenoiseVarCfg, MfxInstance, MfxOptions, MfxTemporalCfg, SceneArrays, check, dptr, iptr, load_library,
+                  pinhole_struct)
 from .denoise import DenoiseConfig, DenoiseVarConfig
+from .temporal import TemporalConfig
 
 DEFAULT_SEED = 0x4D414652
 DEFAULT_RENDER_AHEAD = 64  # fsharp/Native.fs DefaultRenderAhead: Scene.Render served from batches of 64 samples
@@ -147,14 +149,19 @@ class NativeContext:
         return (out, rgba) if want_rgba else out
 
     def denoise_var(self, frame: np.ndarray | None = None, variance: np.ndarray | None = None,
-                    cfg: DenoiseVarConfig = DenoiseVarConfig(), want_rgba: bool = False, want_variance: bool = False):
+                    cfg: DenoiseVarConfig = DenoiseVarConfig(), want_rgba: bool = False, want_variance: bool = False,
+                    source: str | None = None):
         """mfx_denoise_var: the variance-guided a-trous filter (the rule: include/mafrix_rt.h,
         mafrixraytracing_amd/denoise.py) of `frame` ((w*h, 4) x-major, alpha ignored) with `variance`
         ((w*h,) x-major, the variance of each pixel's mean luminance), or with frame=None of the last
         sample_adaptive's result (as resumed since) as it lies on the device (its accumulator, moments and tile counts);
+        or with source="temporal" of the colour and variance the last temporal() call left on the device;
         guided by the feature buffers of the last aov call. Returns the (w*h, 4) filtered frame, or a
         tuple of it, the y-major RGBA8 post (want_rgba) and the (w*h,) filtered variance (want_variance)."""
-        c = MfxDenoiseVarCfg(iterations=cfg.iterations, source=MFX_DN_SRC_ADAPTIVE if frame is None else MFX_DN_SRC_HOST,
+        if source not in (None, "temporal"):
+            raise ValueError('source: None (the frame given, else the adaptive result) or "temporal"')
+        src_code = MFX_DN_SRC_TEMPORAL if source == "temporal" else (MFX_DN_SRC_ADAPTIVE if frame is None else MFX_DN_SRC_HOST)
+        c = MfxDenoiseVarCfg(iterations=cfg.iterations, source=src_code,
                              sigma_normal=cfg.sigma_normal, sigma_depth=cfg.sigma_depth, sigma_albedo=cfg.sigma_albedo,
                              sigma_luma=cfg.sigma_luma, luma_floor=cfg.luma_floor)
         src = var = None
@@ -176,6 +183,63 @@ class NativeContext:
         self.last_denoise_ms = ms.value
         res = (out,) + ((rgba,) if want_rgba else ()) + ((vout,) if want_variance else ())
         return res if len(res) > 1 else out
+
+    def set_camera(self, camera):
+        """mfx_set_camera: make `camera` (a scene-file camera dict, a derived one with position, topleft,
+        right, down, or an MfxPinhole) the camera of every later call. In place when the traversal images'
+        box widening still covers it, else the images are built again (camera_info tells which). The
+        film, the accumulator and next_sample are left as they are: reset() after a move, as the
+        reference's Film.Reset. aov() and sample_adaptive() must run again before denoise, denoise_var,
+        temporal and sample_adaptive_resume."""
+        p = pinhole_struct(camera)
+        check(self.lib.mfx_set_camera(self._h, C.byref(p)), "mfx_set_camera")
+
+    def camera_info(self) -> dict:
+        """mfx_camera_info: the current derived camera (position, topleft, right, down; `derived` the twelve
+        doubles in that order), the camera epoch, the box widening the images were built with, the one the
+        current camera needs, and how often set_camera had to build the images again."""
+        out = np.zeros(16)
+        check(self.lib.mfx_camera_info(self._h, dptr(out)), "mfx_camera_info")
+        return {"position": out[0:3].copy(), "topleft": out[3:6].copy(), "right": out[6:9].copy(), "down": out[9:12].copy(),
+                "derived": out[0:12].copy(), "epoch": int(out[12]), "eps_built": float(out[13]),
+                "eps_needed": float(out[14]), "rebuilds": int(out[15])}
+
+    def temporal(self, frame: np.ndarray | None = None, variance: np.ndarray | None = None,
+                 count: np.ndarray | None = None, cfg: TemporalConfig | None = None, restart: bool = False,
+                 want_rgba: bool = False, **tolerances):
+        """mfx_temporal: reproject the context's history into the current view and merge it with `frame`
+        ((w*h, 4) x-major), its `variance` and sample `count` ((w*h,) each), or with frame=None with the
+        last sample_adaptive's result as it lies on the device (the rule: include/mafrix_rt.h,
+        mafrixraytracing_amd/temporal.py). Returns (frame, variance, count, accepted), plus the y-major
+        RGBA8 post of the frame with want_rgba. cfg: a TemporalConfig, or its fields as keywords
+        (tol_depth, tol_normal2, max_history)."""
+        cfg = cfg if cfg is not None else TemporalConfig(**tolerances)
+        c = MfxTemporalCfg(source=MFX_DN_SRC_ADAPTIVE if frame is None else MFX_DN_SRC_HOST, restart=1 if restart else 0,
+                           tol_depth=cfg.tol_depth, tol_normal2=cfg.tol_normal2, max_history=cfg.max_history)
+        n = self.w * self.h
+        src = var = cnt = None
+        if frame is not None:
+            src = np.ascontiguousarray(frame, dtype=np.float64)
+            assert src.size == n * 4
+        if variance is not None:
+            var = np.ascontiguousarray(variance, dtype=np.float64)
+            assert var.size == n
+        if count is not None:
+            cnt = np.ascontiguousarray(count, dtype=np.float64)
+            assert cnt.size == n
+        out = np.empty((n, 4), dtype=np.float64)
+        vout = np.empty(n, dtype=np.float64)
+        nout = np.empty(n, dtype=np.float64)
+        rgba = np.empty(n * 4, dtype=np.uint8) if want_rgba else None
+        acc = C.c_int64(-1)
+        ms = C.c_double()
+        check(self.lib.mfx_temporal(self._h, C.byref(c), dptr(src) if src is not None else None,
+                                    dptr(var) if var is not None else None, dptr(cnt) if cnt is not None else None,
+                                    dptr(out), dptr(vout), dptr(nout),
+                                    rgba.ctypes.data_as(C.POINTER(C.c_uint8)) if want_rgba else None, C.byref(acc),
+                                    C.byref(ms)), "mfx_temporal")
+        self.last_temporal_ms = ms.value
+        return (out, vout, nout, acc.value) + ((rgba,) if want_rgba else ())
 
     def render_rgba8(self, spp: int = 1, want_pixels: bool = True, out: np.ndarray | None = None) -> np.ndarray | None:
         """Film.GetFrame(spp) + post into `out` (a uint8 buffer of w*h*4, allocated if None), as

@@ -1,0 +1,202 @@
+"""mfx_set_camera on the GPU: a context moved to camera B gives, bit for bit, what a context created with B
+gives and what the CPU oracle gives at B; in place when the boxes' widening still covers B, by building the
+images again otherwise (then the digest and the launch shapes are a fresh create's too); held render-ahead
+frames, the adaptive result and the feature buffers of the old camera are not used afterwards."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from conftest import SEED, scene
+from denoise_helpers import scene_features
+from temporal_helpers import moved, with_camera
+
+pytestmark = pytest.mark.gpu
+
+W, H = 44, 36
+# a move towards the scene (the widening the boxes were built with covers it) and one away from it
+MOVES = {
+    "cornell": (dict(dpos=(0.2, 0.1, -0.5), ddir=(0.05, -0.05, 0.0)), dict(dpos=(0.5, 0.5, 5.0))),
+    "spot16_instanced@2l": (dict(dpos=(-0.5, -0.2, 0.8), ddir=(0.1, 0.0, 0.0)), dict(dpos=(3.0, 2.0, -5.0))),
+}
+
+
+def _ctx(a, **kw):
+    from mafrixraytracing_amd.native import NativeContext
+    return NativeContext(a, seed=SEED, **kw)
+
+
+def _film_frame(oracle, o, bases, w, h):
+    """The RGBA8 frames of one-sample render calls of global samples `bases` on an empty film, by the oracle."""
+    from mafrixraytracing_amd.abi import dptr
+    npix = w * h
+    accum, target, fc = np.zeros((npix, 4)), np.zeros((npix, 4)), np.zeros(1)
+    out = []
+    for s in bases:
+        fr = np.array(o.sample(1, SEED, sample_base=s))
+        oracle.lib().oracle_film_add(dptr(accum), dptr(target), dptr(fc), dptr(fr), npix)
+        out.append(oracle.post_rgba8(target, w, h))
+    return out, target
+
+
+def _same_calls(oracle, m, f, b, spp):
+    """m (moved to b's camera) and f (created with it), both at next_sample 0 with an empty film: sample, aov
+    and a render call agree with each other and with the oracle at that camera."""
+    o = oracle.OracleScene(b)
+    img = m.sample(spp)
+    assert np.array_equal(img, f.sample(spp))
+    assert np.array_equal(m.ray_counts(), f.ray_counts())
+    assert np.array_equal(img, o.sample(spp, SEED))
+    feat = m.aov(2, 1)
+    assert np.array_equal(feat, f.aov(2, 1))
+    assert np.array_equal(feat, scene_features(oracle, b, 2, 1))
+    rgba = m.render_rgba8(1)
+    assert np.array_equal(rgba, f.render_rgba8(1))
+    assert np.array_equal(rgba, _film_frame(oracle, o, [spp], b.width, b.height)[0][0])
+    assert np.array_equal(m.film_mean(), f.film_mean())
+
+
+@pytest.mark.parametrize("name", list(MOVES))
+@pytest.mark.parametrize("mega", [False, True])
+def test_in_place(gpu, oracle, name, mega):
+    from mafrixraytracing_amd.abi import MFX_F_MEGAKERNEL, MFX_F_WAVEFRONT
+    a = scene(name, W, H)
+    cam = moved(a.camera, **MOVES[name][0])
+    b = with_camera(a, cam)
+    flags = MFX_F_MEGAKERNEL if mega else MFX_F_WAVEFRONT
+    with _ctx(a, flags=flags) as m, _ctx(b, flags=flags) as f:
+        before = m.camera_info()
+        assert (before["epoch"], before["rebuilds"]) == (0, 0) and before["eps_needed"] == before["eps_built"]
+        digest = m.build_info()["digest"]
+        m.set_camera(cam)
+        info = m.camera_info()
+        assert (info["epoch"], info["rebuilds"]) == (1, 0)
+        assert info["eps_built"] == before["eps_built"] and info["eps_needed"] <= info["eps_built"]
+        assert np.array_equal(info["derived"], f.camera_info()["derived"])
+        assert m.build_info()["digest"] == digest
+        # (the megakernel adds a pixel's paths in arrival order above one sample per pixel)
+        _same_calls(oracle, m, f, b, 1 if mega else 3)
+
+
+def test_in_place_on_a_repeated_device_list(gpu, oracle):
+    a = scene("cornell", W, H)
+    cam = moved(a.camera, **MOVES["cornell"][0])
+    b = with_camera(a, cam)
+    with _ctx(a, devices=[0, 0]) as m, _ctx(b) as f:
+        m.set_camera(cam)
+        assert (m.camera_info()["epoch"], m.camera_info()["rebuilds"]) == (1, 0)
+        img = m.sample(3)
+        assert np.array_equal(img, oracle.OracleScene(b).sample(3, SEED))
+        assert np.array_equal(img, f.sample(3))
+        assert np.array_equal(m.render_rgba8(1), f.render_rgba8(1))
+        assert np.array_equal(m.film_mean(), f.film_mean())
+
+
+@pytest.mark.parametrize("name", list(MOVES))
+def test_rebuild(gpu, oracle, name):
+    a = scene(name, W, H)
+    cam = moved(a.camera, **MOVES[name][1])
+    b = with_camera(a, cam)
+    with _ctx(a) as m, _ctx(b) as f:
+        before = m.camera_info()
+        m.render_rgba8(2)  # a film that is not empty, and next_sample = 2
+        film = m.film_mean()
+        m.set_camera(cam)
+        info = m.camera_info()
+        assert (info["epoch"], info["rebuilds"]) == (1, 1)
+        assert info["eps_needed"] == info["eps_built"] > before["eps_built"]
+        assert np.array_equal(info["derived"], f.camera_info()["derived"])
+        assert m.build_info()["digest"] == f.build_info()["digest"]
+        shapes = [{k: v for k, v in x.launch_info().items() if k != "pool_max"} for x in (m, f)]  # (pool_max: free memory)
+        assert shapes[0] == shapes[1]
+        assert np.array_equal(m.film_mean(), film)  # the film survived
+        f.render_rgba8(2)
+        img = m.sample(2)  # next_sample survived: samples 2 and 3
+        assert np.array_equal(img, f.sample(2))
+        assert np.array_equal(img, oracle.OracleScene(b).sample(2, SEED, sample_base=2))
+        feat = m.aov(2)
+        assert np.array_equal(feat, f.aov(2))
+        assert np.array_equal(feat, scene_features(oracle, b, 2, 0))
+        m.reset()
+        f.reset()
+        assert np.array_equal(m.render_rgba8(1), f.render_rgba8(1))
+        # and back: the first camera needs less than the images now have
+        m.set_camera(a.camera)
+        info = m.camera_info()
+        assert (info["epoch"], info["rebuilds"]) == (2, 1) and info["eps_needed"] < info["eps_built"]
+        assert np.array_equal(m.sample(1), oracle.OracleScene(a).sample(1, SEED, sample_base=5))
+
+
+def test_render_ahead_serves_no_frame_of_the_old_camera(gpu, oracle):
+    a = scene("cornell", W, H)
+    cam = moved(a.camera, **MOVES["cornell"][0])
+    b = with_camera(a, cam)
+    with _ctx(a, render_ahead=8) as m, _ctx(b, render_ahead=8) as f:
+        for _ in range(3):  # mid-batch: frames of samples 3..7 are held, the next batch is in the background
+            m.render_rgba8(1)
+            f.render_rgba8(1)
+        m.set_camera(cam)
+        m.reset()
+        f.reset()
+        got = [m.render_rgba8(1).copy() for _ in range(4)]
+        want = [f.render_rgba8(1).copy() for _ in range(4)]
+        frames, target = _film_frame(oracle, oracle.OracleScene(b), [3, 4, 5, 6], W, H)
+        for k in range(4):
+            assert np.array_equal(got[k], want[k]), k
+            assert np.array_equal(got[k], frames[k]), k
+        assert np.array_equal(m.film_mean()[:, :3], target[:, :3])
+
+
+def test_what_a_move_invalidates(gpu):
+    from mafrixraytracing_amd.abi import MfxError
+    a = scene("cornell", 16, 8)
+    cam = moved(a.camera, **MOVES["cornell"][0])
+    npix = 16 * 8
+    var, cnt = np.full(npix, 0.01), np.full(npix, 4.0)
+    state = r"\(-4\)"  # MFX_E_STATE
+    with _ctx(a) as c:
+        c.aov(2)
+        frame, tiles = c.sample_adaptive(2, 4, 2, 0.25, 0.01)
+        c.denoise(frame), c.denoise_var(None), c.temporal(None), c.sample_adaptive_resume(6, 2, 0.25, 0.01)
+        c.set_camera(cam)
+        for call in (lambda: c.sample_adaptive_resume(8, 2, 0.25, 0.01), lambda: c.denoise(frame),
+                     lambda: c.denoise_var(frame, variance=var), lambda: c.denoise_var(None),
+                     lambda: c.temporal(frame, var, cnt), lambda: c.temporal(None),
+                     lambda: c.denoise_var(source="temporal")):
+            with pytest.raises(MfxError, match=state):
+                call()
+        c.aov(2)  # the features are the new camera's; the adaptive result is still the old one's
+        c.denoise(frame), c.denoise_var(frame, variance=var)
+        for call in (lambda: c.sample_adaptive_resume(8, 2, 0.25, 0.01), lambda: c.denoise_var(None),
+                     lambda: c.temporal(None), lambda: c.denoise_var(source="temporal")):
+            with pytest.raises(MfxError, match=state):
+                call()
+        c.sample_adaptive(2, 4, 2, 0.25, 0.01)
+        c.sample_adaptive_resume(6, 2, 0.25, 0.01), c.denoise_var(None)
+        assert c.temporal(None)[3] >= 0
+        c.denoise_var(source="temporal")
+        # the current camera again, in either form: nothing happens
+        c.set_camera(cam)
+        c.set_camera({k: c.camera_info()[k] for k in ("position", "topleft", "right", "down")})
+        assert c.camera_info()["epoch"] == 1
+        c.sample_adaptive_resume(6, 2, 0.25, 0.01), c.denoise_var(None), c.denoise_var(source="temporal")
+
+
+def test_refusals(gpu):
+    from mafrixraytracing_amd.abi import pinhole_struct
+    a = scene("cornell", 16, 8)
+    nan, inf = float("nan"), float("inf")
+    with _ctx(a) as c:
+        ok = pinhole_struct(a.camera)
+        assert c.lib.mfx_set_camera(c._h, None) == -1 and c.lib.mfx_set_camera(None, C.byref(ok)) == -1
+        assert c.lib.mfx_camera_info(c._h, None) == -1
+        for bad in (dict(position=(nan, 0, 0)), dict(position=(0, inf, 0)), dict(direction=(0, 0, nan)),
+                    dict(direction=(0.0, 0.0, 0.0)), dict(fov=nan), dict(aspect=inf), dict(aspect=0.0)):
+            p = pinhole_struct({**a.camera, **bad})
+            assert c.lib.mfx_set_camera(c._h, C.byref(p)) == -1, bad  # MFX_E_INVALID
+            assert b"mfx_set_camera" in c.lib.mfx_last_error()
+        d = {k: c.camera_info()[k] for k in ("position", "topleft", "right", "down")}
+        for k in ("topleft", "right", "down"):
+            p = pinhole_struct({**d, k: (0.0, nan, 0.0)})
+            assert c.lib.mfx_set_camera(c._h, C.byref(p)) == -1, k
+        assert c.camera_info()["epoch"] == 0  # none of them moved the camera
