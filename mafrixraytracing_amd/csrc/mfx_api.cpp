@@ -9,7 +9,6 @@
 // call falls back to a CPU path.
 #include <dlfcn.h>
 
-#include <mutex>
 #include <set>
 #include <thread>
 
@@ -104,35 +103,45 @@ mfx_ctx::~mfx_ctx() {
     (void)hipSetDevice(device);
 }
 
-// MFX_STREAM_POOL=K: contexts take their stream from K streams per device that the process creates at
-// its first context and keeps, round robin, instead of creating (and at destruction releasing) one
-// each. The HIP runtime maps streams onto GPU_MAX_HW_QUEUES hardware queues as it creates them; a
-// context created after other streams came and went (torch's stream pools, earlier contexts) can land
-// on a queue another context of its frames in flight already uses, and their launches then serialize.
-// Streams created first, once, keep distinct queues for the process's life (r06k, scripts/share_queues.py).
-static int stream_pool_size() {
-    static const int k = getenv("MFX_STREAM_POOL") ? std::max(0, std::min(16, atoi(getenv("MFX_STREAM_POOL")))) : 0;
-    return k;
+static CreateEnv read_create_env() {
+    const auto set = [](const char* name) { return getenv(name) != nullptr; };
+    const auto num = [](const char* name) { return getenv(name) ? CreateEnv::Int(atoi(getenv(name))) : std::nullopt; };
+    CreateEnv v;
+    v.node_f32 = set("MFX_NODE_F32");
+    v.diag_iter = set("MFX_DIAG_ITER");
+    v.no_gray_light = set("MFX_NO_GRAY_LIGHT");
+    v.no_lit_in_hit = set("MFX_NO_LIT_IN_HIT");
+    v.mega_waves = num("MFX_MEGA_WAVES");
+    v.shadow_target_blocks = num("MFX_SHADOW_TARGET_BLOCKS");
+    v.stack_lds = num("MFX_STACK_LDS");
+    v.ntop = num("MFX_NTOP");
+    v.slot_lds = num("MFX_SLOT_LDS");
+    v.shadow_waves = num("MFX_SHADOW_WAVES");
+    v.blocks_per_cu = num("MFX_BLOCKS_PER_CU");
+    v.camera_packets = num("MFX_CAMERA_PACKETS");
+    v.cam_blocks = num("MFX_CAM_BLOCKS");
+    v.pool_fail_once = num("MFX_POOL_FAIL_ONCE");
+    v.adaptive_check = num("MFX_ADAPTIVE_CHECK");
+    v.iter_events = num("MFX_ITER_EVENTS");
+    v.queue_from = num("MFX_QUEUE_FROM");
+    v.qchunk = num("MFX_QCHUNK");
+    v.ray_queue = num("MFX_RAY_QUEUE");
+    v.mega_chunk = num("MFX_MEGA_CHUNK");
+    v.shd_half = num("MFX_SHD_HALF");
+    v.chunk = num("MFX_CHUNK");
+    if (const char* e = getenv("MFX_POOL")) v.pool = atoll(e);
+    return v;
 }
-static hipError_t process_stream(int device, int k, hipStream_t* out) {
-    static std::mutex mu;
-    static std::vector<std::vector<hipStream_t>> pool;
-    static std::vector<unsigned> next;
-    std::lock_guard<std::mutex> lock(mu);
-    if ((int)pool.size() <= device) {
-        pool.resize(device + 1);
-        next.resize(device + 1, 0);
+
+// the largest v in [lo, hi] that keeps(v) holds for; lo is taken to keep it, and no v above one that does not
+template <typename F>
+static int largest_keeping(int lo, int hi, F keeps) {
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) / 2;
+        if (keeps(mid)) lo = mid;
+        else hi = mid - 1;
     }
-    if (pool[device].empty()) {
-        for (int i = 0; i < k; ++i) {
-            hipStream_t s = nullptr;
-            const hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-            if (e != hipSuccess) return e;
-            pool[device].push_back(s);
-        }
-    }
-    *out = pool[device][next[device]++ % pool[device].size()];
-    return hipSuccess;
+    return lo;
 }
 
 #define CK(expr) HIP_TRY(expr, _e == hipErrorOutOfMemory ? MFX_E_NOMEM : MFX_E_DEVICE, #expr ": ")
@@ -144,7 +153,7 @@ static int scene_upload(mfx_ctx* c) {
     if (c->stack_size > 96) return fail(MFX_E_INVALID, "mfx_create: BVH too deep for the LDS traversal stack");
     CK(upload(c->d_nodes, c->host.nodes));
     CK(upload(c->d_slots, c->host.slots));
-    if (MFX_NODE_F16 && !getenv("MFX_NODE_F32")) {  // (MFX_NODE_F32=1: the F16 build on FP32 nodes)
+    if (MFX_NODE_F16 && !c->env.node_f32) {  // (MFX_NODE_F32=1: the F16 build on FP32 nodes)
         std::vector<MfxNodeH> nh(c->host.nodes.size());
         for (size_t i = 0; i < nh.size(); ++i) nh[i] = node_to_half(c->host.nodes[i]);
         CK(upload(c->d_nodes_h, nh));
@@ -164,14 +173,14 @@ static int scene_upload(mfx_ctx* c) {
 // Occupancy-derived launch shapes of the scene in c->host (its stack bound, node and slot counts,
 // instances), and the buffers sized by them; with the context's device current
 static int scene_shapes(mfx_ctx* c) {
+    const CreateEnv& env = c->env;
     const bool inst = !c->host.inst.empty();
-    const int ninst = (int)c->host.inst.size();
     hipDeviceProp_t prop;
     CK(hipGetDeviceProperties(&prop, c->device));
     int bpc = 0;
     // the megakernel's register budget: 4 waves per SIMD unless the stack is deep (its spills)
     c->mega_waves = c->stack_size <= 36 ? 4 : 1;
-    if (const char* e = getenv("MFX_MEGA_WAVES")) c->mega_waves = atoi(e) == 4 ? 4 : 1;
+    if (env.mega_waves) c->mega_waves = *env.mega_waves == 4 ? 4 : 1;
     CK(mfx_trace_occupancy(c->stack_size, &bpc, inst, c->mega_waves));
     bpc = std::max(1, std::min(bpc, 8));
     c->grid = prop.multiProcessorCount * bpc;
@@ -183,71 +192,54 @@ static int scene_shapes(mfx_ctx* c) {
     // share that keeps it is +2 % (C2, C5) to +4 % (C4) (r02y: 16 entries, the round-1 rule, gained
     // nothing there).
     WfParams& A = c->pool.params;  // the launch shapes go straight into the trace's parameters
+    hipError_t qerr = hipSuccess;  // the first occupancy query that failed (its answer counts as no block)
+    // resident blocks per CU of k_extend or k_shadow with nlds stack entries per lane in LDS (the rest
+    // spilled), and ntop top nodes and nslot slots beside them
+    auto blocks = [&](bool shd, int nlds, int ntop = 0, int nslot = 0) {
+        const WfLdsShape s{shd, nlds < c->stack_size, c->d_nodes_h != nullptr, nlds, ntop, (int)c->host.inst.size(), nslot};
+        int b = 0;
+        const hipError_t e = mfx_wf_kernel_occupancy(s, &b);
+        if (e != hipSuccess && qerr == hipSuccess) qerr = e;
+        return e == hipSuccess ? b : 0;
+    };
     int ebpc = 0, sbpc = 0;
-    const MfxNodeH* nodes_h = c->d_nodes_h;
-    const bool fp16 = nodes_h != nullptr;  // the node format the trace kernels' instances are chosen by
-    const int shd_target_max = getenv("MFX_SHADOW_TARGET_BLOCKS") ? atoi(getenv("MFX_SHADOW_TARGET_BLOCKS")) : 8;
     for (const bool shd : {false, true}) {
-        int full = 0;
-        CK(mfx_wf_kernel_occupancy(shd, c->stack_size, false, 0, ninst, &full, 0, fp16));
-        int nlds = c->stack_size, blocks = full;
+        const int full = blocks(shd, c->stack_size);
+        int nlds = c->stack_size;
         if (c->stack_size > WF_STACK_LDS) {
-            int b16 = 0;
-            CK(mfx_wf_kernel_occupancy(shd, WF_STACK_LDS, true, 0, ninst, &b16, 0, fp16));
-            const int target = shd ? std::max(full, std::min(shd_target_max, b16)) : b16;
-            if (full < target) {
-                int lo = WF_STACK_LDS, hi = c->stack_size - 1;  // blocks only fall as the share grows
-                while (lo < hi) {
-                    const int mid = (lo + hi + 1) / 2;
-                    int b = 0;
-                    CK(mfx_wf_kernel_occupancy(shd, mid, true, 0, ninst, &b, 0, fp16));
-                    if (b >= target) lo = mid;
-                    else hi = mid - 1;
-                }
-                nlds = lo;
-                CK(mfx_wf_kernel_occupancy(shd, nlds, true, 0, ninst, &blocks, 0, fp16));
-            }
+            const int b16 = blocks(shd, WF_STACK_LDS);
+            const int target = shd ? std::max(full, std::min(env.shadow_target_blocks.value_or(8), b16)) : b16;
+            // (blocks only fall as the share grows)
+            if (full < target) nlds = largest_keeping(WF_STACK_LDS, c->stack_size - 1, [&](int n) { return blocks(shd, n) >= target; });
             if (c->diag_iter)
                 fprintf(stderr, "wavefront: %s blocks/CU: full %d-entry stacks %d, %d in LDS %d; chosen %d in LDS, %d\n",
-                        shd ? "k_shadow" : "k_extend", c->stack_size, full, WF_STACK_LDS, b16, nlds, blocks);
+                        shd ? "k_shadow" : "k_extend", c->stack_size, full, WF_STACK_LDS, b16, nlds, blocks(shd, nlds));
         }
-        if (const char* e = getenv("MFX_STACK_LDS")) {
-            nlds = std::max(1, std::min(c->stack_size, atoi(e)));
-            CK(mfx_wf_kernel_occupancy(shd, nlds, nlds < c->stack_size, 0, ninst, &blocks, 0, fp16));
-        }
+        if (env.stack_lds) nlds = std::max(1, std::min(c->stack_size, *env.stack_lds));
         (shd ? A.stack_lds_shd : A.stack_lds_ext) = nlds;
-        (shd ? sbpc : ebpc) = blocks;
+        (shd ? sbpc : ebpc) = blocks(shd, nlds);
     }
     {  // top BVH nodes in LDS: as many as fit in the LDS the resident blocks leave over
         int cap = std::min((int)c->host.nodes.size(), WF_NTOP_MAX);
-        if (const char* e = getenv("MFX_NTOP")) cap = std::max(0, std::min(cap, atoi(e)));
+        if (env.ntop) cap = std::max(0, std::min(cap, *env.ntop));
         for (const bool shd : {false, true}) {
             const int nlds = shd ? A.stack_lds_shd : A.stack_lds_ext, want = shd ? sbpc : ebpc;
-            int lo = 0, hi = cap;  // resident blocks do not grow with ntop: bisect the largest that keeps them
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) / 2;
-                int b = 0;
-                CK(mfx_wf_kernel_occupancy(shd, nlds, nlds < c->stack_size, mid, ninst, &b, 0, fp16));
-                if (b >= want) lo = mid;
-                else hi = mid - 1;
-            }
-            (shd ? A.ntop_shd : A.ntop_ext) = lo;
+            // (resident blocks do not grow with ntop)
+            const int ntop = largest_keeping(0, cap, [&](int n) { return blocks(shd, nlds, n) >= want; });
+            (shd ? A.ntop_shd : A.ntop_ext) = ntop;
             // A small scene's whole slot array (80-B test prefixes) in LDS too, when it fits beside the
             // top nodes without costing a resident block: every leaf test then reads LDS (C3: 26 slots)
             // (two-level scenes: none — their kernel instances never read slots from LDS)
             int ns = inst ? 0 : (int)c->host.slots.size();
-            if (ns > WF_SLOT_LDS_MAX || (getenv("MFX_SLOT_LDS") && atoi(getenv("MFX_SLOT_LDS")) == 0)) ns = 0;
-            if (ns > 0) {
-                int b = 0;
-                CK(mfx_wf_kernel_occupancy(shd, nlds, nlds < c->stack_size, lo, ninst, &b, ns, fp16));
-                if (b < want) ns = 0;
-            }
+            if (ns > WF_SLOT_LDS_MAX || (env.slot_lds && *env.slot_lds == 0)) ns = 0;
+            if (ns > 0 && blocks(shd, nlds, ntop, ns) < want) ns = 0;
             (shd ? A.nslot_shd : A.nslot_ext) = ns;
         }
+        HIP_TRY(qerr, MFX_E_DEVICE, "mfx_wf_kernel_occupancy: ");
         // k_shadow with at most 3 resident blocks per CU (its LDS) runs the instance compiled for 3
         // waves per SIMD: more registers, no spills (C2 / C5 +2 %); with 4 it keeps the 4-wave one
         A.shadow_waves = sbpc <= 3 ? 3 : 4;
-        if (const char* e = getenv("MFX_SHADOW_WAVES")) A.shadow_waves = atoi(e) == 3 ? 3 : 4;
+        if (env.shadow_waves) A.shadow_waves = *env.shadow_waves == 3 ? 3 : 4;
         if (A.shadow_waves == 3) sbpc = std::min(sbpc, 3);
         if (c->diag_iter)
             fprintf(stderr,
@@ -256,17 +248,16 @@ static int scene_shapes(mfx_ctx* c) {
                     A.stack_lds_ext, c->stack_size, A.stack_lds_shd, c->stack_size, ebpc, sbpc,
                     A.shadow_waves, A.ntop_ext, A.ntop_shd, A.nslot_ext, A.nslot_shd);
     }
-    if (const char* b = getenv("MFX_BLOCKS_PER_CU")) {  // tuning knob: resident blocks per CU (<= occupancy)
-        ebpc = std::min(ebpc, std::max(1, atoi(b)));
-        sbpc = std::min(sbpc, std::max(1, atoi(b)));
+    if (env.blocks_per_cu) {  // tuning knob: resident blocks per CU (<= occupancy)
+        ebpc = std::min(ebpc, std::max(1, *env.blocks_per_cu));
+        sbpc = std::min(sbpc, std::max(1, *env.blocks_per_cu));
     }
     c->wf_ext_grid = prop.multiProcessorCount * std::max(1, std::min(ebpc, 8));
     {  // camera-ray packets (flat scenes)
-        int cam = getenv("MFX_CAMERA_PACKETS") ? atoi(getenv("MFX_CAMERA_PACKETS")) : 1;
-        if (cam && !inst) {
+        if (env.camera_packets.value_or(1) && !inst) {
             int cb = 0;
             CK(mfx_cam_occupancy(c->stack_size, &cb));
-            if (const char* e = getenv("MFX_CAM_BLOCKS")) cb = std::min(cb, std::max(1, atoi(e)));
+            if (env.cam_blocks) cb = std::min(cb, std::max(1, *env.cam_blocks));
             c->wf_cam_grid = prop.multiProcessorCount * std::max(1, std::min(cb, 8));
         }
     }
@@ -287,14 +278,9 @@ static int scene_shapes(mfx_ctx* c) {
 // failure the caller destroys the context, which releases whatever was allocated.
 static int ctx_setup(mfx_ctx* c) {
     c->npix = (int64_t)c->host.width * c->host.height;
+    const CreateEnv& env = c->env = read_create_env();
     CK(hipSetDevice(c->device));
-    if (const int k = stream_pool_size()) {  // MFX_STREAM_POOL (see process_stream)
-        hipStream_t s = nullptr;
-        CK(process_stream(c->device, k, &s));
-        c->stream.borrow(s);
-    } else {
-        CK(c->stream.create());
-    }
+    CK(c->stream.create());
     CK(c->h_counters.alloc(WF_NCTR * WF_SHARDS));
     CK(c->ev0.create());
     CK(c->ev1.create());
@@ -314,15 +300,15 @@ static int ctx_setup(mfx_ctx* c) {
     if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree > 0)
         c->pool.max = std::max<int64_t>(1 << 20, std::min<int64_t>(c->pool.max, (int64_t)(mfree / 4 / pool_slot_bytes(c))));
     // (at most 2^28 slots: k_extend's pending entries keep a slot index in 28 bits)
-    c->pool.fail_once = getenv("MFX_POOL_FAIL_ONCE") && atoi(getenv("MFX_POOL_FAIL_ONCE")) != 0;
-    if (const char* pm = getenv("MFX_POOL")) c->pool.max = std::max<int64_t>(2048, std::min<int64_t>(1 << 28, atoll(pm)));
-    c->diag_iter = getenv("MFX_DIAG_ITER") != nullptr;
-    c->adp.check = getenv("MFX_ADAPTIVE_CHECK") && atoi(getenv("MFX_ADAPTIVE_CHECK")) != 0;
-    if (const char* e = getenv("MFX_ITER_EVENTS")) c->iter_events = atoi(e) != 0 || c->diag_iter;
-    if (const char* qf = getenv("MFX_QUEUE_FROM")) c->pool.queue_from = MFX_RAY_QUEUE ? std::max(-2, atoi(qf)) : -1;
-    if (const char* qc = getenv("MFX_QCHUNK")) c->pool.qchunk = std::max(64, std::min(WF_CHUNK_MAX, atoi(qc) / 64 * 64));
-    if (getenv("MFX_RAY_QUEUE") && atoi(getenv("MFX_RAY_QUEUE")) == 0) c->pool.queue_from = -1;
-    if (const char* ck = getenv("MFX_MEGA_CHUNK")) c->mega_chunk = std::max(1, atoi(ck));
+    c->pool.fail_once = env.pool_fail_once.value_or(0) != 0;
+    if (env.pool) c->pool.max = std::max<int64_t>(2048, std::min<int64_t>(1 << 28, *env.pool));
+    c->diag_iter = env.diag_iter;
+    c->adp.check = env.adaptive_check.value_or(0) != 0;
+    if (env.iter_events) c->iter_events = *env.iter_events != 0 || c->diag_iter;
+    if (env.queue_from) c->pool.queue_from = MFX_RAY_QUEUE ? std::max(-2, *env.queue_from) : -1;
+    if (env.qchunk) c->pool.qchunk = std::max(64, std::min(WF_CHUNK_MAX, *env.qchunk / 64 * 64));
+    if (env.ray_queue && *env.ray_queue == 0) c->pool.queue_from = -1;
+    if (env.mega_chunk) c->mega_chunk = std::max(1, *env.mega_chunk);
     // MFX_F_IN_FLIGHT: the caller alternates frames over several contexts of this device, so each
     // launch's ramp-down runs beside another frame's launches: larger chunk fetches and whole ones
     // for k_shadow (r05s, C2's 1/8 share over 3 contexts: 4.44 -> 4.37 ms, the 1/4 share 8.78 -> 8.63)
@@ -330,8 +316,8 @@ static int ctx_setup(mfx_ctx* c) {
         c->wf_chunk = 512;
         c->wf_shd_half = false;
     }
-    if (const char* e = getenv("MFX_SHD_HALF")) c->wf_shd_half = atoi(e) != 0;
-    if (const char* ck = getenv("MFX_CHUNK")) c->wf_chunk = std::max(64, std::min(WF_CHUNK_MAX, atoi(ck) / 64 * 64));
+    if (env.shd_half) c->wf_shd_half = *env.shd_half != 0;
+    if (env.chunk) c->wf_chunk = std::max(64, std::min(WF_CHUNK_MAX, *env.chunk / 64 * 64));
     CK(hipMemset(c->d_accum, 0, 3 * plane));
     CK(hipMemset(c->d_film, 0, 3 * plane));
     CK(hipMemset(c->d_counters, 0, kCounterBytes));

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <functional>
 #include <memory>
+#include <optional>
 #include <string>
 #include <utility>
 #include <variant>
@@ -82,25 +83,20 @@ public:
     operator hipEvent_t() const { return e_; }
 };
 
-class Stream {  // hipStreamCreateWithFlags(hipStreamNonBlocking) / hipStreamDestroy, or a borrowed stream
+class Stream {  // hipStreamCreateWithFlags(hipStreamNonBlocking) / hipStreamDestroy
     hipStream_t s_ = nullptr;
-    bool owned_ = false;
 public:
     Stream() = default;
-    Stream(Stream&& o) noexcept : s_(std::exchange(o.s_, nullptr)), owned_(std::exchange(o.owned_, false)) {}
-    Stream& operator=(Stream&& o) noexcept { return std::swap(s_, o.s_), std::swap(owned_, o.owned_), *this; }
+    Stream(Stream&& o) noexcept : s_(std::exchange(o.s_, nullptr)) {}
+    Stream& operator=(Stream&& o) noexcept { return std::swap(s_, o.s_), *this; }
     ~Stream() { reset(); }
     hipError_t create() {
         reset();
         const hipError_t e = hipStreamCreateWithFlags(&s_, hipStreamNonBlocking);
-        owned_ = e == hipSuccess;
+        if (e != hipSuccess) s_ = nullptr;
         return e;
     }
-    void borrow(hipStream_t s) { reset(), s_ = s; }  // not destroyed here (MFX_STREAM_POOL: the process keeps it)
-    void reset() {
-        if (s_ && owned_) (void)hipStreamDestroy(s_);
-        s_ = nullptr, owned_ = false;
-    }
+    void reset() { if (s_) (void)hipStreamDestroy(std::exchange(s_, nullptr)); }
     hipStream_t get() const { return s_; }
     operator hipStream_t() const { return s_; }
 };
@@ -299,7 +295,18 @@ struct Readback {
     Stream copy_stream;  // frame copies to the host (overlap the background trace); created at the first
                          // render-ahead or mfx_sample call, so a batch-only context holds one stream (one
                          // of the process's GPU_MAX_HW_QUEUES hardware queues)
-    Stream sample_copy2;  // mfx_sample's banded readback: a second copy stream (MFX_SAMPLE_COPY_STREAMS=2)
+};
+
+// The MFX_* variables that shape a context's launches, as the environment held them when the context was
+// created (read_create_env, mfx_api.cpp: the one place that reads them; unset: no value). What they mean,
+// their clamps and their defaults are where they are used: scene_upload, scene_shapes, ctx_setup and the
+// two wf_* rules below. A rebuild under mfx_set_camera uses these values, not the environment's.
+struct CreateEnv {
+    using Int = std::optional<int>;
+    bool node_f32 = false, diag_iter = false, no_gray_light = false, no_lit_in_hit = false;  // set at all
+    Int mega_waves, shadow_target_blocks, stack_lds, ntop, slot_lds, shadow_waves, blocks_per_cu, camera_packets, cam_blocks;
+    Int pool_fail_once, adaptive_check, iter_events, queue_from, qchunk, ray_queue, mega_chunk, shd_half, chunk;
+    std::optional<int64_t> pool;
 };
 
 // Multi-device (primary context only)
@@ -321,7 +328,7 @@ struct Multi {
 // One mfx_ctx = one `Scene` on one or more GPUs (mfx_api.cpp).
 struct __attribute__((visibility("hidden"))) mfx_ctx {
     int device = 0;
-    mfxh::Stream stream;  // the context's own, or one of the process's pool (MFX_STREAM_POOL)
+    mfxh::Stream stream;
     MfxHostScene host;
     mfxh::DevBuf<MfxNode> d_nodes;
     mfxh::DevBuf<MfxSlot> d_slots;
@@ -383,6 +390,7 @@ struct __attribute__((visibility("hidden"))) mfx_ctx {
     double rep_counts[16] = {0};
     double rep_timing[8] = {0};      // mfx_trace_timing's stage split (mfx_sample_adaptive: summed over its passes; else 0)
     double rep_ms = 0.0;
+    mfxh::CreateEnv env;
     bool diag_iter = false;
     bool iter_events = true;  // per-iteration HIP events around each launch (mfx_trace_timing's stage split)
     // per feature: each owns what it allocates
@@ -435,11 +443,11 @@ void fill_scene_ptrs(const mfx_ctx* c, P& p) {
 inline bool wf_gray_light(const mfx_ctx* c) {
     const double* I = c->host.light.color;
     return std::memcmp(&I[0], &I[1], sizeof(double)) == 0 && std::memcmp(&I[0], &I[2], sizeof(double)) == 0 &&
-           !getenv("MFX_NO_GRAY_LIGHT");
+           !c->env.no_gray_light;
 }
 // in place, a HIT state word carries the path's lit mask (WfParams.lit_in_hit)
 inline bool wf_lit_in_hit(const mfx_ctx* c) {
-    return c->host.max_depth <= 3 && c->host.shade.size() <= ((size_t)1 << 25) && !getenv("MFX_NO_LIT_IN_HIT");
+    return c->host.max_depth <= 3 && c->host.shade.size() <= ((size_t)1 << 25) && !c->env.no_lit_in_hit;
 }
 
 // MFX_OK, or MFX_E_STATE for a call that needs one device and the whole film and sample set

@@ -72,6 +72,14 @@ struct QueryParams {
     double tslack;  // MfxHostScene::tslack (SceneView::tslack)
 };
 
+// Blocks per CU that `bytes` of LDS per block allow: gfx950 allocates LDS in 1,280-byte granules out of
+// 160 KB per CU. hipOccupancyMaxActiveBlocksPerMultiprocessor counts finer granules, so near a boundary
+// it reports one block more than fits; the occupancy queries take the smaller of the two.
+inline int mfx_lds_blocks(size_t bytes) {
+    const size_t g = 1280, per_cu = 160 * 1024;
+    return (int)(per_cu / ((bytes + g - 1) / g * g));
+}
+
 hipError_t mfx_launch_trace(const TraceParams& P, bool stats, int grid, hipStream_t st);
 hipError_t mfx_trace_occupancy(int stack_size, int* blocks_per_cu, bool inst = false, int waves = 1);
 hipError_t mfx_launch_query(const QueryParams& Q, bool shadow, hipStream_t st);

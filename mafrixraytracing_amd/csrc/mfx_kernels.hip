@@ -571,9 +571,7 @@ hipError_t mfx_trace_occupancy(int stack_size, int* blocks_per_cu, bool inst, in
     const void* k = waves == 4 ? (inst ? (const void*)trace_kernel<false, true, 4> : (const void*)trace_kernel<false, false, 4>)
                                : (inst ? (const void*)trace_kernel<false, true, 1> : (const void*)trace_kernel<false, false, 1>);
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k, 256, lds);
-    // gfx950 allocates LDS in 1,280-byte granules of its 160 KB (the API counts finer ones)
-    const size_t g = 1280;
-    *blocks_per_cu = std::min(*blocks_per_cu, (int)(160 * 1024 / ((lds + g - 1) / g * g)));
+    *blocks_per_cu = std::min(*blocks_per_cu, mfx_lds_blocks(lds));
     return e;
 }
 

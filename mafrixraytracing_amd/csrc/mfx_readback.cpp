@@ -148,59 +148,6 @@ int mfxh::host_readback(mfx_ctx* c, void* dst, const void* src, size_t bytes, hi
     return copy_staged(c, dst, off, len, used);
 }
 
-// mfx_sample's copy stream. MFX_COPY_PROBE=K (K > 1; an A/B knob, off by default) chooses it by
-// measurement: K candidate streams each copy `bytes` (up to 16 MB) of the frame twice, the second copy
-// timed, and the fastest is kept, once per context. The readback had run at ~53 GB/s in some contexts
-// and ~26-31 GB/s in others; the probe found every candidate of a box alike (29.7 GB/s on one box,
-// r06t: the rate is the box's, not the stream's), and contexts that probed traced 8 % slower in two
-// cases of six (the streams it creates and destroys move the context's hardware queues; r06y, r06z),
-// never without it. One stream, created at the first Sample call, is the default.
-static int pick_copy_stream(mfx_ctx* c, size_t bytes) {
-    int n = 1;
-    if (const char* e = getenv("MFX_COPY_PROBE")) n = std::max(1, std::min(8, atoi(e)));
-    if (n == 1) {
-        HIPCHECK(c->rb.copy_stream.create());
-        return MFX_OK;
-    }
-    const size_t pb = std::min(bytes, (size_t)16 << 20);
-    uint8_t* stage = c->rb.stage;
-    std::vector<Stream> cand(n);
-    std::vector<float> ms(n, 1e30f);
-    Event e0, e1;
-    HIPCHECK(e0.create());
-    HIPCHECK(e1.create());
-    for (int i = 0; i < n; ++i) {
-        HIPCHECK(cand[i].create());
-        HIPCHECK(hipMemcpyAsync(stage, c->d_frame, pb, hipMemcpyDeviceToHost, cand[i]));
-        HIPCHECK(hipEventRecord(e0, cand[i]));
-        HIPCHECK(hipMemcpyAsync(stage, c->d_frame, pb, hipMemcpyDeviceToHost, cand[i]));
-        HIPCHECK(hipEventRecord(e1, cand[i]));
-        HIPCHECK(hipEventSynchronize(e1));
-        HIPCHECK(hipEventElapsedTime(&ms[i], e0, e1));
-    }
-    const int best = (int)(std::min_element(ms.begin(), ms.end()) - ms.begin());
-    if (sample_timing()) {  // (diagnostics: the candidates' copies at once, k = 2 and all n)
-        for (int k : {2, n}) {
-            HIPCHECK(hipDeviceSynchronize());
-            const double t0 = host_ms();
-            for (int i = 0; i < k; ++i)
-                HIPCHECK(hipMemcpyAsync(stage + (size_t)i * (pb / n), (const uint8_t*)c->d_frame.get(), pb / n * (n / k),
-                                        hipMemcpyDeviceToHost, cand[i]));
-            for (int i = 0; i < k; ++i) HIPCHECK(hipStreamSynchronize(cand[i]));
-            const double dt = host_ms() - t0;
-            fprintf(stderr, "pick_copy_stream: %d streams at once, %zu B each: %.1f GB/s together\n", k, pb / n * (n / k),
-                    (double)(pb / n * (n / k)) * k / (dt * 1e6));
-        }
-    }
-    c->rb.copy_stream = std::move(cand[best]);  // the others go with `cand`
-    if (sample_timing()) {
-        fprintf(stderr, "pick_copy_stream: %zu B per probe, GB/s:", pb);
-        for (int i = 0; i < n; ++i) fprintf(stderr, " %.1f", pb / (ms[i] * 1e6));
-        fprintf(stderr, "; kept %d\n", best);
-    }
-    return MFX_OK;
-}
-
 // mfx_sample on one device: the trace with its last resolve in column bands of tiles (ResolveSplit),
 // each band's mean enqueued right behind its resolve and its readback on the copy stream, so the
 // frame's DMA and the host copy overlap the rest of the resolve. A band of tile columns is a contiguous
@@ -224,15 +171,12 @@ static int sample_banded(mfx_ctx* c, int32_t spp, double* frame) {
     Readback& rb = c->rb;
     HIPCHECK(hipSetDevice(c->device));
     MFX_TRY(stage_events(c));
-    if (!rb.copy_stream) MFX_TRY(pick_copy_stream(c, bytes));
-    int ncs = 1;  // MFX_SAMPLE_COPY_STREAMS=2: bands alternate over two copy streams (A/B knob; slower, r06i)
-    if (const char* e = getenv("MFX_SAMPLE_COPY_STREAMS")) ncs = atoi(e) == 2 ? 2 : 1;
+    if (!rb.copy_stream) HIPCHECK(rb.copy_stream.create());  // one stream, created at the first Sample call
     // MFX_SAMPLE_ZEROCOPY=1 (A/B knob): each band's mean kernel runs on a copy stream and writes the
     // frame straight into the page-locked staging buffer across the fabric (no DMA)
     const bool zc = getenv("MFX_SAMPLE_ZEROCOPY") && atoi(getenv("MFX_SAMPLE_ZEROCOPY")) != 0;
     void* stage_dev = nullptr;  // the staging buffer's device address (zero-copy)
     if (zc) HIPCHECK(hipHostGetDevicePointer(&stage_dev, rb.stage, 0));
-    if (ncs == 2 && !rb.sample_copy2) HIPCHECK(rb.sample_copy2.create());
     size_t off[kStageChunks] = {0}, len[kStageChunks] = {0};
     ResolveSplit S;
     S.nbands = nb;
@@ -240,7 +184,7 @@ static int sample_banded(mfx_ctx* c, int32_t spp, double* frame) {
         const int64_t p0 = (int64_t)tx0 * 8 * H, p1 = (int64_t)std::min(W, (tx0 + ntx) * 8) * H;
         off[k] = (size_t)p0 * pxb;
         len[k] = (size_t)(p1 - p0) * pxb;
-        hipStream_t cs = (ncs == 2 && (k & 1)) ? rb.sample_copy2 : rb.copy_stream;
+        hipStream_t cs = rb.copy_stream;
         auto mean = [&](double* out, hipStream_t st) {
             return rgb ? mfx_launch_mean_rgb(c->d_accum, c->npix, (double)spp, out, st, p0, p1)
                        : mfx_launch_mean(c->d_accum, c->npix, (double)spp, out, st, p0, p1);

@@ -242,12 +242,19 @@ hipError_t mfx_wf_tile_check(const TileCheckParams& C, hipStream_t st);
 #ifndef WF_NTOP_MAX
 #define WF_NTOP_MAX MFX_TOP_NODES  // top BVH nodes a trace kernel may keep in LDS (mfx_scene.cpp numbers them first)
 #endif
-// resident blocks per CU of k_extend / k_shadow with `stack_lds` stack entries per lane (spill: the
-// SpillStack instance), ntop top BVH nodes and min(ninst, WF_INST_LDS) instance records in LDS
-// (and nslot slots' test prefixes); fp16: the context walks FP16 nodes (WfParams::nodes_h set), which
-// selects the flat scene kind's per-format instance, the one its launches run
-hipError_t mfx_wf_kernel_occupancy(bool shadow, int stack_lds, bool spill, int ntop, int ninst, int* blocks_per_cu,
-                                   int nslot, bool fp16);
+// What a block of k_extend or k_shadow keeps in LDS, and what of the kernel's instance goes with it: the
+// shape an occupancy query asks about and a launch runs
+struct WfLdsShape {
+    bool shadow;    // k_shadow (else k_extend)
+    bool spill;     // the SpillStack instance: stack entries past stack_lds in the global column
+    bool fp16;      // the context walks FP16 nodes (WfParams::nodes_h set): the flat scene kind's per-format instance
+    int stack_lds;  // traversal stack entries per lane
+    int ntop;       // top BVH nodes
+    int ninst;      // the scene's instances (0: a flat scene), min(ninst, WF_INST_LDS) records of them in LDS
+    int nslot;      // slots' test prefixes
+};
+// resident blocks per CU of the kernel instance that holds shape s
+hipError_t mfx_wf_kernel_occupancy(const WfLdsShape& s, int* blocks_per_cu);
 // resident blocks per CU of k_camera (camera-ray packets)
 hipError_t mfx_cam_occupancy(int stack_size, int* blocks_per_cu);
 // a ray queue's arrays (MFX_RAY_QUEUE): entries in the pool's shard ranges, counts per shard

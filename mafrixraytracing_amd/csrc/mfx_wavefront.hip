@@ -27,6 +27,7 @@
 
 #include <algorithm>
 #include <type_traits>
+#include <utility>
 
 #include "mfx_device.h"
 #include "mfx_trace_common.h"
@@ -1431,31 +1432,56 @@ __global__ void __launch_bounds__(256) k_resolve(WfParams P) {
 // ------------------------------------------------------------------------------------------------
 // top nodes, instances, slots, stacks, pending-ray lists, block reduction scratch (64 B) and, for
 // k_shadow, the shade lists
-static size_t wf_lds_bytes(int stack_size, bool shadow, int ntop, int ninst, int nslot = 0) {
-    const size_t stacks = (size_t)ntop * sizeof(MfxNode) + (size_t)ninst * sizeof(MfxInstance) + (size_t)nslot * 80 +
-                          (size_t)4 * stack_size * 64 * sizeof(int);
-    return shadow ? stacks + 4 * PendShd::BYTES + 64 + 4 * 2 * WF_SHD_LIST * sizeof(int) + sizeof(MfxLight) + sizeof(ShdPtrs) +
-                        sizeof(PixParams) + sizeof(SceneRefs)
-                  : stacks + 4 * WF_EXT_PEND * sizeof(int) + 64;
+static size_t wf_lds_bytes(const WfLdsShape& s) {
+    const size_t stacks = (size_t)s.ntop * sizeof(MfxNode) + (size_t)std::min(s.ninst, WF_INST_LDS) * sizeof(MfxInstance) +
+                          (size_t)s.nslot * 80 + (size_t)4 * s.stack_lds * 64 * sizeof(int);
+    return s.shadow ? stacks + 4 * PendShd::BYTES + 64 + 4 * 2 * WF_SHD_LIST * sizeof(int) + sizeof(MfxLight) + sizeof(ShdPtrs) +
+                          sizeof(PixParams) + sizeof(SceneRefs)
+                    : stacks + 4 * WF_EXT_PEND * sizeof(int) + 64;
 }
 
-// Blocks per CU the LDS allows. gfx950 allocates LDS in 1,280-byte granules out of 160 KB per CU;
-// hipOccupancyMaxActiveBlocksPerMultiprocessor counts finer granules, so near a boundary it
-// reports one block more than fits (measured: k_shadow at 53,952 B per block runs 2 blocks per CU
-// where the API says 3, a 10 % loss).
-static int wf_lds_blocks(size_t bytes) {
-    const size_t g = 1280, per_cu = 160 * 1024;
-    return (int)(per_cu / ((bytes + g - 1) / g * g));
+// An instance of a trace kernel: the kernels' template parameters as run-time values. k_extend takes
+// every field but waves, k_shadow every field but start, k_camera stats and list; a key holds the
+// fields its kernel does not take at the values the *_built rules below name.
+struct WfKey {
+    bool stats, spill;
+    int sk;  // WF_SK_*
+    bool queue, start;
+    int list;   // WF_LIST_*
+    int nf;     // MFX_NF_*
+    int waves;  // k_shadow's build: 3 or 4 waves per SIMD
+};
+// a key's number, and the key of a number: the one place a field passes between run time and compile time
+constexpr int WF_KEYS = 2 * 2 * 3 * 2 * 2 * 3 * 3 * 2;
+static constexpr int key_index(const WfKey& k) {
+    return ((((((k.stats * 2 + k.spill) * 3 + k.sk) * 2 + k.queue) * 2 + k.start) * 3 + k.list) * 3 + k.nf) * 2 + (k.waves - 3);
+}
+static constexpr WfKey key_at(int i) {
+    WfKey k{};
+    k.waves = 3 + i % 2, i /= 2;
+    k.nf = i % 3, i /= 3;
+    k.list = i % 3, i /= 3;
+    k.start = i % 2, i /= 2;
+    k.queue = i % 2, i /= 2;
+    k.sk = i % 3, i /= 3;
+    k.spill = i % 2, i /= 2;
+    k.stats = i;
+    return k;
 }
 
-// the scene kind a kernel instance is built for (k_extend / k_shadow SK)
+// The rules a key is derived by, each in its one function.
+// the scene kind (k_extend / k_shadow SK)
 static int scene_kind(bool inst, int nslot) { return inst ? WF_SK_INST : (nslot > 0 ? WF_SK_SLDS : WF_SK_FLAT); }
-
-// The node format of the instance launched for scene kind SK (k_extend / k_shadow NF): a flat scene's
-// in-place and queue instances without STATS, START or LIST are built per format, FP16 nodes when the
-// context has them (fp16: WfParams::nodes_h), FP32 under MFX_NODE_F32; every other instance takes either
-template <int SK, bool STATS, bool START, int LIST>
-static constexpr bool wf_nf_fixed() { return SK == WF_SK_FLAT && !STATS && !START && !LIST; }
+// the list kind of a trace: none, the adaptive sampler's tile list, or one with per-tile counts
+// (mfx_sample_adaptive_resume)
+static int list_kind(int ntiles, const int32_t* tile_n) {
+    return ntiles > 0 ? (tile_n ? WF_LIST_TILE_N : WF_LIST_TILES) : WF_LIST_NONE;
+}
+// Which instances are built per node format (k_extend / k_shadow NF): a flat scene's in-place and queue
+// instances without STATS, START or LIST, so neither format's loop holds the other's registers; every
+// other instance takes either format (MFX_NF_ANY)
+static constexpr bool wf_nf_fixed(const WfKey& k) { return k.sk == WF_SK_FLAT && !k.stats && !k.start && !k.list; }
+// the node format a context runs: FP16 nodes when it has them (WfParams::nodes_h), FP32 under MFX_NODE_F32
 static bool wf_fp16(const WfParams& P) {
 #if MFX_NODE_F16
     return P.nodes_h != nullptr;
@@ -1463,116 +1489,75 @@ static bool wf_fp16(const WfParams& P) {
     return false;
 #endif
 }
+// k_shadow's build: compiled for 3 waves per SIMD (up to 168 VGPRs) when its LDS allows no more blocks anyway
+static int shadow_build(int shadow_waves) { return shadow_waves == 3 ? 3 : 4; }
 
-// the instance a launch of this shape runs (the 4-wave k_shadow: ctx_setup chooses the 3-wave build from
-// its answer; k_extend's bounce instance, or for the kinds without per-format instances the START
-// one: a superset of the bounce instance's code)
-template <int SK, int NF>
-static const void* occ_kernel(bool shadow, bool spill) {
-    if (shadow)
-        return spill ? (const void*)k_shadow<false, true, 4, SK, false, WF_LIST_NONE, NF>
-                     : (const void*)k_shadow<false, false, 4, SK, false, WF_LIST_NONE, NF>;
-    constexpr bool START = NF == MFX_NF_ANY;
-    return spill ? (const void*)k_extend<false, true, SK, false, START, WF_LIST_NONE, NF>
-                 : (const void*)k_extend<false, false, SK, false, START, WF_LIST_NONE, NF>;
+// The instances the code object holds: a key outside these rules names no kernel.
+static constexpr bool nf_built(const WfKey& k) {
+    return wf_nf_fixed(k) ? k.nf == MFX_NF_F32 || (MFX_NODE_F16 && k.nf == MFX_NF_H) : k.nf == MFX_NF_ANY;
 }
+// (a queue's entries are never FREE slots; only the iteration that starts paths maps them through a list)
+static constexpr bool extend_built(const WfKey& k) {
+    return k.waves == 4 && nf_built(k) && (k.queue ? !k.start && !k.list : k.start || !k.list);
+}
+static constexpr bool shadow_built(const WfKey& k) { return !k.start && nf_built(k); }
+static constexpr bool camera_built(const WfKey& k) {
+    return !k.spill && k.sk == WF_SK_FLAT && !k.queue && k.start && k.nf == MFX_NF_ANY && k.waves == 4;
+}
+static constexpr int built_count(bool (*built)(const WfKey&)) {
+    int n = 0;
+    for (int i = 0; i < WF_KEYS; ++i) n += built(key_at(i));
+    return n;
+}
+static_assert(built_count(extend_built) == (MFX_NODE_F16 ? 64 : 60) && built_count(shadow_built) == (MFX_NODE_F16 ? 152 : 144) &&
+                  built_count(camera_built) == 6,
+              "a new instance is a decision: every one is a kernel to compile, and an occupancy to ask about");
 
-hipError_t mfx_wf_kernel_occupancy(bool shadow, int stack_lds, bool spill, int ntop, int ninst, int* blocks_per_cu,
-                                   int nslot, bool fp16) {
-    const size_t lds = wf_lds_bytes(stack_lds, shadow, ntop, std::min(ninst, WF_INST_LDS), nslot);
-    const int sk = scene_kind(ninst > 0, nslot);
-    const void* k = sk == WF_SK_INST ? occ_kernel<WF_SK_INST, MFX_NF_ANY>(shadow, spill)
-                    : sk == WF_SK_SLDS ? occ_kernel<WF_SK_SLDS, MFX_NF_ANY>(shadow, spill)
-#if MFX_NODE_F16
-                    : fp16 ? occ_kernel<WF_SK_FLAT, MFX_NF_H>(shadow, spill)
-#endif
-                           : occ_kernel<WF_SK_FLAT, MFX_NF_F32>(shadow, spill);
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k, 256, lds);
-    *blocks_per_cu = std::min(*blocks_per_cu, wf_lds_blocks(lds));
+enum { WF_K_EXTEND, WF_K_SHADOW, WF_K_CAMERA };
+template <int KERNEL, int I>
+static const void* instance_at() {
+    constexpr WfKey k = key_at(I);
+    if constexpr (KERNEL == WF_K_EXTEND && extend_built(k))
+        return (const void*)k_extend<k.stats, k.spill, k.sk, k.queue, k.start, k.list, k.nf>;
+    else if constexpr (KERNEL == WF_K_SHADOW && shadow_built(k))
+        return (const void*)k_shadow<k.stats, k.spill, k.waves, k.sk, k.queue, k.list, k.nf>;
+    else if constexpr (KERNEL == WF_K_CAMERA && camera_built(k))
+        return (const void*)k_camera<k.stats, k.list>;
+    else
+        return nullptr;
+}
+template <int KERNEL, size_t... I>
+static const void* instance(const WfKey& k, std::index_sequence<I...>) {
+    static const void* const table[WF_KEYS] = {instance_at<KERNEL, (int)I>()...};
+    return table[key_index(k)];
+}
+// a key's kernel (null: not built)
+static const void* extend_kernel(const WfKey& k) { return instance<WF_K_EXTEND>(k, std::make_index_sequence<WF_KEYS>{}); }
+static const void* shadow_kernel(const WfKey& k) { return instance<WF_K_SHADOW>(k, std::make_index_sequence<WF_KEYS>{}); }
+static const void* camera_kernel(const WfKey& k) { return instance<WF_K_CAMERA>(k, std::make_index_sequence<WF_KEYS>{}); }
+
+// the key of k_extend or k_shadow holding shape s
+static WfKey shape_key(const WfLdsShape& s, bool stats, bool queue, bool start, int list, int waves) {
+    WfKey k{stats, s.spill, scene_kind(s.ninst > 0, s.nslot), queue, start, list, MFX_NF_ANY, waves};
+    if (wf_nf_fixed(k)) k.nf = s.fp16 ? MFX_NF_H : MFX_NF_F32;
+    return k;
+}
+static WfKey camera_key(bool stats, int list) { return {stats, false, WF_SK_FLAT, false, true, list, MFX_NF_ANY, 4}; }
+
+// The query asks the instance a launch of the shape runs, with two deliberate differences: the 4-wave
+// k_shadow whatever the context's build (scene_shapes chooses the 3-wave build from the answer), and, for
+// the scene kinds without per-format instances, k_extend's START instance instead of the bounce one (a
+// superset of the bounce instance's code).
+hipError_t mfx_wf_kernel_occupancy(const WfLdsShape& s, int* blocks_per_cu) {
+    WfKey k = shape_key(s, false, false, false, WF_LIST_NONE, 4);
+    if (!s.shadow && !wf_nf_fixed(k)) k.start = true;
+    const size_t lds = wf_lds_bytes(s);
+    const hipError_t e =
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, s.shadow ? shadow_kernel(k) : extend_kernel(k), 256, lds);
+    // (the API counts finer LDS granules than the hardware allocates: measured, k_shadow at 53,952 B per
+    // block runs 2 blocks per CU where it says 3, a 10 % loss)
+    *blocks_per_cu = std::min(*blocks_per_cu, mfx_lds_blocks(lds));
     return e;
-}
-
-template <bool SPILL, int SK, bool Q, bool START = false, int LIST = WF_LIST_NONE>
-static void launch_extend_q(const WfParams& P, int grid, bool stats, hipStream_t st, size_t lds) {
-    if (stats) {
-        hipLaunchKernelGGL((k_extend<true, SPILL, SK, Q, START, LIST>), dim3(grid), dim3(256), lds, st, P);
-    } else if constexpr (wf_nf_fixed<SK, false, START, LIST>()) {
-#if MFX_NODE_F16
-        if (wf_fp16(P))
-            hipLaunchKernelGGL((k_extend<false, SPILL, SK, Q, START, LIST, MFX_NF_H>), dim3(grid), dim3(256), lds, st, P);
-        else
-#endif
-            hipLaunchKernelGGL((k_extend<false, SPILL, SK, Q, START, LIST, MFX_NF_F32>), dim3(grid), dim3(256), lds, st, P);
-    } else {
-        hipLaunchKernelGGL((k_extend<false, SPILL, SK, Q, START, LIST>), dim3(grid), dim3(256), lds, st, P);
-    }
-}
-template <bool SPILL, int SK>
-static void launch_extend(const WfParams& P, int grid, bool stats, hipStream_t st, size_t lds) {
-    if (P.qcount) launch_extend_q<SPILL, SK, true>(P, grid, stats, st, lds);
-    else if (P.start && P.ntiles > 0 && P.tile_n) launch_extend_q<SPILL, SK, false, true, WF_LIST_TILE_N>(P, grid, stats, st, lds);
-    else if (P.start && P.ntiles > 0) launch_extend_q<SPILL, SK, false, true, WF_LIST_TILES>(P, grid, stats, st, lds);
-    else if (P.start) launch_extend_q<SPILL, SK, false, true>(P, grid, stats, st, lds);
-    else launch_extend_q<SPILL, SK, false>(P, grid, stats, st, lds);
-}
-template <bool SPILL, int WAVES, int SK, bool Q>
-static void launch_shadow_q(const WfParams& P, int grid, bool stats, hipStream_t st, size_t lds) {
-    if (P.ntiles > 0 && P.tile_n) {  // a listed trace with per-tile counts (mfx_sample_adaptive_resume)
-        if (stats)
-            hipLaunchKernelGGL((k_shadow<true, SPILL, WAVES, SK, Q, WF_LIST_TILE_N>), dim3(grid), dim3(256), lds, st, P);
-        else
-            hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q, WF_LIST_TILE_N>), dim3(grid), dim3(256), lds, st, P);
-        return;
-    }
-    if (P.ntiles > 0) {  // a listed trace (adaptive sampling)
-        if (stats)
-            hipLaunchKernelGGL((k_shadow<true, SPILL, WAVES, SK, Q, WF_LIST_TILES>), dim3(grid), dim3(256), lds, st, P);
-        else
-            hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q, WF_LIST_TILES>), dim3(grid), dim3(256), lds, st, P);
-        return;
-    }
-    if (stats) {
-        hipLaunchKernelGGL((k_shadow<true, SPILL, WAVES, SK, Q>), dim3(grid), dim3(256), lds, st, P);
-    } else if constexpr (wf_nf_fixed<SK, false, false, WF_LIST_NONE>()) {
-#if MFX_NODE_F16
-        if (wf_fp16(P))
-            hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q, WF_LIST_NONE, MFX_NF_H>), dim3(grid), dim3(256), lds, st, P);
-        else
-#endif
-            hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q, WF_LIST_NONE, MFX_NF_F32>), dim3(grid), dim3(256), lds, st, P);
-    } else {
-        hipLaunchKernelGGL((k_shadow<false, SPILL, WAVES, SK, Q>), dim3(grid), dim3(256), lds, st, P);
-    }
-}
-// MFX_SHADOW_Q_WAVES=3 (an A/B knob, VERDICT r05 Next #7): the queue instances of a 4-wave k_shadow
-// run the 3-wave build instead (no scratch spill; 3 of the grid's 4 blocks per CU)
-static int shadow_q_waves() {
-    static const int w = getenv("MFX_SHADOW_Q_WAVES") ? atoi(getenv("MFX_SHADOW_Q_WAVES")) : 0;
-    return w;
-}
-template <bool SPILL, int WAVES, int SK>
-static void launch_shadow(const WfParams& P, int grid, bool stats, hipStream_t st, size_t lds) {
-    if (P.qslot || P.ncount) {
-        if (WAVES == 4 && shadow_q_waves() == 3) launch_shadow_q<SPILL, 3, SK, true>(P, grid / 4 * 3, stats, st, lds);
-        else launch_shadow_q<SPILL, WAVES, SK, true>(P, grid, stats, st, lds);
-    } else {
-        launch_shadow_q<SPILL, WAVES, SK, false>(P, grid, stats, st, lds);
-    }
-}
-template <int SK>
-static void launch_shadow_sk(const WfParams& P, int grid, bool stats, hipStream_t st, size_t lds) {
-    // k_shadow is compiled for 3 waves per SIMD (up to 168 VGPRs) when its LDS allows no more blocks anyway
-    const bool spill = P.stack_lds_shd < P.stack_size, w3 = P.shadow_waves == 3;
-    if (spill && w3) launch_shadow<true, 3, SK>(P, grid, stats, st, lds);
-    else if (spill) launch_shadow<true, 4, SK>(P, grid, stats, st, lds);
-    else if (w3) launch_shadow<false, 3, SK>(P, grid, stats, st, lds);
-    else launch_shadow<false, 4, SK>(P, grid, stats, st, lds);
-}
-template <int SK>
-static void launch_extend_sk(const WfParams& P, int grid, bool stats, hipStream_t st, size_t lds) {
-    // each kernel keeps its own share of the traversal stack in LDS (the rest spills)
-    if (P.stack_lds_ext < P.stack_size) launch_extend<true, SK>(P, grid, stats, st, lds);
-    else launch_extend<false, SK>(P, grid, stats, st, lds);
 }
 
 static size_t cam_lds_bytes(int stack_size) {
@@ -1580,48 +1565,45 @@ static size_t cam_lds_bytes(int stack_size) {
 }
 
 hipError_t mfx_cam_occupancy(int stack_size, int* blocks_per_cu) {
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (const void*)k_camera<false>, 256,
-                                                                      cam_lds_bytes(stack_size));
-    return e;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, camera_kernel(camera_key(false, WF_LIST_NONE)), 256,
+                                                        cam_lds_bytes(stack_size));
+}
+
+// a launch's error is left to the hipGetLastError that follows the iteration's launches
+static void launch(const void* kernel, int grid, size_t lds, hipStream_t st, const WfParams& P) {
+    void* args[] = {const_cast<WfParams*>(&P)};
+    (void)hipLaunchKernel(kernel, dim3(grid), dim3(256), args, lds, st);
+}
+
+// what each trace kernel of this trace keeps in LDS (each its own share of the traversal stack; the rest spills)
+static WfLdsShape lds_shape(const WfParams& P, bool shadow) {
+    const int stack_lds = shadow ? P.stack_lds_shd : P.stack_lds_ext;
+    return {shadow, stack_lds < P.stack_size, wf_fp16(P), stack_lds, shadow ? P.ntop_shd : P.ntop_ext,
+            P.inst ? P.ninst_lds : 0, shadow ? P.nslot_shd : P.nslot_ext};
 }
 
 static hipError_t launch_iteration(const WfParams& P, int ext_grid, int shd_grid, bool stats, hipStream_t st,
-                                   hipEvent_t* ev, size_t lds_e, size_t lds_s) {
-    const bool inst = P.inst != nullptr;
-    if (!inst && P.start && P.cam_grid > 0) {  // camera rays as packets
-        const size_t lds_c = cam_lds_bytes(P.stack_size);
-        if (P.ntiles > 0 && P.tile_n) {  // a listed trace with per-tile counts (mfx_sample_adaptive_resume)
-            if (stats) hipLaunchKernelGGL((k_camera<true, WF_LIST_TILE_N>), dim3(P.cam_grid), dim3(256), lds_c, st, P);
-            else hipLaunchKernelGGL((k_camera<false, WF_LIST_TILE_N>), dim3(P.cam_grid), dim3(256), lds_c, st, P);
-        } else if (P.ntiles > 0) {  // a listed trace (adaptive sampling)
-            if (stats) hipLaunchKernelGGL((k_camera<true, WF_LIST_TILES>), dim3(P.cam_grid), dim3(256), lds_c, st, P);
-            else hipLaunchKernelGGL((k_camera<false, WF_LIST_TILES>), dim3(P.cam_grid), dim3(256), lds_c, st, P);
-        } else if (stats) hipLaunchKernelGGL(k_camera<true>, dim3(P.cam_grid), dim3(256), lds_c, st, P);
-        else hipLaunchKernelGGL(k_camera<false>, dim3(P.cam_grid), dim3(256), lds_c, st, P);
+                                   hipEvent_t* ev) {
+    const int list = list_kind(P.ntiles, P.tile_n);
+    if (!P.inst && P.start && P.cam_grid > 0) {  // camera rays as packets
+        launch(camera_kernel(camera_key(stats, list)), P.cam_grid, cam_lds_bytes(P.stack_size), st, P);
     } else {
-        switch (scene_kind(inst, P.nslot_ext)) {
-            case WF_SK_INST: launch_extend_sk<WF_SK_INST>(P, ext_grid, stats, st, lds_e); break;
-            case WF_SK_SLDS: launch_extend_sk<WF_SK_SLDS>(P, ext_grid, stats, st, lds_e); break;
-            default: launch_extend_sk<WF_SK_FLAT>(P, ext_grid, stats, st, lds_e);
-        }
+        const WfLdsShape s = lds_shape(P, false);
+        const bool queue = P.qcount != nullptr, start = !queue && P.start;
+        launch(extend_kernel(shape_key(s, stats, queue, start, start ? list : WF_LIST_NONE, 4)), ext_grid, wf_lds_bytes(s), st, P);
     }
     if (ev) {  // between the two kernels (per-stage timing); null: not recorded
         const hipError_t e = hipEventRecord(ev[0], st);
         if (e != hipSuccess) return e;
     }
-    switch (scene_kind(inst, P.nslot_shd)) {
-        case WF_SK_INST: launch_shadow_sk<WF_SK_INST>(P, shd_grid, stats, st, lds_s); break;
-        case WF_SK_SLDS: launch_shadow_sk<WF_SK_SLDS>(P, shd_grid, stats, st, lds_s); break;
-        default: launch_shadow_sk<WF_SK_FLAT>(P, shd_grid, stats, st, lds_s);
-    }
+    const WfLdsShape s = lds_shape(P, true);
+    const bool queue = P.qslot || P.ncount;
+    launch(shadow_kernel(shape_key(s, stats, queue, false, list, shadow_build(P.shadow_waves))), shd_grid, wf_lds_bytes(s), st, P);
     return hipSuccess;
 }
 
 hipError_t mfx_wf_iteration(const WfParams& P, int ext_grid, int shd_grid, bool stats, hipStream_t st,
                             hipEvent_t* ev) {
-    const int ni = P.inst ? P.ninst_lds : 0;
-    const size_t lds_e = wf_lds_bytes(P.stack_lds_ext, false, P.ntop_ext, ni, P.nslot_ext);
-    const size_t lds_s = wf_lds_bytes(P.stack_lds_shd, true, P.ntop_shd, ni, P.nslot_shd);
     // the chunk heads and, beside them (WF_CTL_Q0 / WF_CTL_Q1), the next queue's shard counts
     unsigned long long* z = P.ctl;
     size_t nz = WF_NCTL;
@@ -1631,7 +1613,7 @@ hipError_t mfx_wf_iteration(const WfParams& P, int ext_grid, int shd_grid, bool 
     }
     hipError_t e = hipMemsetAsync(z, 0, nz * sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
-    e = launch_iteration(P, ext_grid, shd_grid, stats, st, ev, lds_e, lds_s);
+    e = launch_iteration(P, ext_grid, shd_grid, stats, st, ev);
     if (e != hipSuccess) return e;
     return hipGetLastError();
 }
