@@ -168,7 +168,12 @@ typedef struct mfx_ctx mfx_ctx;
 /* ---- lifetime ------------------------------------------------------------------------- */
 
 /* Replaces `new Scene(state)` (Scene.fs:298-313): builds the reference's heap BVH leaf grouping
- * (BvhNode.fs:24-61), the GPU traversal BVH over it, uploads everything to HBM.            */
+ * (BvhNode.fs:24-61), the GPU traversal BVH over it, uploads everything to HBM.
+ * MFX_E_INVALID (before any BVH is built, on the host): a NaN or +-inf in what a primitive's kind reads
+ * (a triangle's three corners, a rect's four, a sphere's centre and p[1][0]; the rest of p is not looked
+ * at), in the light or in the camera (as mfx_set_camera: direction, fov and aspect count with
+ * derived == 0, topleft, right and down otherwise); coordinates whose magnitude plus a ray's length
+ * exceeds 2^126 (DESIGN.md §3 "Coordinate range"). The message names the first offender.          */
 int mfx_create(const mfx_scene_desc* scene, const mfx_options* opt, mfx_ctx** out);
 void mfx_destroy(mfx_ctx* ctx);
 /* mfx_create for an instanced scene: scene->prims are the template primitives, `instances`

@@ -84,6 +84,8 @@ __device__ __forceinline__ float box_area(float lx, float ly, float lz, float hx
 }
 
 // bin of a centroid coordinate: SahBuilder::build's (int)((c - lo) / ext * NB), clamped
+// (the cast never sees a NaN: mfx_build_scene refuses non-finite coordinates and extents past 2^126, so
+// c, lo and ext are finite, ext > 0 where this is called, and the quotient lies in [0, 1])
 __device__ __forceinline__ int bin_of(float c, float lo, float ext) {
     int k = (int)((c - lo) / ext * NB);
     return min(NB - 1, max(0, k));

@@ -75,6 +75,44 @@ bool plan_instances(const mfx_scene_desc* d0, const mfx_instance* instances, int
     return true;
 }
 
+bool all_finite(const double* v, int k) {
+    for (int i = 0; i < k; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+// The light and the create-time camera hold no NaN or inf (mfx_set_camera's rule for a later camera:
+// direction, fov and aspect count without `derived`, topleft, right and down with it). The primitives'
+// values are checked where their records are made (make_prim_records), before this.
+bool validate_light_camera(const mfx_scene_desc& d, std::string& err) {
+    for (int k = 0; k < 4; ++k)
+        if (!all_finite(d.light.p[k], 3)) {
+            err = "light corner " + std::to_string(k) + " is not finite";
+            return false;
+        }
+    const mfx_pinhole& c = d.camera;
+    const char* bad = !all_finite(d.light.normal, 3)      ? "light normal"
+                      : !all_finite(d.light.intensity, 3) ? "light intensity"
+                      : !all_finite(c.position, 3)        ? "camera position"
+                      : c.derived ? (!all_finite(c.topleft, 3) ? "camera topleft"
+                                     : !all_finite(c.right, 3) ? "camera right"
+                                     : !all_finite(c.down, 3)  ? "camera down"
+                                                               : nullptr)
+                                  : (!all_finite(c.direction, 3) ? "camera direction"
+                                     : !std::isfinite(c.fov)     ? "camera fov"
+                                     : !std::isfinite(c.aspect)  ? "camera aspect"
+                                                                 : nullptr);
+    if (bad) err = std::string(bad) + " is not finite";
+    return !bad;
+}
+
+// The largest R + T (Extent, below; a template frame: R + |off| + T) the FP32 builders hold: 2^126.
+// A plane is round_up(x + eps) with |x| <= R and eps = (float)ldexp(R + T, -19), so at most
+// (R + T)(1 + 2^-18) in magnitude; a centroid's sum lo + hi and a centroid box's extent hi - lo are at
+// most twice that plus a rounding, below 2^127 (1 + 2^-16) < FLT_MAX: every one finite.
+const double EXTENT_MAX = 0x1p126;
+const char* const TOO_FAR = "scene extent too large: R + T (the coordinates' magnitude plus a ray's length) must not exceed 2^126";
+
 bool validate_desc(const mfx_scene_desc* d, std::string& err) {
     if (!d || !d->prims || d->nprims < 1) {
         err = "scene has no primitives (Bvh.Build on an empty array throws, BvhNode.fs:26)";
@@ -147,6 +185,19 @@ bool make_prim_records(const mfx_scene_desc& d, PrimRecords& r, std::string& err
         const mfx_prim& p = d.prims[i];
         if (p.material < 0 || p.material >= d.nmat) {
             err = "primitive " + std::to_string(i) + " has material index out of range";
+            return false;
+        }
+        // what the kind reads must be finite (a triangle's p[3] is not read, nor a sphere's p[1][1] on):
+        // per primitive the material, then the kind, then its values in order
+        const int nv = p.kind == MFX_PRIM_TRIANGLE ? 3 : p.kind == MFX_PRIM_RECT ? 4 : p.kind == MFX_PRIM_SPHERE ? 1 : 0;
+        for (int v = 0; v < nv; ++v)
+            if (!all_finite(p.p[v], 3)) {
+                err = "primitive " + std::to_string(i) + (p.kind == MFX_PRIM_SPHERE ? ": centre" : ": corner " + std::to_string(v)) +
+                      " is not finite";
+                return false;
+            }
+        if (p.kind == MFX_PRIM_SPHERE && !std::isfinite(p.p[1][0])) {
+            err = "primitive " + std::to_string(i) + ": radius is not finite";
             return false;
         }
         r.slot_of[i] = (int)r.pslots.size();
@@ -644,7 +695,12 @@ bool build_two_level(const mfx_prim* tprims, const InstancePlan& plan, const Ext
     double offmax = 0;
     for (const Use& u : uses)
         for (int a = 0; a < 3; ++a) offmax = std::max(offmax, std::fabs(u.off[a]));
-    // template frame: coordinates and ray origins up to R + |off| in magnitude
+    // template frame: coordinates and ray origins up to R + |off| in magnitude (mfx_build_scene refuses
+    // this before any BVH work; the check stays beside the eps it guards)
+    if (!(ext.R + offmax + ext.T <= EXTENT_MAX)) {
+        err = TOO_FAR;
+        return false;
+    }
     const float eps_t = (float)std::ldexp(ext.R + offmax + ext.T, -19);
     s.inst_offmax = offmax;
     s.eps_templates = eps_t;
@@ -846,10 +902,18 @@ bool mfx_build_scene(const mfx_scene_desc* d0, MfxHostScene& s, std::string& err
 
     PrimRecords rec;
     if (!make_prim_records(*d, rec, err)) return false;
+    if (!validate_light_camera(*d, err)) return false;
+    const Extent ext = scene_extent(*d, rec.pb, s);
+    double offmax = 0;  // a template frame's coordinates reach R + |off| (build_two_level)
+    for (const Use& u : plan.uses)
+        for (int a = 0; a < 3; ++a) offmax = std::max(offmax, std::fabs(u.off[a]));
+    if (!(ext.R + offmax + ext.T <= EXTENT_MAX)) {  // before either BVH is built
+        err = TOO_FAR;
+        return false;
+    }
     RefGrouping grp;
     if (!group_reference_leaves(rec, s, grp, err)) return false;
     set_camera_light(*d, s);
-    const Extent ext = scene_extent(*d, rec.pb, s);
     s.eps = (float)std::ldexp(ext.R + ext.T, -19);
     s.inst_offmax = 0.0;
     s.eps_templates = 0.f;

@@ -196,6 +196,8 @@ struct SahBuilder {
             float wb[NB] = {0};
             int cnt[NB] = {0};
             for (int k = 0; k < NB; ++k) bb[k] = FBox::empty();
+            // the cast never sees a NaN: mfx_build_scene refuses non-finite coordinates and extents past
+            // 2^126, so centroids and ext are finite, ext > 0 here, and the quotient lies in [0, 1]
             for (int i = b; i < e; ++i) {
                 int k = (int)((cent[3 * ids[i] + a] - cbox.lo[a]) / ext * NB);
                 k = std::min(NB - 1, std::max(0, k));

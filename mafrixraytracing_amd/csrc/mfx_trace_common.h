@@ -662,7 +662,7 @@ __device__ __forceinline__ float f_round_up(double x) {
     return f;
 }
 // a node step's distance limit: x rounded up, at most FLT_MAX, so a box whose entry distance
-// overflows to +inf (an empty child's +inf planes, mfx_api.cpp node_to_half) is never entered
+// overflows to +inf (an empty child's +inf planes, mfx_half.h node_to_half) is never entered
 __device__ __forceinline__ float f_tlim(double x) { return fminf(f_round_up(x), 3.402823466e38f); }
 
 // FP32 ray for the cluster-BVH slab tests

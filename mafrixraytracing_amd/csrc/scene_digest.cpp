@@ -4,11 +4,22 @@
 // a machine without a GPU (tests/test_gpu_build.py pins the GPU-built image to the host-built one).
 // Scenes come from an integer hash, so the inputs are the same bits under every standard library.
 // The camera is left out: it goes through std::tan, which another libm may round differently.
+// After those: half_dir (mfx_half.h) against a search over the table of all finite halves, the FP16 node
+// image of every scene above (digest, and how many planes are +-inf, subnormal or not rounded outward),
+// and soup_600 scaled and moved past and below the binary16 range.
+#include <algorithm>
+#include <cfloat>
 #include <cinttypes>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
+#include <string>
+#include <utility>
+#include <vector>
 
 #include "mfx_build.h"
+#include "mfx_half.h"
 #include "mfx_scene.h"
 
 // the host build never reaches the GPU entry point
@@ -161,6 +172,97 @@ std::vector<mfx_instance> two_level_entries() {
             entry(0, 40, 1.1, 2.2, -3.3),     entry(40, 30, -2.5, -0.125, 1.0)};
 }
 
+// ---- the FP16 node image (mfx_half.h): its rounding against a table, its bytes, its planes ----------
+double half_value(uint16_t h) {  // finite halves only
+    const int e = (h >> 10) & 31, m = h & 1023;
+    const double v = e == 0 ? std::ldexp((double)m, -24) : std::ldexp((double)(1024 + m), e - 25);
+    return (h & 0x8000) ? -v : v;
+}
+
+// half_dir by search: the table of the 31,744 finite non-negative halves in ascending order is indexed by
+// their bits; away from zero the least entry >= |x| (none: inf), towards zero the greatest entry <= |x|
+uint16_t half_dir_by_search(const std::vector<double>& table, float x, bool up) {
+    if (std::isinf(x)) return x > 0 ? 0x7c00 : 0xfc00;
+    const bool neg = x < 0;
+    const double ax = std::fabs((double)x);
+    int i;
+    if (up != neg) {
+        i = (int)(std::lower_bound(table.begin(), table.end(), ax) - table.begin());  // 31744 == 0x7c00: inf
+    } else {
+        i = (int)(std::upper_bound(table.begin(), table.end(), ax) - table.begin()) - 1;
+    }
+    return (uint16_t)(i | (neg ? 0x8000 : 0));
+}
+
+float float_of_bits(uint32_t u) {
+    float f;
+    std::memcpy(&f, &u, sizeof(f));
+    return f;
+}
+
+// every half and its two FP32 neighbours, 2,000,000 FP32 bit patterns and a few extremes, both signs,
+// both directions
+void print_half_selfcheck() {
+    std::vector<double> table(0x7c00);
+    for (int h = 0; h < 0x7c00; ++h) table[h] = half_value((uint16_t)h);
+    int64_t checks = 0, wrong = 0;
+    const auto check = [&](float x) {
+        if (std::isnan(x)) return;
+        for (const float v : {x, -x})
+            for (const bool up : {false, true}) {
+                ++checks;
+                if (mfx_half::half_dir(v, up) != half_dir_by_search(table, v, up)) ++wrong;
+            }
+    };
+    for (int h = 0; h < 0x7c00; ++h) {
+        const float f = (float)table[h];
+        check(f);
+        check(std::nextafter(f, -FLT_MAX));
+        check(std::nextafter(f, FLT_MAX));
+    }
+    Rng r{16};
+    for (int i = 0; i < 2000000; ++i) check(float_of_bits((uint32_t)r.next()));
+    for (const float x : {65504.f, 65519.996f, 65520.f, 65536.f, 1e30f, FLT_MAX, FLT_MIN, 1.401298464e-45f, 0x1p-24f,
+                          0x1p-25f, 0x1p-14f, HUGE_VALF})
+        check(x);
+    std::printf("half_dir selfcheck checks=%" PRId64 " wrong=%" PRId64 "\n", checks, wrong);
+}
+
+struct HalfImage {
+    uint64_t digest = FNV0;
+    int planes = 0, inf = 0, subnormal = 0, not_outward = 0;  // over the planes of non-empty children
+};
+HalfImage half_image(const std::vector<MfxNode>& nodes) {
+    HalfImage r;
+    for (const MfxNode& n : nodes) {
+        const MfxNodeH h = mfx_half::node_to_half(n);
+        r.digest = fnv(r.digest, &h, sizeof(h));
+        const float* lo32[3] = {n.lox, n.loy, n.loz};
+        const float* hi32[3] = {n.hix, n.hiy, n.hiz};
+        const uint16_t* lo16[3] = {h.lox, h.loy, h.loz};
+        const uint16_t* hi16[3] = {h.hix, h.hiy, h.hiz};
+        for (int k = 0; k < 4; ++k) {
+            if (n.child[k] == MFX_CHILD_EMPTY) continue;
+            for (int a = 0; a < 3; ++a)
+                for (int side = 0; side < 2; ++side) {
+                    const uint16_t b = side ? hi16[a][k] : lo16[a][k];
+                    const double f = side ? hi32[a][k] : lo32[a][k];
+                    ++r.planes;
+                    if ((b & 0x7fff) == 0x7c00) {
+                        ++r.inf;
+                        if ((b == 0x7c00) != (side == 1)) ++r.not_outward;  // -inf below, +inf above
+                        continue;
+                    }
+                    if ((b & 0x7c00) == 0 && (b & 0x3ff) != 0) ++r.subnormal;
+                    if (side ? half_value(b) < f : half_value(b) > f) ++r.not_outward;
+                }
+        }
+    }
+    return r;
+}
+
+std::vector<std::pair<std::string, HalfImage>> g_half;  // of every scene print_case built, in order
+
 void print_case(const char* name, const mfx_scene_desc& d, const mfx_instance* inst = nullptr, int ninst = 0,
                 bool flatten = false) {
     MfxHostScene s;
@@ -169,6 +271,7 @@ void print_case(const char* name, const mfx_scene_desc& d, const mfx_instance* i
         std::printf("%s FAILED: %s\n", name, err.c_str());
         return;
     }
+    g_half.emplace_back(name, half_image(s.nodes));
     uint64_t ref = FNV0;
     ref = fnv(ref, s.ref_indices.data(), s.ref_indices.size() * sizeof(int32_t));
     ref = fnv(ref, s.leaf_first.data(), s.leaf_first.size() * sizeof(int32_t));
@@ -188,6 +291,39 @@ void print_err(const char* name, const mfx_scene_desc& d, const mfx_instance* in
     std::string err;
     const bool ok = mfx_build_scene(&d, s, err, false, inst, ninst, false);
     std::printf("err %s: %s\n", name, ok ? "(accepted)" : err.c_str());
+}
+
+// x*s + off on every point, sphere centre, light corner and the camera's position; radii times s
+void similar(std::vector<mfx_prim>& v, mfx_scene_desc& d, double s, const double* off) {
+    for (mfx_prim& p : v) {
+        const int nv = p.kind == MFX_PRIM_SPHERE ? 1 : 4;
+        for (int k = 0; k < nv; ++k)
+            for (int a = 0; a < 3; ++a) p.p[k][a] = p.p[k][a] * s + off[a];
+        if (p.kind == MFX_PRIM_SPHERE) p.p[1][0] *= s;
+    }
+    for (int a = 0; a < 3; ++a) {
+        for (int k = 0; k < 4; ++k) d.light.p[k][a] = d.light.p[k][a] * s + off[a];
+        d.camera.position[a] = d.camera.position[a] * s + off[a];
+    }
+}
+
+// soup_600 past and below the half range: the host image, its FP16 node image and that image's planes
+void print_range(double s, double ox, double oy, double oz) {
+    std::vector<mfx_prim> v = soup(600, 600);
+    mfx_scene_desc d = desc_of(v);
+    const double off[3] = {ox, oy, oz};
+    similar(v, d, s, off);
+    MfxHostScene h;
+    std::string err;
+    if (!mfx_build_scene(&d, h, err)) {
+        std::printf("range soup_600 s=%a off=(%a,%a,%a) FAILED: %s\n", s, ox, oy, oz, err.c_str());
+        return;
+    }
+    const HalfImage hi = half_image(h.nodes);
+    std::printf("range soup_600 s=%a off=(%a,%a,%a) image=%016" PRIx64 " nodes2=%d nodes=%zu eps=%a half=%016" PRIx64
+                " planes=%d inf=%d (%.3f) subnormal=%d (%.3f) not_outward=%d\n",
+                s, ox, oy, oz, mfx_scene_digest(h), h.nodes2, h.nodes.size(), (double)h.eps, hi.digest, hi.planes, hi.inf,
+                (double)hi.inf / hi.planes, hi.subnormal, (double)hi.subnormal / hi.planes, hi.not_outward);
 }
 
 }  // namespace
@@ -274,5 +410,93 @@ int main() {
         const mfx_instance bad[2] = {entry(0, 3, 0, 0, 0, 4), entry(5, 1, 0, 0, 0)};
         print_err("several_instanced", d, bad, 2);
     }
+
+    // ---- values no builder can hold: NaN, inf and extents past 2^126 (mfx_scene.cpp EXTENT_MAX) ------
+    const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+    {
+        std::vector<mfx_prim> v = good;
+        v[1].p[2][1] = nan;
+        print_err("nan_coordinate", desc_of(v));
+        v = good;
+        v[2].p[1][0] = inf;
+        print_err("inf_radius", desc_of(v));
+        v = good;
+        v[0].p[3][0] = nan;  // a triangle reads three corners
+        v[2].p[1][1] = nan;  // a sphere reads its centre and p[1][0]
+        print_err("nan_unused_values", desc_of(v));
+        mfx_scene_desc d = desc_of(good);
+        d.light.p[2][1] = nan;
+        print_err("nan_light_corner", d);
+        d = desc_of(good);
+        d.light.intensity[1] = inf;
+        print_err("inf_light_intensity", d);
+        d = desc_of(good);
+        d.camera.position[0] = -inf;
+        print_err("inf_camera_position", d);
+        d = desc_of(good);
+        d.camera.fov = nan;
+        print_err("nan_camera_fov", d);
+        d.camera.derived = 1;  // fov is not read then
+        print_err("nan_camera_fov_derived", d);
+    }
+    {
+        // one thin triangle 2a long and the camera c from its box's middle: R = max(a, c), T = 2a + c
+        // exactly (the height's square is below an ulp of 4a^2)
+        std::vector<mfx_prim> v{good[0]};
+        const double a = 0x1p124;
+        pt(v[0].p[0], -a, 0.0, 0.0);
+        pt(v[0].p[1], a, 0.0, 0.0);
+        pt(v[0].p[2], 0.0, 1.0, 0.0);
+        mfx_scene_desc d = desc_of(v);
+        pt(d.camera.position, 0.0, 0.5, 0x1p124);
+        print_err("extent_2_126", d);
+        print_case("extent_2_126", d);
+        pt(d.camera.position, 0.0, 0.5, 0x1p124 + 0x1p75);
+        print_err("extent_past_2_126", d);
+        // two uses of one template 2^75 apart: R + T = 2^126 - 2^74, and the template frame adds |off|
+        const mfx_instance apart[2] = {entry(0, 1, 0.0, 0.0, 0.0), entry(0, 1, 0.0, 0.0, 0x1p75)};
+        pt(d.camera.position, 0.0, 0.5, 0x1p124);
+        print_err("extent_past_2_126_by_instance_offset", d, apart, 2);
+    }
+    {
+        // which comes first: primitives in order, per primitive the material, the kind, then its values;
+        // the light and the camera after every primitive, the extent last
+        std::vector<mfx_prim> v = good;
+        v[0].p[0][0] = nan;
+        v[1].material = 3;
+        print_err("nan_then_material", desc_of(v));
+        v = good;
+        v[1].material = 3;
+        v[1].p[0][0] = nan;
+        v[2].p[1][0] = nan;
+        print_err("material_and_nan_in_one", desc_of(v));
+        v = good;
+        v[2].p[0][2] = inf;
+        mfx_scene_desc d = desc_of(v);
+        d.light.normal[0] = nan;
+        d.camera.aspect = nan;
+        d.max_depth = 16;
+        print_err("depth_then_nan", d);
+        d.max_depth = 3;
+        print_err("prim_then_light_then_camera", d);
+        d.prims = good.data();
+        print_err("light_then_camera", d);
+        const mfx_instance moved[2] = {entry(0, 3, 0, 0, 0), entry(0, 3, 1, nan, 0)};
+        print_err("nan_instance_offset", desc_of(good), moved, 2);
+    }
+
+    // ---- the FP16 node image: half_dir against a table, then every scene above ------------------------
+    print_half_selfcheck();
+    for (const auto& h : g_half)
+        std::printf("half %s digest=%016" PRIx64 " planes=%d inf=%d subnormal=%d not_outward=%d\n", h.first.c_str(),
+                    h.second.digest, h.second.planes, h.second.inf, h.second.subnormal, h.second.not_outward);
+    print_range(1.0, 0.0, 0.0, 0.0);
+    print_range(1.0, 1e5, 0.0, -7e4);
+    print_range(1.0, 65504.0, 65504.0, -65504.0);
+    print_range(1e5, 0.0, 0.0, 0.0);
+    print_range(1e-4, 0.0, 0.0, 0.0);
+    print_range(1.0, 1e7, 0.0, 0.0);
+    print_range(3e19, 0.0, 0.0, 0.0);
+    print_range(1e30, 0.0, 0.0, 0.0);
     return 0;
 }

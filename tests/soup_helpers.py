@@ -391,7 +391,10 @@ def far_case(s, offset):
     return a, b, rr, np.random.default_rng(9500).uniform(0.05, 3.0, size=len(rr)) * s
 
 
-FAR = [(1e3, 5e3), (1.0, 3e4)]
+# (s, offset); from the third on the coordinates leave what binary16 holds (past 65504, or below 6.1e-5):
+# the query kernels walk the FP32 nodes, tests/range_helpers.py has the images on the FP16 ones
+FAR = [(1e3, 5e3), (1.0, 3e4), (1.0, 1e5), (1.0, (1e5, 0.0, -7e4)), (1.0, (65504.0, 65504.0, -65504.0)), (1e5, 0.0),
+       (1e-4, 0.0), (1.0, 1e7)]
 
 
 def moved_two_spheres_plane():

@@ -179,8 +179,11 @@ def test_far_cases_hit(oracle, s, offset):
     o = oracle.OracleScene(b)
     t, prim, _ = o.closest_hit(rr)
     occ = o.any_hit(rr, tmax)
+    print(f"s={s} offset={offset}: hit share {(prim >= 0).mean():.3f}, sphere hits {(a.prims['kind'][prim[prim >= 0]] == 2).sum()}")
     assert (prim >= 0).mean() > 0.01 and 0 < occ.sum() < len(occ)
-    assert set(a.prims["kind"][prim[prim >= 0]].tolist()) == {0, 1, 2}
+    # Triangle.Hit culls |div| < 1e-6 absolutely (Trangle.fs:120-155), and div is a product of two edges:
+    # at s = 1e-4 the soup's edges are below 3e-5, so no triangle or rect can be hit there, only spheres
+    assert set(a.prims["kind"][prim[prim >= 0]].tolist()) == ({2} if s == 1e-4 else {0, 1, 2})
 
 
 def test_moved_sphere_scene_is_lit(oracle):
