@@ -173,6 +173,9 @@ type MfxDenoiseVarCfg =
 module Api =
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
     extern int mfx_create(MfxSceneDesc& scene, MfxOptions& opt, nativeint& ctx)
+    // several area lights, one picked per path vertex (the lights replace scene.light; instances: 0n, 0 for a flat scene)
+    [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
+    extern int mfx_create_lights(MfxSceneDesc& scene, MfxQuadLight[] lights, int nlights, nativeint instances, int ninstances, MfxOptions& opt, nativeint& ctx)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
     extern void mfx_destroy(nativeint ctx)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]

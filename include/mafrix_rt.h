@@ -33,6 +33,7 @@ extern "C" {
 #define MFX_ABI_VERSION 6  /* 6: device lists partition the film by tile rows; MFX_F_ROW_PARTITION */
 #define MFX_MAX_DEVICES 64
 #define MFX_MAX_RENDER_AHEAD 1024
+#define MFX_MAX_LIGHTS 64 /* lights of a context at most (mfx_create_lights; ABI 6, additive) */
 
 /* error codes */
 #define MFX_OK 0
@@ -198,6 +199,51 @@ int mfx_instancing_info(mfx_ctx* ctx, double out[8]);
  * images are the same either way).                                                              */
 int mfx_build_instanced_info(const mfx_scene_desc* scene, const mfx_instance* instances, int32_t ninstances,
                              int32_t flags, double out[8], int32_t* stack_entries);
+
+/* ---- several area lights (ABI 6, additive; an extension: a reference `Scene` holds one light) ------
+ * A context has lights L_0 .. L_{N-1}, 1 <= N <= MFX_MAX_LIGHTS. Per light, creation computes the two
+ * sample triangles, `area` and 1 / area exactly as for the one light of mfx_create, and then stores
+ * pdf_n = (1.0 / area_n) / (double)N: two divisions, in that order.
+ * At a path vertex (PathIntegrator.TraceRay, Integrators.fs:118-136):
+ *  1. the hemisphere sample: unchanged, draw for draw;
+ *  2. the pick, only when N >= 2: one more draw r, n = (int)floor(r * (double)N). With N == 1 no draw is
+ *     taken and n = 0;
+ *  3. light n's Sample_Li: the draws sel, tu, tv, then toLight, dist and the shadow query on
+ *     [1e-6, dist - 1e-6];
+ *  4. the direct term l = (unit . normal_hit) * L_n(toLight), with light n's normal, area and intensity:
+ *     black unless toLight . normal_n < 0;
+ *  5. the term added is l / pdf_n; in the kernels' factored form a_v = (cs * (solid_n * I_n[c])) / pdf_n,
+ *     one rounding per operation;
+ *  6. everything else (col, the fold (a_v + f) * c_v, depth handling, ray counts) is as with one light.
+ * The pick is the reference's RandomDirectLightIntegrator (Integrators.fs:57-78: n = int(floor(
+ * rand.NextDouble() * float lights.Length)), then SingleDirectLightIntegrator on lights[n]), with one
+ * deliberate departure: the division by N inside pdf_n. The reference returns the picked light's own
+ * pdf and so renders the mean of the lights; radiance is linear in emission, so the lights' sum is what
+ * a scene with N lamps looks like, and that is what this renders (unbiased for the sum).
+ * The pick needs no clamp: a draw is k * 2^-53 with k < 2^53, and (1 - 2^-53) * N rounds to a double
+ * below N for every N <= MFX_MAX_LIGHTS (mafrixraytracing_amd/lights.py `pick` has the argument).
+ * N == 1 through this entry point is, bit for bit, mfx_create (or mfx_create_instanced) with that light:
+ * the same kernel instances, pool layout and grids.
+ *
+ * lights[0..nlights) replace scene->light, which is not read. instances == NULL && ninstances == 0 is
+ * a flat scene; otherwise the call behaves as mfx_create_instanced. MFX_E_INVALID, decided on the host
+ * before any device is touched: nlights < 1 or > MFX_MAX_LIGHTS, or NULL lights; a non-finite corner,
+ * normal or intensity of a light (the message names the light's index and the field); with nlights >= 2
+ * a light whose area is 0 or not finite (one light keeps mfx_create's behaviour), and MFX_F_MEGAKERNEL
+ * or MFX_F_COUNT_STATS (the megakernel and the counting instances are built for one light only).
+ * With N >= 2 every trace runs the wavefront pipeline, as under MFX_F_WAVEFRONT, and the pool keeps one
+ * more byte per path vertex (the picked light of a lit vertex). Every sampling call composes with it
+ * (the one-sample call, render-ahead, adaptive sampling and its resume, device lists, partitions,
+ * mfx_set_camera); mfx_launch_info's out[13] (gray light) is 0.                                   */
+int mfx_create_lights(const mfx_scene_desc* scene, const mfx_quad_light* lights, int32_t nlights,
+                      const mfx_instance* instances, int32_t ninstances, const mfx_options* opt, mfx_ctx** out);
+/* out[0] = N, out[1] = 1 if the several-light kernel instances run (N >= 2), out[2] = bytes of the
+ * device light table, out[3] = bytes per path slot the lights add to the pool (0 with one light),
+ * out[4] / out[5] = resident blocks per CU of the k_shadow / k_resolve instance in use, the rest 0.  */
+int mfx_light_info(mfx_ctx* ctx, double out[8]);
+/* Host-only (no device needed): what creation derives from the lights, by the code creation runs.
+ * out[nlights][4] = area, 1 / area, pdf_n, 0. The same refusals as mfx_create_lights' for the lights. */
+int mfx_light_table(const mfx_quad_light* lights, int32_t nlights, double* out);
 
 /* ---- the camera (an extension of the ABI: the reference's PinholeCamera has mutable position /
  * topleft / coord, Camera.fs:122-133, and Film.Reset exists for a camera move). Additive in ABI 6. ---- */
@@ -661,8 +707,9 @@ int mfx_device_info(mfx_ctx* ctx, int32_t* out, int32_t cap);
  * slots in LDS (> 0: the small-scene instances), out[9] = instance records in LDS (two-level
  * scenes; the others are read from global memory), out[10] = k_shadow's build (3 or 4 waves per
  * SIMD), out[11] = the megakernel's (1 or 4), out[12] = 1 if a HIT state word carries the lit mask,
- * out[13] = 1 if a lit vertex's direct term is recorded as one double (a gray light), out[14] = 1 if
- * camera rays run as packets, out[15] / out[16] / out[17] = blocks of k_extend / k_shadow / k_camera
+ * out[13] = 1 if a lit vertex's direct term is recorded as one double (a gray light; 0 with several
+ * lights), out[14] = 1 if camera rays run as packets, out[15] / out[16] / out[17] = blocks of k_extend /
+ * k_shadow / k_camera
  * (0: no packets), out[18] = the spill buffer's entries per lane, out[19] = the lanes it holds,
  * out[20] = slots per chunk fetch, out[21] = 1 if k_shadow takes half chunks on small frames,
  * out[22] = the first iteration that moves paths to a ray queue (-1 never, -2 automatic),

@@ -27,6 +27,7 @@ MFX_F_ROW_PARTITION = 64
 MFX_F_IN_FLIGHT = 128
 MFX_INSTANCE_VERBATIM = 1
 MFX_MAX_DEVICES = 64
+MFX_MAX_LIGHTS = 64
 MFX_DN_SRC_HOST = 0
 MFX_DN_SRC_ACCUM = 1
 MFX_DN_SRC_ADAPTIVE = 2
@@ -135,9 +136,12 @@ class SceneArrays:
     (MFX_F_TWO_LEVEL)."""
 
     def __init__(self, prims: np.ndarray, albedo: np.ndarray, light: dict, camera: dict,
-                 width: int, height: int, max_depth: int = 3, instancing=None, two_level: bool = False):
+                 width: int, height: int, max_depth: int = 3, instancing=None, two_level: bool = False,
+                 lights=None):
         self.prims = np.ascontiguousarray(prims, dtype=PRIM_DTYPE)
         self.two_level = bool(two_level)
+        # every area light of the scene, in order (light dicts; mfx_create_lights), or None: `light` alone
+        self.lights = list(lights) if lights is not None else None
         self.instancing = None
         if instancing is not None:
             self.instancing = (np.ascontiguousarray(instancing[0], dtype=PRIM_DTYPE),
@@ -172,12 +176,34 @@ class SceneArrays:
 
     def with_film(self, width: int, height: int) -> "SceneArrays":
         return SceneArrays(self.prims, self.albedo, self.light, self.camera, width, height, self.max_depth,
-                           self.instancing, self.two_level)
+                           self.instancing, self.two_level, self.lights)
 
     def flat(self) -> "SceneArrays":
         """The same scene without its instancing (the reference's flat primitive list)."""
         return SceneArrays(self.prims, self.albedo, self.light, self.camera, self.width, self.height,
-                           self.max_depth)
+                           self.max_depth, lights=self.lights)
+
+
+def quad_lights(lights):
+    """A ctypes array of MfxQuadLight from light dicts (p: four corners, normal, intensity)."""
+    arr = (MfxQuadLight * max(1, len(lights)))()
+    for n, L in enumerate(lights):
+        for k in range(4):
+            for c in range(3):
+                arr[n].p[k][c] = float(L["p"][k][c])
+        for c in range(3):
+            arr[n].normal[c] = float(L["normal"][c])
+            arr[n].intensity[c] = float(L["intensity"][c])
+    return arr
+
+
+def light_table(lights) -> np.ndarray:
+    """Host-only: (N, 4) area, 1 / area, pdf_n, 0 of the lights as context creation derives them
+    (mfx_light_table; lights.light_table is the numpy statement of the same)."""
+    lib = load_library()
+    out = np.zeros((max(1, len(lights)), 4))
+    check(lib.mfx_light_table(quad_lights(lights), len(lights), dptr(out)), "mfx_light_table")
+    return out[:len(lights)]
 
 
 _P = C.POINTER
@@ -190,6 +216,10 @@ def _bind(lib, strict: bool = True):
         "mfx_create": (C.c_int, [_P(MfxSceneDesc), _P(MfxOptions), _P(C.c_void_p)]),
         "mfx_create_instanced": (C.c_int, [_P(MfxSceneDesc), _P(MfxInstance), C.c_int32, _P(MfxOptions),
                                            _P(C.c_void_p)]),
+        "mfx_create_lights": (C.c_int, [_P(MfxSceneDesc), _P(MfxQuadLight), C.c_int32, _P(MfxInstance), C.c_int32,
+                                        _P(MfxOptions), _P(C.c_void_p)]),
+        "mfx_light_info": (C.c_int, [C.c_void_p, _dp]),
+        "mfx_light_table": (C.c_int, [_P(MfxQuadLight), C.c_int32, _dp]),
         "mfx_expand_instances": (C.c_int, [_P(MfxPrim), C.c_int64, _P(MfxInstance), C.c_int32, _P(MfxPrim),
                                            C.c_int64, _P(C.c_int64)]),
         "mfx_instancing_info": (C.c_int, [C.c_void_p, _dp]),
@@ -246,7 +276,7 @@ def _bind(lib, strict: bool = True):
 
 
 EXPORTED_SYMBOLS = [
-    "mfx_create", "mfx_create_instanced", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_sample_adaptive_resume", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_temporal", "mfx_pinhole_derive", "mfx_camera_info", "mfx_set_camera", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
+    "mfx_create", "mfx_create_instanced", "mfx_create_lights", "mfx_light_info", "mfx_light_table", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_sample_adaptive_resume", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_temporal", "mfx_pinhole_derive", "mfx_camera_info", "mfx_set_camera", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
     "mfx_film_mean", "mfx_stats",
     "mfx_trace_accumulate", "mfx_accum_clear", "mfx_accum_reduce", "mfx_accum_device_ptr", "mfx_accum_attach", "mfx_accum_read_mean",
     "mfx_sync", "mfx_stream", "mfx_ray_counts", "mfx_last_trace_ms", "mfx_trace_timing", "mfx_ray_counts_total", "mfx_closest_hit", "mfx_any_hit", "mfx_ref_leaves",

@@ -128,6 +128,8 @@ static int scene_upload(mfx_ctx* c) {
     CK(upload(c->d_shade, c->host.shade));
     CK(upload(c->d_albedo, c->host.albedo));
     CK(upload(c->d_light, std::vector<MfxLight>{c->host.light}));
+    if (wf_multi_light(c)) CK(upload(c->d_lights, c->host.lights));  // (once per device of a list: every device runs this)
+    else c->d_lights.reset();
     CK(upload(c->d_cam, std::vector<MfxCamera>{c->host.camera}));
     CK(upload(c->d_refs, std::vector<const void*>{c->d_slot_ref.get(), c->d_ref_blob.get()}));
     if (!c->host.inst.empty()) CK(upload(c->d_inst, c->host.inst));
@@ -161,7 +163,8 @@ static int scene_shapes(mfx_ctx* c) {
     // resident blocks per CU of k_extend or k_shadow with nlds stack entries per lane in LDS (the rest
     // spilled), and ntop top nodes and nslot slots beside them
     auto blocks = [&](bool shd, int nlds, int ntop = 0, int nslot = 0) {
-        const WfLdsShape s{shd, nlds < c->stack_size, c->d_nodes_h != nullptr, nlds, ntop, (int)c->host.inst.size(), nslot};
+        const WfLdsShape s{shd, nlds < c->stack_size, c->d_nodes_h != nullptr, nlds, ntop, (int)c->host.inst.size(), nslot,
+                           shd && wf_multi_light(c)};
         int b = 0;
         const hipError_t e = mfx_wf_kernel_occupancy(s, &b);
         if (e != hipSuccess && qerr == hipSuccess) qerr = e;
@@ -205,6 +208,7 @@ static int scene_shapes(mfx_ctx* c) {
         // waves per SIMD: more registers, no spills (C2 / C5 +2 %); with 4 it keeps the 4-wave one
         A.shadow_waves = sbpc <= 3 ? 3 : 4;
         if (env.shadow_waves) A.shadow_waves = *env.shadow_waves == 3 ? 3 : 4;
+        if (wf_multi_light(c)) A.shadow_waves = 4;  // the several-light instances are the 4-wave build's only
         if (A.shadow_waves == 3) sbpc = std::min(sbpc, 3);
         if (c->diag_iter)
             fprintf(stderr,
@@ -327,10 +331,21 @@ static hipError_t repeated_device_setup(mfx_ctx* c) {
     return hipSetDevice(c->device);
 }
 
+static_assert(WF_MAX_LIGHTS == MFX_MAX_LIGHTS, "the kernels' light index width is the ABI's bound");
+
+// lights (mfx_create_lights): the list that replaces scene->light (null: scene->light, N = 1)
 static int create_impl(const mfx_scene_desc* scene, const mfx_instance* instances, int32_t ninstances,
-                       const mfx_options* opt, mfx_ctx** out) {
+                       const mfx_options* opt, mfx_ctx** out, const mfx_quad_light* lights = nullptr, int32_t nlights = 0) {
     if (!scene || !opt || !out) return fail(MFX_E_INVALID, "mfx_create: null argument");
     *out = nullptr;
+    std::vector<MfxLight> prepared;  // the lights' one validation: mfx_build_scene takes the result
+    if (lights) {  // on the host, before any device is asked for
+        std::string lerr;
+        if (!mfx_prepare_lights(lights, nlights, prepared, lerr)) return fail(MFX_E_INVALID, "mfx_create_lights: " + lerr);
+        // the megakernel and the counting instances of the trace kernels are built for one light
+        if (nlights >= 2 && (opt->flags & (MFX_F_MEGAKERNEL | MFX_F_COUNT_STATS)))
+            return fail(MFX_E_INVALID, "mfx_create_lights: MFX_F_MEGAKERNEL and MFX_F_COUNT_STATS need a single light");
+    }
     if (opt->part_count < 1 || opt->part_index < 0 || opt->part_index >= opt->part_count)
         return fail(MFX_E_INVALID, "mfx_create: bad sample partition");
     if (opt->ndevices < 0 || opt->ndevices > MFX_MAX_DEVICES || (opt->ndevices > 0 && !opt->devices))
@@ -357,7 +372,8 @@ static int create_impl(const mfx_scene_desc* scene, const mfx_instance* instance
     // the traversal BVH is built on the first device unless the caller asks for the host build
     // (the same tree either way: tests/test_gpu_build.py); the other devices get copies
     const bool flatten = flatten_instances(scene, instances, ninstances, opt->flags, dev_free);
-    if (!mfx_build_scene(scene, c->host, err, (opt->flags & MFX_F_HOST_BVH) == 0, instances, ninstances, flatten)) {
+    if (!mfx_build_scene(scene, c->host, err, (opt->flags & MFX_F_HOST_BVH) == 0, instances, ninstances, flatten, lights,
+                         lights ? &prepared : nullptr)) {
         const bool dev = err.rfind("GPU BVH build", 0) == 0;
         return fail(dev ? MFX_E_DEVICE : MFX_E_INVALID, "mfx_create: " + err);
     }
@@ -366,6 +382,7 @@ static int create_impl(const mfx_scene_desc* scene, const mfx_instance* instance
         k.prims.assign(scene->prims, scene->prims + scene->nprims);
         k.albedo.assign(scene->albedo, scene->albedo + 3 * (size_t)scene->nmat);
         if (instances) k.instances.assign(instances, instances + ninstances);
+        if (lights) k.lights.assign(lights, lights + nlights);
         k.desc = *scene;
         k.desc.prims = nullptr;
         k.desc.albedo = nullptr;
@@ -462,6 +479,7 @@ struct SceneState {
     DevBuf<MfxInstance> d_inst;
     DevBuf<double> d_albedo;
     DevBuf<MfxLight> d_light;
+    DevBuf<MfxLight> d_lights;
     DevBuf<MfxCamera> d_cam;
     DevBuf<const void*> d_refs;
     DevBuf<int32_t> d_spill;
@@ -481,6 +499,7 @@ static void swap_scene_state(mfx_ctx* c, SceneState& s) {
     std::swap(c->d_inst, s.d_inst);
     std::swap(c->d_albedo, s.d_albedo);
     std::swap(c->d_light, s.d_light);
+    std::swap(c->d_lights, s.d_lights);
     std::swap(c->d_cam, s.d_cam);
     std::swap(c->d_refs, s.d_refs);
     std::swap(c->d_spill, s.d_spill);
@@ -507,7 +526,8 @@ static int rebuild_for_camera(mfx_ctx* c, const mfx_pinhole* cam) {
     HIPCHECK(hipSetDevice(c->device));
     MfxHostScene h;
     std::string err;
-    if (!mfx_build_scene(&d, h, err, k.gpu_bvh, k.instanced ? k.instances.data() : nullptr, (int)k.instances.size(), k.flatten)) {
+    if (!mfx_build_scene(&d, h, err, k.gpu_bvh, k.instanced ? k.instances.data() : nullptr, (int)k.instances.size(), k.flatten,
+                         k.lights.empty() ? nullptr : k.lights.data(), &c->host.lights)) {  // (validated at creation)
         const bool dev = err.rfind("GPU BVH build", 0) == 0;
         return fail(dev ? MFX_E_DEVICE : MFX_E_INVALID, "mfx_set_camera: " + err);
     }
@@ -619,6 +639,46 @@ int mfx_create_instanced(const mfx_scene_desc* scene, const mfx_instance* instan
                          const mfx_options* opt, mfx_ctx** out) {
     if (!instances || ninstances < 1) return fail(MFX_E_INVALID, "mfx_create_instanced: no instances");
     return create_impl(scene, instances, ninstances, opt, out);
+}
+
+int mfx_create_lights(const mfx_scene_desc* scene, const mfx_quad_light* lights, int32_t nlights,
+                      const mfx_instance* instances, int32_t ninstances, const mfx_options* opt, mfx_ctx** out) {
+    if (!lights || nlights < 1 || nlights > MFX_MAX_LIGHTS)
+        return fail(MFX_E_INVALID, "mfx_create_lights: nlights must be 1 .. MFX_MAX_LIGHTS with a light array");
+    const bool flat = !instances && ninstances == 0;
+    if (!flat && (!instances || ninstances < 1)) return fail(MFX_E_INVALID, "mfx_create_lights: no instances");
+    return create_impl(scene, instances, flat ? 0 : ninstances, opt, out, lights, nlights);
+}
+
+int mfx_light_table(const mfx_quad_light* lights, int32_t nlights, double* out) {
+    if (!out) return fail(MFX_E_INVALID, "mfx_light_table: null argument");
+    std::vector<MfxLight> t;
+    std::string err;
+    if (!mfx_prepare_lights(lights, nlights, t, err)) return fail(MFX_E_INVALID, "mfx_light_table: " + err);
+    for (int32_t n = 0; n < nlights; ++n) {
+        out[4 * n + 0] = t[n].area;
+        out[4 * n + 1] = 1. / t[n].area;
+        out[4 * n + 2] = t[n].pdf;
+        out[4 * n + 3] = 0.0;
+    }
+    return MFX_OK;
+}
+
+int mfx_light_info(mfx_ctx* c, double out[8]) {
+    if (!c || !out) return fail(MFX_E_INVALID, "mfx_light_info: null argument");
+    const bool ml = wf_multi_light(c);
+    const WfParams& A = c->pool.params;
+    HIPCHECK(hipSetDevice(c->device));
+    const WfLdsShape s{true, A.stack_lds_shd < c->stack_size, c->d_nodes_h != nullptr, A.stack_lds_shd, A.ntop_shd,
+                       (int)c->host.inst.size(), A.nslot_shd, ml};
+    int sb = 0, rb = 0;
+    HIPCHECK(mfx_wf_kernel_occupancy(s, &sb));
+    if (A.shadow_waves == 3) sb = std::min(sb, 3);  // (the 3-wave build: scene_shapes)
+    HIPCHECK(mfx_wf_resolve_occupancy(ml, &rb));
+    const double v[8] = {(double)c->host.lights.size(), ml ? 1.0 : 0.0, ml ? (double)(c->host.lights.size() * sizeof(MfxLight)) : 0.0,
+                         ml ? (double)WF_LIGHT_BYTES_PER_SLOT(c->host.max_depth + 1) : 0.0, (double)sb, (double)rb, 0.0, 0.0};
+    std::copy(v, v + 8, out);
+    return MFX_OK;
 }
 
 void mfx_destroy(mfx_ctx* ctx) { delete ctx; }

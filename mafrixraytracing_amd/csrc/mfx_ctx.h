@@ -280,6 +280,7 @@ struct KeptScene {
     std::vector<mfx_prim> prims;
     std::vector<double> albedo;
     std::vector<mfx_instance> instances;
+    std::vector<mfx_quad_light> lights;  // mfx_create_lights' list (empty: desc.light)
     mfx_scene_desc desc{};   // prims / albedo point nowhere: set from the vectors at use
     bool instanced = false;  // created by mfx_create_instanced
     bool flatten = false;    // the choice creation made for an instanced scene
@@ -383,6 +384,7 @@ struct __attribute__((visibility("hidden"))) mfx_ctx {
     mfxh::DevBuf<double> d_vscratch;   // megakernel: per-lane vertex records [max_depth + 1][6][grid * 256]
     mfxh::DevBuf<double> d_albedo;      // [nmat][3]
     mfxh::DevBuf<MfxLight> d_light;     // the light (k_shadow reads it into LDS)
+    mfxh::DevBuf<MfxLight> d_lights;    // several lights: the table k_shadow<ML> gathers from (null with one light)
     mfxh::DevBuf<MfxCamera> d_cam;      // the camera (k_camera reads it into LDS)
     mfxh::DevBuf<const void*> d_refs;   // {d_slot_ref, d_ref_blob} (k_shadow reads them into LDS)
     bool rep_valid = false;          // the last call was served from held frames, or was mfx_sample_adaptive
@@ -421,10 +423,14 @@ inline int band_rows(const mfx_ctx* d) {
     return band_row_count(d->band_index, d->band_count, tr);
 }
 
+// several lights (mfx_create_lights, N >= 2): the ML instances of k_shadow and k_resolve, the wavefront
+// pipeline for every trace, a light-index plane in the pool
+inline bool wf_multi_light(const mfx_ctx* c) { return c->host.lights.size() >= 2; }
+
 // bytes of one path slot of the wavefront pool (ray queues included)
 inline size_t pool_slot_bytes(const mfx_ctx* c) {
     const int nv = c->host.max_depth + 1;  // vertices per path
-    return WF_DOUBLES_PER_SLOT(nv) * 8 + WF_WORDS_PER_SLOT(nv) * 4;
+    return WF_DOUBLES_PER_SLOT(nv) * 8 + WF_WORDS_PER_SLOT(nv) * 4 + (wf_multi_light(c) ? WF_LIGHT_BYTES_PER_SLOT(nv) : 0);
 }
 
 // the scene images' device pointers of a kernel parameter struct (WfParams, TraceParams, AovParams, QueryParams)
@@ -443,7 +449,7 @@ void fill_scene_ptrs(const mfx_ctx* c, P& p) {
 inline bool wf_gray_light(const mfx_ctx* c) {
     const double* I = c->host.light.color;
     return std::memcmp(&I[0], &I[1], sizeof(double)) == 0 && std::memcmp(&I[0], &I[2], sizeof(double)) == 0 &&
-           !c->env.no_gray_light;
+           !c->env.no_gray_light && !wf_multi_light(c);  // (several lights: the term depends on the picked one)
 }
 // in place, a HIT state word carries the path's lit mask (WfParams.lit_in_hit)
 inline bool wf_lit_in_hit(const mfx_ctx* c) {

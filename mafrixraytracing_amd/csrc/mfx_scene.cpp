@@ -348,26 +348,31 @@ void mfx_derive_camera(const mfx_pinhole& c, MfxCamera& cam) {
 namespace {
 
 // ---- camera and light (Light.fs:31-40) ----------------------------------------------------------
-void set_camera_light(const mfx_scene_desc& d, MfxHostScene& s) {
-    mfx_derive_camera(d.camera, s.camera);
-
-    const mfx_quad_light& L = d.light;
+// one light of nlights: pdf = (1 / area) / nlights, two divisions (the second by 1.0 is exact)
+void make_light(const mfx_quad_light& L, int nlights, MfxLight& out) {
     D3 q[4] = {d3(L.p[0]), d3(L.p[1]), d3(L.p[2]), d3(L.p[3])};
     D3 tv[2][3] = {{q[0], q[1], q[2]}, {q[0], q[2], q[3]}};
     double area = 0;
     for (int t = 0; t < 2; ++t) {
         D3 e1 = sub(tv[t][1], tv[t][0]), e2 = sub(tv[t][2], tv[t][0]);
-        put(s.light.v0[t], tv[t][0]);
-        put(s.light.e1[t], e1);
-        put(s.light.e2[t], e2);
+        put(out.v0[t], tv[t][0]);
+        put(out.e1[t], e1);
+        put(out.e2[t], e2);
         double al = len(cross(e1, e2));
         double ta = al * 0.5;  // Trangle.fs:114
         area = (t == 0) ? ta : area + ta;
     }
-    s.light.area = area;
-    s.light.pdf = 1. / area;
-    put(s.light.normal, d3(L.normal));
-    put(s.light.color, d3(L.intensity));
+    out.area = area;
+    const double inv = 1. / area;
+    out.pdf = inv / (double)nlights;
+    put(out.normal, d3(L.normal));
+    put(out.color, d3(L.intensity));
+}
+
+void set_camera_light(const mfx_scene_desc& d, MfxHostScene& s) {
+    mfx_derive_camera(d.camera, s.camera);
+    make_light(d.light, 1, s.light);
+    s.lights.assign(1, s.light);
 }
 
 // ---- what the conservative widening of the boxes is sized by: R bounds the magnitude of every
@@ -386,13 +391,18 @@ Extent extent_with_camera(const MfxHostScene& s, const double* pos) {
 }
 // records what does not depend on the camera (the scene box, R of the primitives and the light) in s:
 // mfx_set_camera sizes eps for another position from them (mfx_camera_eps)
-Extent scene_extent(const mfx_scene_desc& d, const std::vector<Box>& pb, MfxHostScene& s) {
+// (every light's corners: a shadow ray ends on any of them; d.light is lights[0] when there is a list)
+Extent scene_extent(const mfx_scene_desc& d, const std::vector<Box>& pb, MfxHostScene& s,
+                    const mfx_quad_light* lights = nullptr, int nlights = 0) {
     Box all = pb[0];
     for (size_t i = 1; i < pb.size(); ++i) all = join(all, pb[i]);
     double R0 = 0;
     for (double v : {all.lo.x, all.lo.y, all.lo.z, all.hi.x, all.hi.y, all.hi.z}) R0 = std::max(R0, std::fabs(v));
     for (int k = 0; k < 4; ++k)
         for (int a = 0; a < 3; ++a) R0 = std::max(R0, std::fabs(d.light.p[k][a]));
+    for (int n = 1; n < nlights; ++n)
+        for (int k = 0; k < 4; ++k)
+            for (int a = 0; a < 3; ++a) R0 = std::max(R0, std::fabs(lights[n].p[k][a]));
     s.extent_R0 = R0;
     put(s.box_lo, all.lo);
     put(s.box_hi, all.hi);
@@ -878,18 +888,60 @@ uint64_t mfx_scene_digest(const MfxHostScene& s) {
     mix(s.ref_blob.data(), s.ref_blob.size());
     mix(s.shade.data(), s.shade.size() * sizeof(MfxShade));
     mix(s.inst.data(), s.inst.size() * sizeof(MfxInstance));
+    // several lights: the table too (one light: the digest it always had)
+    if (s.lights.size() >= 2) mix(s.lights.data(), s.lights.size() * sizeof(MfxLight));
     return x;
 }
 
+bool mfx_prepare_lights(const mfx_quad_light* lights, int nlights, std::vector<MfxLight>& out, std::string& err) {
+    if (!lights || nlights < 1 || nlights > MFX_MAX_LIGHTS) {
+        err = "nlights must be 1 .. " + std::to_string(MFX_MAX_LIGHTS) + " with a light array";
+        return false;
+    }
+    out.assign((size_t)nlights, MfxLight{});
+    for (int n = 0; n < nlights; ++n) {
+        const mfx_quad_light& L = lights[n];
+        const std::string who = "light " + std::to_string(n);
+        for (int k = 0; k < 4; ++k)
+            if (!all_finite(L.p[k], 3)) {
+                err = who + " corner " + std::to_string(k) + " is not finite";
+                return false;
+            }
+        const char* bad = !all_finite(L.normal, 3) ? " normal" : !all_finite(L.intensity, 3) ? " intensity" : nullptr;
+        if (bad) {
+            err = who + bad + " is not finite";
+            return false;
+        }
+        make_light(L, nlights, out[n]);
+        // (one light keeps mfx_create's behaviour, whatever its area)
+        if (nlights >= 2 && !(out[n].area > 0.0 && std::isfinite(out[n].area) && std::isfinite(out[n].pdf))) {
+            err = who + " has no finite positive area (its pdf divides the direct term)";
+            return false;
+        }
+    }
+    return true;
+}
+
 bool mfx_build_scene(const mfx_scene_desc* d0, MfxHostScene& s, std::string& err, bool gpu_bvh,
-                     const mfx_instance* instances, int ninstances, bool flatten) {
+                     const mfx_instance* instances, int ninstances, bool flatten, const mfx_quad_light* lights,
+                     const std::vector<MfxLight>* prepared) {
     const auto t_start = Clock::now();
     InstancePlan plan;
     const mfx_scene_desc* d = d0;
     mfx_scene_desc dw;
+    const int nlights = lights && prepared ? (int)prepared->size() : 0;
+    if (lights) {  // the list replaces the description's light: lights[0] stands in its place
+        if (!d0 || nlights < 1) {
+            err = "null scene or no prepared lights";
+            return false;
+        }
+        dw = *d0;
+        dw.light = lights[0];
+        d = &dw;
+    }
     if (instances) {
         if (!plan_instances(d0, instances, ninstances, flatten, plan, err)) return false;
-        dw = *d0;
+        if (!lights) dw = *d0;
         dw.prims = plan.world.data();
         dw.nprims = (int64_t)plan.world.size();
         d = &dw;
@@ -903,7 +955,7 @@ bool mfx_build_scene(const mfx_scene_desc* d0, MfxHostScene& s, std::string& err
     PrimRecords rec;
     if (!make_prim_records(*d, rec, err)) return false;
     if (!validate_light_camera(*d, err)) return false;
-    const Extent ext = scene_extent(*d, rec.pb, s);
+    const Extent ext = scene_extent(*d, rec.pb, s, lights, nlights);
     double offmax = 0;  // a template frame's coordinates reach R + |off| (build_two_level)
     for (const Use& u : plan.uses)
         for (int a = 0; a < 3; ++a) offmax = std::max(offmax, std::fabs(u.off[a]));
@@ -914,6 +966,10 @@ bool mfx_build_scene(const mfx_scene_desc* d0, MfxHostScene& s, std::string& err
     RefGrouping grp;
     if (!group_reference_leaves(rec, s, grp, err)) return false;
     set_camera_light(*d, s);
+    if (lights) {
+        s.lights = *prepared;
+        s.light = s.lights[0];  // (N == 1: set_camera_light's own bits, (1 / area) / 1.0)
+    }
     s.eps = (float)std::ldexp(ext.R + ext.T, -19);
     s.inst_offmax = 0.0;
     s.eps_templates = 0.f;

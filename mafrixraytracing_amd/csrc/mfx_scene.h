@@ -24,7 +24,8 @@ struct MfxHostScene {
     int32_t world_slots = 0;        // slots of the world primitives (what a flat image holds)
     int32_t tlas_nodes = 0, blas_nodes = 0, blas_slots = 0, ntemplates = 0, top_slots = 0;  // two-level shape (blas_slots: one run per template)
     std::vector<double> albedo;  // [nmat][3]
-    MfxLight light;
+    MfxLight light;                // lights[0]: what the one-light kernel instances and the megakernel read
+    std::vector<MfxLight> lights;  // L_0 .. L_{N-1} (mfx_create_lights; N == 1: {light}), pdf = (1 / area) / N
     MfxCamera camera;
     int32_t width = 0, height = 0, max_depth = 3;
     int32_t bvh_depth = 0;     // longest root-to-leaf path in nodes[]
@@ -53,8 +54,15 @@ struct MfxHostScene {
 // gpu_bvh: build the traversal BVH2 on the current HIP device (the same tree as the host build).
 // instances (mfx_create_instanced): d->prims are templates, the world scene is their expansion;
 // flatten: trace it through one flat BVH instead of two levels.
+// lights (mfx_create_lights): the lights that replace d->light, which is then not read, with what
+// mfx_prepare_lights made of them (prepared->size() of them; the caller validates them there, once).
 bool mfx_build_scene(const mfx_scene_desc* d, MfxHostScene& s, std::string& err, bool gpu_bvh = false,
-                     const mfx_instance* instances = nullptr, int ninstances = 0, bool flatten = false);
+                     const mfx_instance* instances = nullptr, int ninstances = 0, bool flatten = false,
+                     const mfx_quad_light* lights = nullptr, const std::vector<MfxLight>* prepared = nullptr);
+// The lights of a context as the kernels read them (Light.fs:31-40): per light the two sample triangles,
+// area and pdf = (1 / area) / N. False with `err` set: a count outside 1 .. MFX_MAX_LIGHTS, a non-finite
+// field (err names the light's index), and with N >= 2 an area that is 0 or not finite.
+bool mfx_prepare_lights(const mfx_quad_light* lights, int nlights, std::vector<MfxLight>& out, std::string& err);
 // PinholeCamera's constructor (Camera.fs:122-133), or with c.derived the fields as they are.
 void mfx_derive_camera(const mfx_pinhole& c, MfxCamera& cam);
 // The widening mfx_build_scene would give s's boxes with the camera at pos: (float)ldexp(R + T, -19), and
@@ -64,7 +72,8 @@ void mfx_camera_eps(const MfxHostScene& s, const double* pos, float* eps, float*
 // The world primitive list of an instanced scene (mfx_instance: template + offset, FP64).
 bool mfx_expand(const mfx_prim* prims, int64_t nprims, const mfx_instance* inst, int ninst,
                 std::vector<mfx_prim>& world, std::string& err);
-// FNV-1a over the device images (nodes, slots, slot_ref, ref_blob, shade, inst): mfx_build_info's digest.
+// FNV-1a over the device images (nodes, slots, slot_ref, ref_blob, shade, inst) and, with several lights,
+// the light table: mfx_build_info's digest.
 uint64_t mfx_scene_digest(const MfxHostScene& s);
 
 #endif

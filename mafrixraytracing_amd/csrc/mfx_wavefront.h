@@ -192,7 +192,15 @@ struct WfParams {
     // counts are constant through a trace. Such a trace sets tile_padding whatever the film's size.
     const int32_t* tile_n;
     int32_t list_max;
+    // Several lights (mfx_create_lights with N >= 2; one light: null, 0, null, and none of the one-light
+    // kernel instances reads them). They run the ML instances of k_shadow and k_resolve: at a vertex one
+    // more draw picks light n = floor(r * N), the lane gathers that light from the table, and a lit
+    // vertex records n in vlt, where k_resolve finds the intensity and pdf_n its direct term takes.
+    const MfxLight* lights;  // [nlights] the device light table, pdf = (1 / area) / N
+    int32_t nlights;
+    uint8_t* vlt;            // [vertex][stride] a lit vertex's light (beside vmat; allocated with N >= 2 only)
 };
+#define WF_MAX_LIGHTS 64  // MFX_MAX_LIGHTS: a light index is 6 bits of k_shadow's pending flag word
 
 // The adaptive sampler's tile check (k_tile_check: one wave per active tile) and the compaction of the
 // tiles that go on (k_tile_compact). The rule is stated in include/mafrix_rt.h (mfx_sample_adaptive).
@@ -229,6 +237,8 @@ hipError_t mfx_wf_tile_check(const TileCheckParams& C, hipStream_t st);
 #define WF_WORDS_PER_SLOT(nvert) (3 + (nvert) + (MFX_RAY_QUEUE ? 7 : 0))  // rn, depth, state + the vertices' materials
 // the two ray queues' share of that (queue 0's ray and draw count; both queues' depth, state and slot)
 #define WF_QUEUE_BYTES_PER_SLOT (MFX_RAY_QUEUE ? 6 * 8 + 7 * 4 : 0)
+// several lights: one byte per vertex more, the lit vertices' light indices (WfParams::vlt)
+#define WF_LIGHT_BYTES_PER_SLOT(nvert) (nvert)
 
 #ifndef WF_STACK_LDS
 #define WF_STACK_LDS 16  // traversal stack entries per lane kept in LDS (deeper ones spill to HBM/L2)
@@ -252,9 +262,12 @@ struct WfLdsShape {
     int ntop;       // top BVH nodes
     int ninst;      // the scene's instances (0: a flat scene), min(ninst, WF_INST_LDS) records of them in LDS
     int nslot;      // slots' test prefixes
+    bool ml;        // k_shadow's several-light instance (WfParams::lights set; the same LDS footprint)
 };
 // resident blocks per CU of the kernel instance that holds shape s
 hipError_t mfx_wf_kernel_occupancy(const WfLdsShape& s, int* blocks_per_cu);
+// resident blocks per CU of k_resolve's accumulator instance (ml: the several-light one)
+hipError_t mfx_wf_resolve_occupancy(bool ml, int* blocks_per_cu);
 // resident blocks per CU of k_camera (camera-ray packets)
 hipError_t mfx_cam_occupancy(int stack_size, int* blocks_per_cu);
 // a ray queue's arrays (MFX_RAY_QUEUE): entries in the pool's shard ranges, counts per shard

@@ -486,10 +486,24 @@ struct VertexSample {
     DV wi, unit;
     double ei, dist, cs, solid;
     bool lightable;
+    int light;  // ML: the picked light
 };
-// LT: the light (k_shadow's LDS copy).
-__device__ __forceinline__ VertexSample sample_vertex(const MfxLight& LT, bool own, DV hp, DV nm, uint64_t key,
-                                                      uint32_t& rn, int* scratch) {
+// k_shadow's several-light instances keep these in the LDS block the one light's copy takes otherwise
+struct MlPtrs {
+    const MfxLight* lights;
+    uint8_t* vlt;
+    int32_t nlights;
+};
+static_assert(sizeof(MlPtrs) <= sizeof(MfxLight), "MlPtrs lies in the light's LDS block: k_shadow's footprint stays");
+// LT1: the light (k_shadow's LDS copy).
+// ML: several lights (mfx_create_lights). After the hemisphere sample one more draw r picks light
+// n = floor(r * N) of the table `lights` (no clamp: r <= 1 - 2^-53, and (1 - 2^-53) * N rounds below N for
+// N <= 64); the lane reads that light's fields from global memory (lanes of a wave pick different
+// lights; the table is 208 B a light and stays in L1 / L2), and LT is not read.
+template <bool ML = false>
+__device__ __forceinline__ VertexSample sample_vertex(const MfxLight& LT1, bool own, DV hp, DV nm, uint64_t key,
+                                                      uint32_t& rn, int* scratch, const MfxLight* lights = nullptr,
+                                                      int nlights = 1) {
     VertexSample V{};
 #if defined(MFX_DIAG_ONE_TRIAL)  // timing experiment only: the first trial, mirrored into the hemisphere
     DV p = dv(rng_next(key, rn) * 2.0 - 1.0, rng_next(key, rn) * 2.0 - 1.0, rng_next(key, rn) * 2.0 - 1.0);
@@ -500,6 +514,11 @@ __device__ __forceinline__ VertexSample sample_vertex(const MfxLight& LT, bool o
     if (!own) return V;
     V.wi = vnormalize(p);
     V.ei = vdot(nm, V.wi);
+    if constexpr (ML) {  // the pick (RandomDirectLightIntegrator, Integrators.fs:62)
+        const double r = rng_next(key, rn);
+        V.light = (int)floor(r * (double)nlights);
+    }
+    const MfxLight& LT = ML ? lights[V.light] : LT1;
     const double sel = rng_next(key, rn);
     const int lt = sel < 0.5 ? 0 : 1;
     const double tu = rng_next(key, rn);
@@ -508,10 +527,10 @@ __device__ __forceinline__ VertexSample sample_vertex(const MfxLight& LT, bool o
     if (tu + tv > 1.) { uu = 1. - tu; vv = 1. - tv; }
     const double sq = sqrt(1. - uu);
     const double s1 = 1. - sq, s2 = vv * sq;
-    // both halves from scalar registers, selected per lane
-    const DV lv0 = lt ? ld3(LT.v0[1]) : ld3(LT.v0[0]);
-    const DV le1 = lt ? ld3(LT.e1[1]) : ld3(LT.e1[0]);
-    const DV le2 = lt ? ld3(LT.e2[1]) : ld3(LT.e2[0]);
+    // both halves from scalar registers, selected per lane (ML: the lane's half of its light, gathered)
+    const DV lv0 = ML ? ld3(LT.v0[lt]) : lt ? ld3(LT.v0[1]) : ld3(LT.v0[0]);
+    const DV le1 = ML ? ld3(LT.e1[lt]) : lt ? ld3(LT.e1[1]) : ld3(LT.e1[0]);
+    const DV le2 = ML ? ld3(LT.e2[lt]) : lt ? ld3(LT.e2[1]) : ld3(LT.e2[0]);
     const DV lp = vadd(vadd(lv0, vmul(le1, s1)), vmul(le2, s2));
     const DV toLight = vsub(lp, hp);
     V.dist = vlen(toLight);
@@ -898,7 +917,14 @@ struct ShdPtrs {
 // Q: the instance that reads a ray queue (P.qslot) or writes the next one (P.ncount), MFX_RAY_QUEUE
 // LIST: the instances for a listed trace (adaptive sampling: path_pixel's tile list, and WF_LIST_TILE_N's counts)
 // NF: the node format, as k_extend's
-template <bool STATS, bool SPILL, int WAVES, int SK, bool Q, int LIST = WF_LIST_NONE, int NF = MFX_NF_ANY>
+// ML: the instances for several lights (mfx_create_lights, N >= 2): the pick draw and the picked light's
+// gather in sample_vertex, the light's index in bits 24..29 of the pending flag word (free: the lit mask
+// ends at bit 23), and a lit vertex's index written to P.vlt beside its cs and solid. The table pointer,
+// the count and vlt lie in the LDS block the one light's copy takes otherwise (MlPtrs), so the LDS
+// footprint, and with it the blocks per CU, are the one-light instance's. A template parameter, not a
+// branch on the count: the one-light instances hold none of this (r04c: one run-time branch in the leaf
+// test cost 1.8 to 4 %).
+template <bool STATS, bool SPILL, int WAVES, int SK, bool Q, int LIST = WF_LIST_NONE, int NF = MFX_NF_ANY, bool ML = false>
 __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
     constexpr bool INST = SK == WF_SK_INST, SLDS = SK == WF_SK_SLDS;
     extern __shared__ int lds_all[];
@@ -915,8 +941,12 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
     uint32_t* red = (uint32_t*)(pend_base + 4 * PendShd::BYTES);
     // the light, after the four waves' shade lists (8-B aligned): copied before load_top_nodes' barrier
     MfxLight* light_lds = (MfxLight*)((int*)(red + 16) + 4 * 2 * WF_SHD_LIST);
-    if (threadIdx.x < sizeof(MfxLight) / 8)
-        ((double*)light_lds)[threadIdx.x] = ((const double*)P.light_dev)[threadIdx.x];
+    if constexpr (ML) {
+        if (threadIdx.x == 3) *(MlPtrs*)light_lds = MlPtrs{P.lights, P.vlt, P.nlights};
+    } else {
+        if (threadIdx.x < sizeof(MfxLight) / 8)
+            ((double*)light_lds)[threadIdx.x] = ((const double*)P.light_dev)[threadIdx.x];
+    }
     if (threadIdx.x == 0)
         *(ShdPtrs*)(light_lds + 1) = ShdPtrs{P.ox, P.oy, P.oz, P.dx, P.dy, P.dz, P.vei, P.vls, P.vmat, P.rn, P.depth,
                                             P.shade, P.fstate, P.qslot, P.nox, P.noy, P.noz, P.ndx, P.ndy, P.ndz,
@@ -950,6 +980,7 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
     if (INST) load_inst_lds(inst_lds, P.inst, P.ninst_lds);
     if (SLDS) load_slots_lds(slot_lds, P.slots, nslot);
     const MfxLight& LT = *light_lds;
+    [[maybe_unused]] const MlPtrs& M = *(const MlPtrs*)light_lds;  // ML: the same block holds these instead
     // the pool's and the queues' array pointers, read from LDS where they are used (the shading batch,
     // the records) instead of held in scalar registers through the traversal loop
     const ShdPtrs& C = *(const ShdPtrs*)(light_lds + 1);
@@ -1072,7 +1103,7 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
                     }
                 }
                 wave_lds_sync();  // every owner has read its shl entries: shl[0, 64) is the sampler's scratch
-                const VertexSample V = sample_vertex(LT, own, hp, nm, key, rn, shl);
+                const VertexSample V = sample_vertex<ML>(LT, own, hp, nm, key, rn, shl, ML ? M.lights : nullptr, ML ? M.nlights : 1);
                 if (own) {
                     const DV wi = V.wi, unit = V.unit;
                     const double dist = V.dist, cs = V.cs, solid = V.solid;
@@ -1093,12 +1124,13 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
                     }
                     // shadow bvh.Hit(Ray(hit.point, unit), 1e-6, dist - 1e-6) (Integrators.fs:44)
                     pd.slot[lane] = (Q && cn && C.ncount) ? qi : j;
-                    pd.flag[lane] = (cn ? 1 : 0) | (lightable ? 2 : 0) | (v << 2) | (dw & ~0xff);
+                    pd.flag[lane] = (cn ? 1 : 0) | (lightable ? 2 : 0) | (v << 2) | (dw & ~0xff) | (ML ? V.light << 24 : 0);
                     pd.v[0 * 64 + lane] = unit.x; pd.v[1 * 64 + lane] = unit.y; pd.v[2 * 64 + lane] = unit.z;
                     pd.v[3 * 64 + lane] = dist - 1e-6;
                     // a gray light: the direct term itself, (cs * (solid * I)) / pdf_li (Integrators.fs:52,
                     // Light.fs:52-53), the expression k_resolve evaluates per channel otherwise
-                    pd.v[4 * 64 + lane] = P.gray_light ? (cs * (solid * LT.color[0])) / LT.pdf : cs;
+                    // (ML: never gray; k_resolve has every light's intensity and pdf)
+                    pd.v[4 * 64 + lane] = (!ML && P.gray_light) ? (cs * (solid * LT.color[0])) / LT.pdf : cs;
                     pd.v[5 * 64 + lane] = solid;
                     c_shadow++;
                 }
@@ -1122,7 +1154,7 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
                 s = pd.slot[e];
                 vflag = pd.flag[e];
                 scs = pd.v[4 * 64 + e];
-                ssolid = P.gray_light ? 0.0 : pd.v[5 * 64 + e];
+                ssolid = (!ML && P.gray_light) ? 0.0 : pd.v[5 * 64 + e];
                 // origin = the hit point k_extend stored (a cache hit: the shading just read it), or
                 // its copy in the next queue. That copy (nox..noz, and nslot below) was stored in this
                 // kernel by the lane that shaded the hit, which may be another lane of this wave: the
@@ -1177,7 +1209,8 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
                 const int jr = nq ? C.nslot[s] : ((Q && C.qslot) ? C.qslot[s] : s);
                 double* vl = C.vls + (int64_t)(2 * v) * P.vstride + jr;
                 vl[0] = scs;
-                if (!P.gray_light) vl[P.vstride] = ssolid;
+                if (ML || !P.gray_light) vl[P.vstride] = ssolid;
+                if constexpr (ML) M.vlt[(int64_t)v * P.vstride + jr] = (uint8_t)((vflag >> 24) & (WF_MAX_LIGHTS - 1));
                 mask |= 1 << v;
             }
             const bool cont = (vflag & 1) != 0;
@@ -1242,7 +1275,9 @@ struct PathRec {
     int mask;  // lit-vertex mask (0: black path, or not a finished path of this generation)
     double ei[WF_RES_VERTS], cs[WF_RES_VERTS], so[WF_RES_VERTS];
     int mat[WF_RES_VERTS];
+    int lt[WF_RES_VERTS];  // ML: a lit vertex's light (P.vlt); the one-light instances never touch it
 };
+template <bool ML>
 __device__ __forceinline__ void load_path(const WfParams& P, int64_t j, int mask, PathRec& R) {
     R.mask = mask;
     if (mask == 0) return;
@@ -1250,13 +1285,15 @@ __device__ __forceinline__ void load_path(const WfParams& P, int64_t j, int mask
 #pragma unroll
     for (int v = 0; v < WF_RES_VERTS; ++v) {
         R.ei[v] = 0.0; R.cs[v] = 0.0; R.so[v] = 0.0; R.mat[v] = 0;
+        if constexpr (ML) R.lt[v] = 0;
         if (v <= top) {
             R.ei[v] = P.vei[v * P.vstride + j];
             R.mat[v] = P.vmat[v * P.vstride + j];
             if ((mask >> v) & 1) {
                 const double* vl = P.vls + (int64_t)(2 * v) * P.vstride + j;
                 R.cs[v] = vl[0];  // (a gray light: a_v itself)
-                if (!P.gray_light) R.so[v] = vl[P.vstride];
+                if (ML || !P.gray_light) R.so[v] = vl[P.vstride];
+                if constexpr (ML) R.lt[v] = P.vlt[v * P.vstride + j] & (WF_MAX_LIGHTS - 1);  // (the mask keeps the LDS read in bounds)
             }
         }
     }
@@ -1266,15 +1303,26 @@ __device__ __forceinline__ void load_path(const WfParams& P, int64_t j, int mask
 //   c_v = col = TwoPi * (ei * (INVPI * a))            (Material.fs:36, the expression k_shadow had)
 //   a_v = (cs * (solid * I)) / pdf_li, 0 if unlit     (Integrators.fs:52, Light.fs:52-53)
 //   f  <- (a_v + f) * c_v                             (Integrators.fs:135-136, pdf = 1)
+// ML (several lights): the lit vertex's light lt selects I and pdf_n from the kernel's LDS table
+// lt_lds[light][4] = I[0..2], pdf_n; the same expression, one rounding per operation. Never gray.
+template <bool ML>
 __device__ __forceinline__ void fold_vertex(const WfParams& P, bool lit, double ei, int mat, double cs, double so,
-                                            const double* alb_lds, double& fx, double& fy, double& fz) {
-    const MfxLight& LT = P.light;
+                                            const double* alb_lds, double& fx, double& fy, double& fz,
+                                            const double* lt_lds, int lt) {
+    [[maybe_unused]] const MfxLight& LT = P.light;
     const double* al = mat < WF_RES_MAT_LDS ? alb_lds + 3 * mat : P.albedo + 3 * mat;
     const double cx = TWOPI * (ei * (INVPI * al[0]));
     const double cy = TWOPI * (ei * (INVPI * al[1]));
     const double cz = TWOPI * (ei * (INVPI * al[2]));
     double ax = 0.0, ay = 0.0, az = 0.0;
-    if (lit && P.gray_light) {  // cs holds a_v, recorded by k_shadow with the same expression
+    if constexpr (ML) {
+        if (lit) {
+            const double* L = lt_lds + 4 * lt;
+            ax = (cs * (so * L[0])) / L[3];
+            ay = (cs * (so * L[1])) / L[3];
+            az = (cs * (so * L[2])) / L[3];
+        }
+    } else if (lit && P.gray_light) {  // cs holds a_v, recorded by k_shadow with the same expression
         ax = ay = az = cs;
     } else if (lit) {
         ax = (cs * (so * LT.color[0])) / LT.pdf;
@@ -1285,20 +1333,23 @@ __device__ __forceinline__ void fold_vertex(const WfParams& P, bool lit, double 
     fy = (ay + fy) * cy;
     fz = (az + fz) * cz;
 }
+template <bool ML>
 __device__ __forceinline__ void fold_path(const WfParams& P, int64_t j, const PathRec& R, const double* alb_lds,
-                                          double& fx, double& fy, double& fz) {
+                                          double& fx, double& fy, double& fz, const double* lt_lds) {
     const int top = 31 - __builtin_clz(R.mask);
     // vertices deeper than the batched records (max_depth >= WF_RES_VERTS), read here
     for (int v = top; v >= WF_RES_VERTS; --v) {
         const bool lit = (R.mask >> v) & 1;
         const double* vl = P.vls + (int64_t)(2 * v) * P.vstride + j;
-        fold_vertex(P, lit, P.vei[v * P.vstride + j], P.vmat[v * P.vstride + j], lit ? vl[0] : 0.0,
-                    lit ? vl[P.vstride] : 0.0, alb_lds, fx, fy, fz);
+        fold_vertex<ML>(P, lit, P.vei[v * P.vstride + j], P.vmat[v * P.vstride + j], lit ? vl[0] : 0.0,
+                        lit ? vl[P.vstride] : 0.0, alb_lds, fx, fy, fz, lt_lds,
+                        (ML && lit) ? P.vlt[v * P.vstride + j] & (WF_MAX_LIGHTS - 1) : 0);
     }
     // the batched ones, indices known at compile time (the records stay in registers)
 #pragma unroll
     for (int v = WF_RES_VERTS - 1; v >= 0; --v)
-        if (v <= top) fold_vertex(P, (R.mask >> v) & 1, R.ei[v], R.mat[v], R.cs[v], R.so[v], alb_lds, fx, fy, fz);
+        if (v <= top)
+            fold_vertex<ML>(P, (R.mask >> v) & 1, R.ei[v], R.mat[v], R.cs[v], R.so[v], alb_lds, fx, fy, fz, lt_lds, ML ? R.lt[v] : 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1328,12 +1379,25 @@ __device__ __forceinline__ void fold_path(const WfParams& P, int64_t j, const Pa
 #define WF_RES_ACCUM 0
 #define WF_RES_FRAMES 1
 #define WF_RES_MOMENTS 2
-template <int MODE>
+// ML: the instances for several lights: every light's intensity and pdf_n in LDS (2 KB for 64 lights),
+// indexed by the light a lit vertex recorded (P.vlt); the one-light instances carry none of it
+template <int MODE, bool ML = false>
 __global__ void __launch_bounds__(256) k_resolve(WfParams P) {
     constexpr bool FRAMES = MODE == WF_RES_FRAMES, MOM = MODE == WF_RES_MOMENTS;
     __shared__ double alb[3 * WF_RES_MAT_LDS];
     const int nm = P.nmat < WF_RES_MAT_LDS ? P.nmat : WF_RES_MAT_LDS;
     for (int i = threadIdx.x; i < 3 * nm; i += blockDim.x) alb[i] = P.albedo[i];
+    const double* lt_lds = nullptr;
+    if constexpr (ML) {
+        __shared__ double ltab[4 * WF_MAX_LIGHTS];
+        const int nl = P.nlights < WF_MAX_LIGHTS ? P.nlights : WF_MAX_LIGHTS;
+        for (int i = threadIdx.x; i < 4 * WF_MAX_LIGHTS; i += blockDim.x) {
+            const int n = i >> 2, f = i & 3;
+            // (entries past the table: pdf 1, intensity 0; never indexed by a well-formed record)
+            ltab[i] = n < nl ? (f < 3 ? P.lights[n].color[f] : P.lights[n].pdf) : (f < 3 ? 0.0 : 1.0);
+        }
+        lt_lds = ltab;
+    }
     __syncthreads();
     const int tiles_x = (P.width + 7) >> 3;
     const bool list = MOM && P.ntiles > 0;
@@ -1388,12 +1452,12 @@ __global__ void __launch_bounds__(256) k_resolve(WfParams P) {
         }
         PathRec R[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) load_path(P, jv[u], mask[u], R[u]);
+        for (int u = 0; u < U; ++u) load_path<ML>(P, jv[u], mask[u], R[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (!in[u]) continue;
             double fx = 0.0, fy = 0.0, fz = 0.0;
-            if (R[u].mask) fold_path(P, jv[u], R[u], alb, fx, fy, fz);
+            if (R[u].mask) fold_path<ML>(P, jv[u], R[u], alb, fx, fy, fz, lt_lds);
             if (FRAMES) {
                 ax = ax + (0.0 + fx) / 1.0;
                 ay = ay + (0.0 + fy) / 1.0;
@@ -1450,11 +1514,13 @@ struct WfKey {
     int list;   // WF_LIST_*
     int nf;     // MFX_NF_*
     int waves;  // k_shadow's build: 3 or 4 waves per SIMD
+    bool ml;    // k_shadow's several-light instance (WfParams::lights)
 };
 // a key's number, and the key of a number: the one place a field passes between run time and compile time
-constexpr int WF_KEYS = 2 * 2 * 3 * 2 * 2 * 3 * 3 * 2;
+constexpr int WF_KEYS = 2 * 2 * 2 * 3 * 2 * 2 * 3 * 3 * 2;
 static constexpr int key_index(const WfKey& k) {
-    return ((((((k.stats * 2 + k.spill) * 3 + k.sk) * 2 + k.queue) * 2 + k.start) * 3 + k.list) * 3 + k.nf) * 2 + (k.waves - 3);
+    return (((((((k.ml * 2 + k.stats) * 2 + k.spill) * 3 + k.sk) * 2 + k.queue) * 2 + k.start) * 3 + k.list) * 3 + k.nf) * 2 +
+           (k.waves - 3);
 }
 static constexpr WfKey key_at(int i) {
     WfKey k{};
@@ -1465,7 +1531,8 @@ static constexpr WfKey key_at(int i) {
     k.queue = i % 2, i /= 2;
     k.sk = i % 3, i /= 3;
     k.spill = i % 2, i /= 2;
-    k.stats = i;
+    k.stats = i % 2, i /= 2;
+    k.ml = i;
     return k;
 }
 
@@ -1497,21 +1564,25 @@ static constexpr bool nf_built(const WfKey& k) {
     return wf_nf_fixed(k) ? k.nf == MFX_NF_F32 || (MFX_NODE_F16 && k.nf == MFX_NF_H) : k.nf == MFX_NF_ANY;
 }
 // (a queue's entries are never FREE slots; only the iteration that starts paths maps them through a list)
+// (several lights, ml: k_shadow alone reads a light, and its ML instances are the 4-wave build without
+// the traversal counters: contexts with several lights refuse MFX_F_COUNT_STATS and take the 4-wave build)
 static constexpr bool extend_built(const WfKey& k) {
-    return k.waves == 4 && nf_built(k) && (k.queue ? !k.start && !k.list : k.start || !k.list);
+    return !k.ml && k.waves == 4 && nf_built(k) && (k.queue ? !k.start && !k.list : k.start || !k.list);
 }
-static constexpr bool shadow_built(const WfKey& k) { return !k.start && nf_built(k); }
+static constexpr bool shadow_built(const WfKey& k) { return !k.start && nf_built(k) && (!k.ml || (!k.stats && k.waves == 4)); }
 static constexpr bool camera_built(const WfKey& k) {
-    return !k.spill && k.sk == WF_SK_FLAT && !k.queue && k.start && k.nf == MFX_NF_ANY && k.waves == 4;
+    return !k.ml && !k.spill && k.sk == WF_SK_FLAT && !k.queue && k.start && k.nf == MFX_NF_ANY && k.waves == 4;
 }
 static constexpr int built_count(bool (*built)(const WfKey&)) {
     int n = 0;
     for (int i = 0; i < WF_KEYS; ++i) n += built(key_at(i));
     return n;
 }
-static_assert(built_count(extend_built) == (MFX_NODE_F16 ? 64 : 60) && built_count(shadow_built) == (MFX_NODE_F16 ? 152 : 144) &&
-                  built_count(camera_built) == 6,
-              "a new instance is a decision: every one is a kernel to compile, and an occupancy to ask about");
+static_assert(built_count(extend_built) == (MFX_NODE_F16 ? 64 : 60) &&
+                  built_count(shadow_built) == (MFX_NODE_F16 ? 152 + 40 : 144 + 36) && built_count(camera_built) == 6,
+              "a new instance is a decision: every one is a kernel to compile, and an occupancy to ask about "
+              "(k_shadow: 152 / 144 one-light instances, plus the several-light ones, ML: every spill, scene kind, "
+              "queue and list of the 4-wave build without counters, 36, and the FP16 format of the 4 flat unlisted ones)");
 
 enum { WF_K_EXTEND, WF_K_SHADOW, WF_K_CAMERA };
 template <int KERNEL, int I>
@@ -1520,7 +1591,7 @@ static const void* instance_at() {
     if constexpr (KERNEL == WF_K_EXTEND && extend_built(k))
         return (const void*)k_extend<k.stats, k.spill, k.sk, k.queue, k.start, k.list, k.nf>;
     else if constexpr (KERNEL == WF_K_SHADOW && shadow_built(k))
-        return (const void*)k_shadow<k.stats, k.spill, k.waves, k.sk, k.queue, k.list, k.nf>;
+        return (const void*)k_shadow<k.stats, k.spill, k.waves, k.sk, k.queue, k.list, k.nf, k.ml>;
     else if constexpr (KERNEL == WF_K_CAMERA && camera_built(k))
         return (const void*)k_camera<k.stats, k.list>;
     else
@@ -1538,11 +1609,11 @@ static const void* camera_kernel(const WfKey& k) { return instance<WF_K_CAMERA>(
 
 // the key of k_extend or k_shadow holding shape s
 static WfKey shape_key(const WfLdsShape& s, bool stats, bool queue, bool start, int list, int waves) {
-    WfKey k{stats, s.spill, scene_kind(s.ninst > 0, s.nslot), queue, start, list, MFX_NF_ANY, waves};
+    WfKey k{stats, s.spill, scene_kind(s.ninst > 0, s.nslot), queue, start, list, MFX_NF_ANY, waves, s.shadow && s.ml};
     if (wf_nf_fixed(k)) k.nf = s.fp16 ? MFX_NF_H : MFX_NF_F32;
     return k;
 }
-static WfKey camera_key(bool stats, int list) { return {stats, false, WF_SK_FLAT, false, true, list, MFX_NF_ANY, 4}; }
+static WfKey camera_key(bool stats, int list) { return {stats, false, WF_SK_FLAT, false, true, list, MFX_NF_ANY, 4, false}; }
 
 // The query asks the instance a launch of the shape runs, with two deliberate differences: the 4-wave
 // k_shadow whatever the context's build (scene_shapes chooses the 3-wave build from the answer), and, for
@@ -1579,7 +1650,7 @@ static void launch(const void* kernel, int grid, size_t lds, hipStream_t st, con
 static WfLdsShape lds_shape(const WfParams& P, bool shadow) {
     const int stack_lds = shadow ? P.stack_lds_shd : P.stack_lds_ext;
     return {shadow, stack_lds < P.stack_size, wf_fp16(P), stack_lds, shadow ? P.ntop_shd : P.ntop_ext,
-            P.inst ? P.ninst_lds : 0, shadow ? P.nslot_shd : P.nslot_ext};
+            P.inst ? P.ninst_lds : 0, shadow ? P.nslot_shd : P.nslot_ext, shadow && P.lights != nullptr};
 }
 
 static hipError_t launch_iteration(const WfParams& P, int ext_grid, int shd_grid, bool stats, hipStream_t st,
@@ -1598,12 +1669,16 @@ static hipError_t launch_iteration(const WfParams& P, int ext_grid, int shd_grid
     }
     const WfLdsShape s = lds_shape(P, true);
     const bool queue = P.qslot || P.ncount;
-    launch(shadow_kernel(shape_key(s, stats, queue, false, list, shadow_build(P.shadow_waves))), shd_grid, wf_lds_bytes(s), st, P);
+    const void* shd = shadow_kernel(shape_key(s, stats, queue, false, list, shadow_build(P.shadow_waves)));
+    if (!shd) return hipErrorInvalidValue;  // (several lights with counters or the 3-wave build: refused at creation)
+    launch(shd, shd_grid, wf_lds_bytes(s), st, P);
     return hipSuccess;
 }
 
 hipError_t mfx_wf_iteration(const WfParams& P, int ext_grid, int shd_grid, bool stats, hipStream_t st,
                             hipEvent_t* ev) {
+    // several lights: the table, its count and the index plane go together (k_shadow<ML> writes vlt)
+    if (P.lights && (!P.vlt || P.nlights < 2 || P.nlights > WF_MAX_LIGHTS || P.gray_light || stats)) return hipErrorInvalidValue;
     // the chunk heads and, beside them (WF_CTL_Q0 / WF_CTL_Q1), the next queue's shard counts
     unsigned long long* z = P.ctl;
     size_t nz = WF_NCTL;
@@ -1619,16 +1694,30 @@ hipError_t mfx_wf_iteration(const WfParams& P, int ext_grid, int shd_grid, bool 
 }
 
 hipError_t mfx_wf_resolve(const WfParams& P, hipStream_t st) {
+    const bool ml = P.lights != nullptr;  // several lights: the ML instance of each mode
+    if (ml && (!P.vlt || P.nlights < 2 || P.nlights > WF_MAX_LIGHTS || P.gray_light)) return hipErrorInvalidValue;
     if (P.mom || P.ntiles > 0) {  // the adaptive sampler's passes: the moments instance (a listed trace runs no other)
         if (!P.mom || P.film || P.res_ntx > 0) return hipErrorInvalidValue;
         const int64_t n = P.ntiles > 0 ? (int64_t)P.ntiles * 64 : (int64_t)((P.width + 7) >> 3) * P.band_rows * 64;
-        hipLaunchKernelGGL(k_resolve<WF_RES_MOMENTS>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P);
+        if (ml) hipLaunchKernelGGL((k_resolve<WF_RES_MOMENTS, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P);
+        else hipLaunchKernelGGL(k_resolve<WF_RES_MOMENTS>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P);
         return hipGetLastError();
     }
     const int64_t per_sample = (int64_t)(P.res_ntx > 0 ? P.res_ntx : (P.width + 7) >> 3) * P.band_rows * 64;
+    const dim3 grid((unsigned)((per_sample + 255) / 256));
+    if (ml) {
+        if (P.film) hipLaunchKernelGGL((k_resolve<WF_RES_FRAMES, true>), grid, dim3(256), 0, st, P);
+        else hipLaunchKernelGGL((k_resolve<WF_RES_ACCUM, true>), grid, dim3(256), 0, st, P);
+        return hipGetLastError();
+    }
     if (P.film) hipLaunchKernelGGL(k_resolve<WF_RES_FRAMES>, dim3((unsigned)((per_sample + 255) / 256)), dim3(256), 0, st, P);
     else hipLaunchKernelGGL(k_resolve<WF_RES_ACCUM>, dim3((unsigned)((per_sample + 255) / 256)), dim3(256), 0, st, P);
     return hipGetLastError();
+}
+
+hipError_t mfx_wf_resolve_occupancy(bool ml, int* blocks_per_cu) {
+    return ml ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_resolve<WF_RES_ACCUM, true>, 256, 0)
+              : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_resolve<WF_RES_ACCUM>, 256, 0);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -13,7 +13,7 @@ import numpy as np
 from .abi import (INSTANCING_KEYS, LAUNCH_INFO_KEYS, MFX_DN_SRC_ACCUM, MFX_DN_SRC_ADAPTIVE, MFX_DN_SRC_HOST,
                   MFX_DN_SRC_TEMPORAL, MFX_F_NONE, MFX_F_TWO_LEVEL, MfxAdaptive, MfxAdaptiveResume, MfxDenoiseCfg,
                   MfxDenoiseVarCfg, MfxInstance, MfxOptions, MfxTemporalCfg, SceneArrays, check, dptr, iptr, load_library,
-                  pinhole_struct)
+                  pinhole_struct, quad_lights)
 from .denoise import DenoiseConfig, DenoiseVarConfig
 from .temporal import TemporalConfig
 
@@ -26,13 +26,17 @@ class NativeContext:
 
     def __init__(self, arrays: SceneArrays, seed: int = DEFAULT_SEED, device: int = 0, flags: int = MFX_F_NONE,
                  part_index: int = 0, part_count: int = 1, devices: list[int] | None = None,
-                 instancing: bool = True, render_ahead: int = 0):
+                 instancing: bool = True, render_ahead: int = 0, lights: list | None = None):
         """devices: drive this list of HIP devices from one context (mfx_options.devices; the
         library's own RCCL reduce sums them into devices[0]); None: the single `device`.
         instancing: a scene with instancing data is created through mfx_create_instanced (two-level
         traversal; MFX_F_FLATTEN flattens it in the library); False: mfx_create on the world list.
         render_ahead: mfx_options.render_ahead (one-sample render calls served from batches of K
-        samples; 0 = off)."""
+        samples; 0 = off).
+        lights: a list of light dicts (scene_io's shape: p, normal, intensity) creates the context through
+        mfx_create_lights (one light picked per path vertex, the image is the lights' sum; they replace
+        arrays.light). Pass arrays.lights for a scene loaded with all_lights=True. None: mfx_create /
+        mfx_create_instanced with arrays.light alone, whatever arrays.lights holds."""
         self.lib = load_library()
         self.arrays = arrays
         self.w, self.h = arrays.width, arrays.height
@@ -46,7 +50,14 @@ class NativeContext:
                          ndevices=len(devices) if devices else 0, render_ahead=render_ahead,
                          devices=C.cast(self._devs, C.POINTER(C.c_int32)) if devices else None)
         h = C.c_void_p()
-        if inst:
+        self.lights = list(lights) if lights is not None else None
+        if self.lights is not None:
+            self._lights = quad_lights(self.lights)
+            self._inst = arrays.instancing[1] if inst else None
+            ip = self._inst.ctypes.data_as(C.POINTER(MfxInstance)) if inst else None
+            check(self.lib.mfx_create_lights(C.byref(self._desc), self._lights, len(self.lights), ip,
+                                             len(self._inst) if inst else 0, C.byref(opt), C.byref(h)), "mfx_create_lights")
+        elif inst:
             self._inst = arrays.instancing[1]
             ip = self._inst.ctypes.data_as(C.POINTER(MfxInstance))
             check(self.lib.mfx_create_instanced(C.byref(self._desc), ip, len(self._inst), C.byref(opt), C.byref(h)),
@@ -369,6 +380,14 @@ class NativeContext:
         check(self.lib.mfx_launch_info(self._h, iptr(out), len(out)), "mfx_launch_info")
         flags = ("spill_ext", "spill_shd", "lit_in_hit", "gray_light", "camera_packets", "shd_half")
         return {k: bool(v) if k in flags else int(v) for k, v in zip(LAUNCH_INFO_KEYS, out)}
+
+    def light_info(self) -> np.ndarray:
+        """mfx_light_info: [0] lights N, [1] 1 if the several-light kernel instances run, [2] bytes of the
+        device light table, [3] bytes per path slot the lights add to the pool, [4] / [5] resident blocks
+        per CU of the k_shadow / k_resolve instance in use; the rest 0."""
+        out = np.zeros(8)
+        check(self.lib.mfx_light_info(self._h, dptr(out)), "mfx_light_info")
+        return out
 
     def instancing_info(self) -> dict:
         """How instances are traced (mfx_instancing_info): two-level shape and image bytes."""

@@ -257,6 +257,8 @@ class SceneState:
     # start, count) runs of `prims`, and the template primitives per key
     segments: list = field(default_factory=list)
     templates: dict = field(default_factory=dict)
+    # InitSceneState(all_lights=True): every <Light> element in document order (None: `light` alone)
+    lights: list | None = None
 
     def arrays(self, max_depth: int = 3, width: int | None = None, height: int | None = None) -> SceneArrays:
         inst = None
@@ -275,7 +277,7 @@ class SceneState:
                     tmpl.extend(self.prims[start:start + count])
             inst = (_prim_array(tmpl), np.array(rows, dtype=INSTANCE_DTYPE))
         return SceneArrays(_prim_array(self.prims), self.manager.albedo_table(), self.light, self.camera,
-                           width or self.width, height or self.height, max_depth, instancing=inst)
+                           width or self.width, height or self.height, max_depth, instancing=inst, lights=self.lights)
 
 
 def _prim_array(plist) -> np.ndarray:
@@ -322,8 +324,12 @@ RELEASE_FALLBACK_LIGHT = {
 
 
 def InitSceneState(xml_text: str, base_dir: str = ".", manager: MaterialManager | None = None,
-                   light_fallback: str = "debug") -> SceneState:
+                   light_fallback: str = "debug", all_lights: bool = False) -> SceneState:
     """InitSceneState (Scene.fs:265-271): parse XML *text*, version must be 0.1.
+
+    all_lights: with True, every <Light type="area"> element becomes a light, in document order
+    (SceneState.lights; a context then picks one per path vertex, mfx_create_lights). The default keeps
+    the reference's behaviour: the last <Light> element wins (Scene.fs:247).
 
     light_fallback: what a light group whose first primitive is not a Rect does. "debug" (the
     default) raises SceneError, as the reference's Debug build does at `assert(false)`
@@ -372,27 +378,30 @@ def InitSceneState(xml_text: str, base_dir: str = ".", manager: MaterialManager 
                 raise SceneError(f"unknown model argument {a.get('name')!r}")
         models[n.get("name")] = load_obj(os.path.join(base_dir, fname), mgr)
     # Light (Scene.fs:179-199)
-    ln = nodes.get("Light")
-    if ln is None or ln.get("type") != "area":
-        raise SceneError("an area light is required")
-    ref, inten = "", (0.0, 0.0, 0.0)
-    for a in ln:
-        if a.get("name") == "shape_ref":
-            ref = a.get("value")
-        elif a.get("name") == "intensity":
-            inten = _f3(a)
-        else:
-            raise SceneError(f"unknown light argument {a.get('name')!r}")
-    grp = _find_model(ref, models)
-    if not grp:  # FindModel(...).ToArray()[0] on an empty group throws in either build
-        raise SceneError("the light's group has no primitive")
-    if grp[0].kind != MFX_PRIM_RECT:
-        if light_fallback == "debug":
-            raise SceneError("the light's first primitive must be a quad (Rect)")
-        light = dict(RELEASE_FALLBACK_LIGHT)
-    else:
+    def parse_light(ln):
+        if ln is None or ln.get("type") != "area":
+            raise SceneError("an area light is required")
+        ref, inten = "", (0.0, 0.0, 0.0)
+        for a in ln:
+            if a.get("name") == "shape_ref":
+                ref = a.get("value")
+            elif a.get("name") == "intensity":
+                inten = _f3(a)
+            else:
+                raise SceneError(f"unknown light argument {a.get('name')!r}")
+        grp = _find_model(ref, models)
+        if not grp:  # FindModel(...).ToArray()[0] on an empty group throws in either build
+            raise SceneError("the light's group has no primitive")
+        if grp[0].kind != MFX_PRIM_RECT:
+            if light_fallback == "debug":
+                raise SceneError("the light's first primitive must be a quad (Rect)")
+            return dict(RELEASE_FALLBACK_LIGHT)
         q = grp[0].pts
-        light = {"p": (q[0], q[1], q[2], q[3]), "normal": tri_normal(q[0], q[1], q[2]), "intensity": inten}
+        return {"p": (q[0], q[1], q[2], q[3]), "normal": tri_normal(q[0], q[1], q[2]), "intensity": inten}
+
+    light = parse_light(nodes.get("Light"))
+    # all_lights: every <Light type="area"> element, in document order (`light` stays the last one)
+    lights = [parse_light(n) for n in root if n.tag == "Light"] if all_lights else None
     # Film (Scene.fs:201-211)
     w, h = 800, 800
     fn = nodes.get("Film")
@@ -480,15 +489,16 @@ def InitSceneState(xml_text: str, base_dir: str = ".", manager: MaterialManager 
     for p in prims:
         if not (0 <= p.material < len(mgr.materials)):
             raise SceneError(f"material index {p.material} out of range (manager has {len(mgr.materials)})")
-    return SceneState(cam, light, w, h, prims, mgr, segments, templates)
+    return SceneState(cam, light, w, h, prims, mgr, segments, templates, lights)
 
 
-def load_scene_file(path: str, fresh_manager: bool = True, light_fallback: str = "debug", **kw) -> SceneArrays:
+def load_scene_file(path: str, fresh_manager: bool = True, light_fallback: str = "debug", all_lights: bool = False,
+                    **kw) -> SceneArrays:
     """Convenience: XML file -> SceneArrays, with a fresh MaterialManager (the reference's
     manager is process-global; a fresh one gives the index space of a first load)."""
     with open(path, "r", encoding="utf-8") as f:
         text = f.read()
     mgr = MaterialManager() if fresh_manager else None
     st = InitSceneState(text, base_dir=os.path.dirname(os.path.abspath(path)), manager=mgr,
-                        light_fallback=light_fallback)
+                        light_fallback=light_fallback, all_lights=all_lights)
     return st.arrays(**kw)
