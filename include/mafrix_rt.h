@@ -713,9 +713,29 @@ int mfx_device_info(mfx_ctx* ctx, int32_t* out, int32_t cap);
  * (0: no packets), out[18] = the spill buffer's entries per lane, out[19] = the lanes it holds,
  * out[20] = slots per chunk fetch, out[21] = 1 if k_shadow takes half chunks on small frames,
  * out[22] = the first iteration that moves paths to a ray queue (-1 never, -2 automatic),
- * out[23] = path slots of the pool at most (saturated at 2^31 - 1).                           */
-#define MFX_LAUNCH_INFO_N 24
+ * out[23] = path slots of the pool at most (saturated at 2^31 - 1).
+ * The camera cuts (camera packets that start from a per-tile cut of the BVH, cached per camera; off
+ * with MFX_CAMERA_CUTS=0, on two-level scenes and without camera packets): out[24] = 1 if they are in
+ * use, out[25] = entries per tile (MFX_CAMERA_CUT_CAP), out[26] = bytes of the table, and of the last
+ * table built on the primary device (0 before the first; the call waits for a build in flight):
+ * out[27] = 1000 x its mean cut length, out[28] = its longest cut, out[29] = its tiles whose cut is the
+ * root alone; out[30] = tables built so far, out[31] = the fewest samples of a trace that builds one
+ * (MFX_CAMERA_CUT_MIN_SAMPLES; a table that is already the camera's serves every trace).        */
+#define MFX_LAUNCH_INFO_N 32
 int mfx_launch_info(mfx_ctx* ctx, int32_t* out, int32_t cap);
+/* The primary device's camera-cut table for the current camera: rows [tile ty * tiles_x + tx][out[25]
+ * of mfx_launch_info] of 32-byte entries {int32 code, float lb, float lo[3], float hi[3]} (code >= 0 an
+ * internal node, < 0 a leaf, INT32_MIN after a row's last entry). host == 0: the device's table, built
+ * now if it is not this camera's; host != 0: the same routine run on the host over the host image (the
+ * two are equal byte for byte). *nbytes = the table's size; out may be NULL to ask for it alone.
+ * MFX_E_STATE when the context does not use cuts, MFX_E_INVALID: cap_bytes < *nbytes.           */
+int mfx_camera_cut_table(mfx_ctx* ctx, void* out, int64_t cap_bytes, int64_t* nbytes, int32_t host);
+/* The primary device's last camera-cut build (waits for one in flight; all 0 without cuts or before the
+ * first): out[0] = tables built so far, out[1] = the last build's device time in ms (HIP events),
+ * out[2] = the sum of its cut lengths, out[3] = the longest, out[4] = tiles whose cut is the root
+ * alone, out[5] = tiles with an empty cut, out[6] = film tiles, out[7] = entries per tile,
+ * out[8 + n] = tiles whose cut has n entries (n = 0 .. 16); the rest 0.                        */
+int mfx_camera_cut_info(mfx_ctx* ctx, double out[32]);
 
 /* ---- misc -------------------------------------------------------------------------------- */
 const char* mfx_last_error(void);

@@ -37,7 +37,8 @@ MFX_ABI_VERSION = 6
 LAUNCH_INFO_KEYS = ("stack_size", "stack_lds_ext", "stack_lds_shd", "spill_ext", "spill_shd", "ntop_ext", "ntop_shd",
                     "nslot_ext", "nslot_shd", "ninst_lds", "shadow_waves", "mega_waves", "lit_in_hit", "gray_light",
                     "camera_packets", "wf_ext_grid", "wf_shd_grid", "wf_cam_grid", "spill_entries_per_lane",
-                    "spill_lanes", "chunk", "shd_half", "queue_from", "pool_max")
+                    "spill_lanes", "chunk", "shd_half", "queue_from", "pool_max", "camera_cuts", "cut_cap",
+                    "cut_table_bytes", "cut_len_mean_x1000", "cut_len_max", "cut_root_tiles", "cut_builds", "cut_min_samples")
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MFX_LIB_PATH: another build of the same library (scripts' A/B and roof passes on a variant)
@@ -262,6 +263,8 @@ def _bind(lib, strict: bool = True):
         "mfx_build_info": (C.c_int, [C.c_void_p, _dp, _P(C.c_uint64)]),
         "mfx_device_info": (C.c_int, [C.c_void_p, _ip, C.c_int32]),
         "mfx_launch_info": (C.c_int, [C.c_void_p, _ip, C.c_int32]),
+        "mfx_camera_cut_info": (C.c_int, [C.c_void_p, _dp]),
+        "mfx_camera_cut_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int32]),
         "mfx_last_error": (C.c_char_p, []),
         "mfx_abi_version": (C.c_int, []),
         "mfx_device_count": (C.c_int, []),
@@ -280,7 +283,7 @@ EXPORTED_SYMBOLS = [
     "mfx_film_mean", "mfx_stats",
     "mfx_trace_accumulate", "mfx_accum_clear", "mfx_accum_reduce", "mfx_accum_device_ptr", "mfx_accum_attach", "mfx_accum_read_mean",
     "mfx_sync", "mfx_stream", "mfx_ray_counts", "mfx_last_trace_ms", "mfx_trace_timing", "mfx_ray_counts_total", "mfx_closest_hit", "mfx_any_hit", "mfx_ref_leaves",
-    "mfx_fp64_selftest", "mfx_aabb_selftest", "mfx_build_leaves", "mfx_build_info", "mfx_device_info", "mfx_launch_info", "mfx_last_error", "mfx_abi_version", "mfx_device_count",
+    "mfx_fp64_selftest", "mfx_aabb_selftest", "mfx_build_leaves", "mfx_build_info", "mfx_device_info", "mfx_launch_info", "mfx_camera_cut_table", "mfx_camera_cut_info", "mfx_last_error", "mfx_abi_version", "mfx_device_count",
 ]
 
 _lib = None

@@ -85,6 +85,9 @@ static CreateEnv read_create_env() {
     v.blocks_per_cu = num("MFX_BLOCKS_PER_CU");
     v.camera_packets = num("MFX_CAMERA_PACKETS");
     v.cam_blocks = num("MFX_CAM_BLOCKS");
+    v.camera_cuts = num("MFX_CAMERA_CUTS");
+    v.camera_cut_cap = num("MFX_CAMERA_CUT_CAP");
+    v.camera_cut_min_samples = num("MFX_CAMERA_CUT_MIN_SAMPLES");
     v.pool_fail_once = num("MFX_POOL_FAIL_ONCE");
     v.adaptive_check = num("MFX_ADAPTIVE_CHECK");
     v.iter_events = num("MFX_ITER_EVENTS");
@@ -114,6 +117,7 @@ static int largest_keeping(int lo, int hi, F keeps) {
 // The scene images of c->host in HBM, with the context's device current (ctx_setup at creation;
 // mfx_set_camera when the images are built again)
 static int scene_upload(mfx_ctx* c) {
+    c->image_gen += 1;  // (the camera cuts are the old image's)
     c->stack_size = std::max(1, c->host.stack_entries);
     if (c->stack_size > 96) return fail(MFX_E_INVALID, "mfx_create: BVH too deep for the LDS traversal stack");
     CK(upload(c->d_nodes, c->host.nodes));
@@ -225,7 +229,11 @@ static int scene_shapes(mfx_ctx* c) {
     {  // camera-ray packets (flat scenes)
         if (env.camera_packets.value_or(1) && !inst) {
             int cb = 0;
-            CK(mfx_cam_occupancy(c->stack_size, &cb));
+            // camera cuts (mfx_camera_cuts.h): on unless MFX_CAMERA_CUTS=0, MFX_CAMERA_CUT_CAP entries a tile
+            c->cuts.on = env.camera_cuts.value_or(1) != 0;
+            c->cuts.cap = std::max(1, std::min(env.camera_cut_cap.value_or(MFX_CUT_CAP_DEFAULT), MFX_CUT_CAP_MAX));
+            c->cuts.min_samples = std::max(1, env.camera_cut_min_samples.value_or(MFX_CUT_MIN_SAMPLES));
+            CK(mfx_cam_occupancy(c->stack_size, &cb, c->cuts.on));
             if (env.cam_blocks) cb = std::min(cb, std::max(1, *env.cam_blocks));
             c->wf_cam_grid = prop.multiProcessorCount * std::max(1, std::min(cb, 8));
         }
@@ -753,13 +761,60 @@ int mfx_launch_info(mfx_ctx* c, int32_t* out, int32_t cap) {
     if (cap < MFX_LAUNCH_INFO_N) return fail(MFX_E_INVALID, "mfx_launch_info: cap < MFX_LAUNCH_INFO_N");
     const WfParams& A = c->pool.params;
     const bool inst = !c->host.inst.empty();
+    const bool cuts = cuts_apply(c);
+    if (cuts) MFX_TRY(cuts_read_stats(c));
+    const CamCuts& K = c->cuts;
+    const int64_t tiles = (int64_t)((c->host.width + 7) / 8) * ((c->host.height + 7) / 8);
     const int32_t v[MFX_LAUNCH_INFO_N] = {
         c->stack_size, A.stack_lds_ext, A.stack_lds_shd, A.stack_lds_ext < c->stack_size, A.stack_lds_shd < c->stack_size,
         A.ntop_ext, A.ntop_shd, A.nslot_ext, A.nslot_shd, inst ? std::min<int>((int)c->host.inst.size(), WF_INST_LDS) : 0,
         A.shadow_waves, c->mega_waves, wf_lit_in_hit(c), wf_gray_light(c), !inst && c->wf_cam_grid > 0,
         c->wf_ext_grid, c->wf_shd_grid, inst ? 0 : c->wf_cam_grid, c->spill_deep, c->spill_lanes,
-        c->wf_chunk, c->wf_shd_half, c->pool.queue_from, (int32_t)std::min<int64_t>(c->pool.max, INT32_MAX)};
+        c->wf_chunk, c->wf_shd_half, c->pool.queue_from, (int32_t)std::min<int64_t>(c->pool.max, INT32_MAX),
+        cuts, cuts ? K.cap : 0, cuts ? (int32_t)std::min<int64_t>(tiles * K.cap * (int64_t)sizeof(MfxCutEntry), INT32_MAX) : 0,
+        (int32_t)(K.last.len_sum * 1000 / (unsigned long long)std::max<int64_t>(1, tiles)), (int32_t)K.last.len_max,
+        (int32_t)K.last.root_tiles, (int32_t)std::min<int64_t>(K.builds, INT32_MAX), cuts ? K.min_samples : 0};
     std::copy(v, v + MFX_LAUNCH_INFO_N, out);
+    return MFX_OK;
+}
+
+int mfx_camera_cut_table(mfx_ctx* c, void* out, int64_t cap_bytes, int64_t* nbytes, int32_t host) {
+    if (!c || !nbytes) return fail(MFX_E_INVALID, "mfx_camera_cut_table: null argument");
+    if (!cuts_apply(c)) return fail(MFX_E_STATE, "mfx_camera_cut_table: the context does not use camera cuts");
+    const size_t tiles = (size_t)((c->host.width + 7) / 8) * (size_t)((c->host.height + 7) / 8);
+    const size_t bytes = tiles * c->cuts.cap * sizeof(MfxCutEntry);
+    *nbytes = (int64_t)bytes;
+    if (!out) return MFX_OK;
+    if (cap_bytes < (int64_t)bytes) return fail(MFX_E_INVALID, "mfx_camera_cut_table: output too small");
+    if (host) {
+        std::vector<MfxCutEntry> t(tiles * c->cuts.cap);
+        MfxCutStats st;
+        mfx_cut::table_host(c->host.nodes.data(), c->host.camera, c->host.width, c->host.height, c->cuts.cap, t.data(), st);
+        std::memcpy(out, t.data(), bytes);
+        return MFX_OK;
+    }
+    HIPCHECK(hipSetDevice(c->device));
+    MFX_TRY(cuts_ensure(c));
+    HIPCHECK(hipMemcpyAsync(out, c->cuts.table, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    return MFX_OK;
+}
+
+int mfx_camera_cut_info(mfx_ctx* c, double out[32]) {
+    if (!c || !out) return fail(MFX_E_INVALID, "mfx_camera_cut_info: null argument");
+    for (int k = 0; k < 32; ++k) out[k] = 0.0;
+    if (!cuts_apply(c)) return MFX_OK;
+    MFX_TRY(cuts_read_stats(c));
+    const CamCuts& K = c->cuts;
+    out[0] = (double)K.builds;
+    out[1] = (double)K.last_ms;
+    out[2] = (double)K.last.len_sum;
+    out[3] = (double)K.last.len_max;
+    out[4] = (double)K.last.root_tiles;
+    out[5] = (double)K.last.empty_tiles;
+    out[6] = (double)((int64_t)((c->host.width + 7) / 8) * ((c->host.height + 7) / 8));
+    out[7] = (double)K.cap;
+    for (int n = 0; n <= MFX_CUT_CAP_MAX; ++n) out[8 + n] = (double)K.last.hist[n];
     return MFX_OK;
 }
 

@@ -7,6 +7,7 @@
 
 #include <vector>
 
+#include "mfx_camera_cuts.h"
 #include "mfx_layout.h"
 
 // The whole traversal image of a flat scene, built on the current HIP device: a binned-SAH BVH2
@@ -37,5 +38,11 @@ struct MfxGpuImages {
 };
 hipError_t mfx_gpu_build_images(const float* prim_box, const float* cent, const int32_t* weight, int n, int max_leaf,
                                 float c_isect, const MfxGpuLayoutIn& in, MfxGpuImages& out);
+
+// The camera cuts of a flat scene's node image for the camera in device memory (mfx_camera_cuts.h), enqueued on
+// st: table[tiles_y * tiles_x][cap] by the routine the host twin (mfx_cut::table_host) runs, so the same
+// bytes; stats_dev is zeroed and summed over the tiles.
+hipError_t mfx_build_cut_table(const MfxNode* nodes, const MfxCamera* cam_dev, int W, int H, int cap, MfxCutEntry* table,
+                               MfxCutStats* stats_dev, hipStream_t st);
 
 #endif

@@ -27,6 +27,7 @@
 #include <numeric>
 
 #include "mfx_build.h"
+#include "mfx_camera_cuts.h"
 
 namespace {
 
@@ -702,4 +703,51 @@ hipError_t mfx_gpu_build_images(const float* prim_box, const float* cent, const 
         if (p) (void)hipFree(p);
     bvh2_free(D);
     return e;
+}
+
+// ---- the camera cuts (mfx_camera_cuts.h): one thread per film tile runs the routine the host twin runs ----
+__global__ void __launch_bounds__(64) k_cut_table(const MfxNode* __restrict__ nodes, const MfxCamera* __restrict__ cam, int W, int H,
+                                                  int tiles_x, int ntiles, int cap, MfxCutEntry* __restrict__ table,
+                                                  MfxCutStats* __restrict__ stats) {
+    __shared__ MfxCutEntry lists[MFX_CUT_CAP_MAX * 64];  // the threads' working lists, entry i of thread t at [i * 64 + t]
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool valid = t < ntiles;
+    int n = -1;
+    bool root = false;
+    if (valid) {
+        MfxCutEntry* row = table + (size_t)t * cap;
+        n = mfx_cut::tile_cut(nodes, *cam, W, H, t % tiles_x, t / tiles_x, cap, row, lists + threadIdx.x, 64);
+        root = n == 1 && row[0].code == 0;
+    }
+    // the statistics: summed over the wave (a block is one wave), one atomic per counter and wave (an atomic
+    // per tile on the same few words serialises the whole launch)
+    int sum = valid ? n : 0, mx = sum;
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_xor(sum, off);
+        mx = max(mx, __shfl_xor(mx, off));
+    }
+    const unsigned long long roots = __popcll(__ballot(root));
+    for (int v = 0; v <= cap; ++v) {
+        const unsigned long long cnt = __popcll(__ballot(n == v));
+        if (threadIdx.x == 0 && cnt) {
+            atomicAdd(&stats->hist[v], cnt);
+            if (v == 0) atomicAdd(&stats->empty_tiles, cnt);
+        }
+    }
+    if (threadIdx.x == 0) {
+        atomicAdd(&stats->len_sum, (unsigned long long)sum);
+        atomicMax(&stats->len_max, (unsigned long long)mx);
+        if (roots) atomicAdd(&stats->root_tiles, roots);
+    }
+}
+
+hipError_t mfx_build_cut_table(const MfxNode* nodes, const MfxCamera* cam_dev, int W, int H, int cap, MfxCutEntry* table,
+                               MfxCutStats* stats_dev, hipStream_t st) {
+    const int tiles_x = (W + 7) / 8, ntiles = tiles_x * ((H + 7) / 8);
+    if (cap < 1 || cap > MFX_CUT_CAP_MAX || ntiles < 1) return hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(stats_dev, 0, sizeof(MfxCutStats), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_cut_table, dim3((ntiles + 63) / 64), dim3(64), 0, st, nodes, cam_dev, W, H, tiles_x, ntiles, cap, table,
+                       stats_dev);
+    return hipGetLastError();
 }

@@ -306,8 +306,31 @@ struct CreateEnv {
     using Int = std::optional<int>;
     bool node_f32 = false, diag_iter = false, no_gray_light = false, no_lit_in_hit = false;  // set at all
     Int mega_waves, shadow_target_blocks, stack_lds, ntop, slot_lds, shadow_waves, blocks_per_cu, camera_packets, cam_blocks;
+    Int camera_cuts, camera_cut_cap, camera_cut_min_samples;
     Int pool_fail_once, adaptive_check, iter_events, queue_from, qchunk, ray_queue, mega_chunk, shd_half, chunk;
     std::optional<int64_t> pool;
+};
+
+// The camera cuts of one device (mfx_camera_cuts.h): the table k_camera's CUTS instances start their packets
+// from, built lazily by cuts_for_trace (mfx_trace.cpp) on the context's stream for the device's current
+// camera and node image, and kept until either changes.
+struct CamCuts {
+    bool on = true;                  // MFX_CAMERA_CUTS=0: off
+    int cap = MFX_CUT_CAP_DEFAULT;   // MFX_CAMERA_CUT_CAP
+    int min_samples = MFX_CUT_MIN_SAMPLES;  // a trace of fewer samples does not pay a build (MFX_CAMERA_CUT_MIN_SAMPLES)
+    DevBuf<MfxCutEntry> table;       // [tiles_y * tiles_x][cap]
+    DevBuf<MfxCutStats> stats;
+    size_t entries = 0;              // allocated
+    // what the table was built for: mfx_set_camera changes the camera exactly when cam_epoch moves (on
+    // every device of a list), and every scene_upload takes a new image_gen
+    bool valid = false;
+    MfxCamera cam{};
+    uint64_t image_gen = 0;
+    int64_t builds = 0;
+    Event e0, e1;                    // around the last build
+    MfxCutStats last{};              // the last build's statistics, read back by mfx_launch_info
+    bool last_read = false;
+    float last_ms = 0.f;
 };
 
 // Multi-device (primary context only)
@@ -360,6 +383,8 @@ struct __attribute__((visibility("hidden"))) mfx_ctx {
     double frame_count = 0.0;
     uint64_t cam_epoch = 0;    // 0 after create, +1 per mfx_set_camera that changed the camera (primary)
     int64_t cam_rebuilds = 0;  // of which had to build the images again
+    uint64_t image_gen = 0;    // +1 per scene_upload on this device (a new node image)
+    mfxh::CamCuts cuts;
     mfxh::KeptScene kept;      // (primary)
     int grid = 0;
     int stack_size = 1;
@@ -461,6 +486,9 @@ int whole_film_single_device(const mfx_ctx* c, const char* who);
 
 // mfx_trace.cpp
 int wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, TraceMode mode = {});
+bool cuts_apply(const mfx_ctx* c);
+int cuts_ensure(mfx_ctx* c);
+int cuts_read_stats(mfx_ctx* c);
 int dev_trace_accumulate(mfx_ctx* c, int32_t spp, int64_t sample_base, ResolveSplit* split = nullptr);
 int settle_queue_auto(mfx_ctx* c);
 void note_live(mfx_ctx* c, const unsigned long long* h);

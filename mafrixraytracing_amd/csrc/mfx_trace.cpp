@@ -1,6 +1,7 @@
 // mfx_trace.cpp — the trace calls of the extern "C" boundary: the wavefront pool and its driver
 // (wf_trace), mfx_trace_accumulate, the multi-device reduce, the accumulator calls, trace timing and
 // the ray counters.
+#include "mfx_build.h"
 #include "mfx_ctx.h"
 
 using namespace mfxh;
@@ -155,6 +156,49 @@ static void fill_scene_params(mfx_ctx* c, WfParams& P) {
     P.nmat = (int32_t)(c->host.albedo.size() / 3);
 }
 
+// ---- camera cuts (mfx_camera_cuts.h): the per-device table and when it is built ----
+// a context whose camera rays run k_camera with cuts on (flat scenes, MFX_CAMERA_PACKETS and MFX_CAMERA_CUTS not 0)
+bool mfxh::cuts_apply(const mfx_ctx* c) { return c->host.inst.empty() && c->wf_cam_grid > 0 && c->cuts.on; }
+
+// The device's table for its current camera and node image, built on its stream if it is another's
+// (context creation, a camera change, a scene rebuild): every later launch on the stream sees it.
+int mfxh::cuts_ensure(mfx_ctx* c) {
+    CamCuts& K = c->cuts;
+    if (K.valid && K.image_gen == c->image_gen && std::memcmp(&K.cam, &c->host.camera, sizeof(MfxCamera)) == 0) return MFX_OK;
+    const size_t tiles = (size_t)((c->host.width + 7) / 8) * (size_t)((c->host.height + 7) / 8);
+    if (K.entries < tiles * K.cap) {
+        HIP_TRY(K.table.alloc(tiles * K.cap), _e == hipErrorOutOfMemory ? MFX_E_NOMEM : MFX_E_DEVICE, "camera cuts: ");
+        K.entries = tiles * K.cap;
+    }
+    if (!K.stats) {
+        HIPCHECK(K.stats.alloc(1));
+        HIPCHECK(K.e0.create());
+        HIPCHECK(K.e1.create());
+    }
+    K.valid = false;
+    HIPCHECK(hipEventRecord(K.e0, c->stream));
+    HIPCHECK(mfx_build_cut_table(c->d_nodes, c->d_cam, c->host.width, c->host.height, K.cap, K.table, K.stats, c->stream));
+    HIPCHECK(hipEventRecord(K.e1, c->stream));
+    K.cam = c->host.camera;
+    K.image_gen = c->image_gen;
+    K.valid = true;
+    K.builds += 1;
+    K.last_read = false;
+    return MFX_OK;
+}
+
+// the last build's statistics and time (waits for it)
+int mfxh::cuts_read_stats(mfx_ctx* c) {
+    CamCuts& K = c->cuts;
+    if (K.builds == 0 || K.last_read) return MFX_OK;
+    HIPCHECK(hipSetDevice(c->device));
+    HIPCHECK(hipEventSynchronize(K.e1));
+    HIPCHECK(hipEventElapsedTime(&K.last_ms, K.e0, K.e1));
+    HIPCHECK(hipMemcpy(&K.last, K.stats, sizeof(MfxCutStats), hipMemcpyDeviceToHost));
+    K.last_read = true;
+    return MFX_OK;
+}
+
 // The wavefront pipeline. The frame's path indices (sample-major, 8x8 tiles) are cut into
 // generations of at most pool.max paths; slot j of a generation holds path path_base + j. A
 // generation is max_depth + 1 iterations of (k_extend, k_shadow) — the primary ray and the
@@ -233,6 +277,19 @@ int mfxh::wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, TraceMode mode) 
     const bool stats = (c->flags & MFX_F_COUNT_STATS) != 0;
     P.cam_grid = c->host.inst.empty() ? c->wf_cam_grid : 0;
     if (own_events) c->cam_last = P.cam_grid > 0;
+    // camera cuts: a table that is already this camera's costs nothing; a trace of fewer than min_samples
+    // samples does not pay for a build and walks from the root (the break-even)
+    P.cuts = nullptr;
+    P.cut_cap = 0;
+    if (P.cam_grid > 0 && cuts_apply(c)) {
+        const CamCuts& K = c->cuts;
+        const bool have = K.valid && K.image_gen == c->image_gen && std::memcmp(&K.cam, &c->host.camera, sizeof(MfxCamera)) == 0;
+        if (have || ns >= K.min_samples) {
+            MFX_TRY(cuts_ensure(c));
+            P.cuts = K.table;
+            P.cut_cap = K.cap;
+        }
+    }
     const int64_t ngen = (total + gen_max - 1) / gen_max;
     const int per_gen = P.max_depth + 1;  // bounce-synchronous iterations per generation
     const int iters = (int)ngen * per_gen;

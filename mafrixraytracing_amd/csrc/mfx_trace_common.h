@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mfx_camera_cuts.h"
 #include "mfx_layout.h"
 
 // ----------------------------------------------------------------------------------------------
@@ -1127,14 +1128,15 @@ __device__ __forceinline__ int packet_node_step(const MfxNode* __restrict__ node
 // 128-B node each) and leaf slots (an 80-B test prefix each), counted on every lane alike.
 // PH (diagnostic builds, -DMFX_DIAG_STAMPS=3): ph[0] += the wave's cycles in node steps, ph[1] += in
 // leaf tests, ph[2] += node steps, ph[3] += leaf visits
+// The walk from `node` with the lanes of `mask`, on an empty stack, until the stack runs empty again: the
+// whole walk from the root, or one entry of a tile's cut (packet_walk_cuts). tMax is the query's, tlim
+// the lanes' current limits (they fall with every hit); rep is the lane whose distances order the children.
 template <bool STATS, bool PH, bool UNI>
-__device__ __forceinline__ void packet_walk(const SceneView& S, DV o, DV d, const RayF& rf, uint64_t mask, Best& B,
-                                            int* stk, uint64_t* stm, Stats& st, uint32_t& pk_nodes,
-                                            uint32_t& pk_slots, uint64_t* ph, const PacketPlanes& pp) {
-    const double tMax = B.t;  // (camera rays: 99999999., beyond every box, so no SceneView::tslack here)
-    float tlim = f_tlim(tMax);
-    const int rep = __builtin_ctzll(mask);
-    int sp = 0, node = 0;
+__device__ __forceinline__ void packet_walk_from(const SceneView& S, DV o, DV d, const RayF& rf, int node, uint64_t mask,
+                                                 const int rep, const double tMax, float& tlim, Best& B, int* stk,
+                                                 uint64_t* stm, Stats& st, uint32_t& pk_nodes, uint32_t& pk_slots,
+                                                 uint64_t* ph, const PacketPlanes& pp) {
+    int sp = 0;
     uint64_t t0 = 0;
     while (true) {
         if (PH) t0 = diag_clock();
@@ -1170,12 +1172,71 @@ __device__ __forceinline__ void packet_walk(const SceneView& S, DV o, DV d, cons
         }
     }
 }
+template <bool STATS, bool PH, bool UNI>
+__device__ __forceinline__ void packet_walk(const SceneView& S, DV o, DV d, const RayF& rf, uint64_t mask, Best& B,
+                                            int* stk, uint64_t* stm, Stats& st, uint32_t& pk_nodes,
+                                            uint32_t& pk_slots, uint64_t* ph, const PacketPlanes& pp) {
+    const double tMax = B.t;  // (camera rays: 99999999., beyond every box, so no SceneView::tslack here)
+    float tlim = f_tlim(tMax);
+    packet_walk_from<STATS, PH, UNI>(S, o, d, rf, 0, mask, __builtin_ctzll(mask), tMax, tlim, B, stk, stm, st, pk_nodes,
+                                     pk_slots, ph, pp);
+}
+#ifndef MFX_CUT_LB_CULL
+#define MFX_CUT_LB_CULL 1  // 0 (A/B builds): no cull by lb; every entry's box is still tested against the lanes' limits
+#endif
+// The walk started from the tile's cut (mfx_camera_cuts.h; DESIGN.md §3, "Camera cuts") instead of the
+// root: row[0 .. cap) are the tile's entries by ascending lb, MFX_CUT_END after the last. An entry is one
+// 32-B scalar load (the next one is asked for before this one is walked). Its box is the one its parent
+// node stores for it, so the lanes test it as the parent's node step would have (the same planes, the
+// same limit) and the entry's subtree is walked with the lanes that hit; a leaf entry goes straight to
+// its leaf test. The entries cover every leaf a ray of the tile can reach, and candidates may come in
+// any order and number (leaf_hit, Best), so every lane's closest hit is the walk from the root's.
+// The cull: lb bounds every lane's entry distance into the entry's box below, so when lb is above every
+// active lane's limit the node test's own rule (n <= f) fails for every lane; the entries are sorted,
+// so it fails for every later one too and the window ends.
+template <bool STATS, bool PH, bool UNI>
+__device__ __forceinline__ void packet_walk_cuts(const SceneView& S, DV o, DV d, const RayF& rf, const uint64_t mask, Best& B,
+                                                 int* stk, uint64_t* stm, Stats& st, uint32_t& pk_nodes,
+                                                 uint32_t& pk_slots, uint32_t& pk_cuts, uint64_t* ph,
+                                                 const PacketPlanes& pp, const MfxCutEntry* __restrict__ row, const int cap) {
+    const double tMax = B.t;
+    float tlim = f_tlim(tMax);
+    const int rep = __builtin_ctzll(mask);
+    mfx_ci4* q = (mfx_ci4*)row;
+    mfx_i4 e0 = q[0], e1 = q[1];
+    for (int i = 0; i < cap; ++i) {
+        const int code = e0.x;
+        if (code == MFX_CUT_END) break;
+        const float lb = __int_as_float(e0.y);
+        const float lox = __int_as_float(e0.z), loy = __int_as_float(e0.w), loz = __int_as_float(e1.x);
+        const float hix = __int_as_float(e1.y), hiy = __int_as_float(e1.z), hiz = __int_as_float(e1.w);
+        if (i + 1 < cap) {
+            e0 = q[2 * i + 2];
+            e1 = q[2 * i + 3];
+        }
+        if (STATS) pk_cuts++;
+        if (MFX_CUT_LB_CULL && (__builtin_amdgcn_ballot_w64(lb <= tlim) & mask) == 0) break;
+        uint64_t m = mask;
+        if (code != 0) {  // (the root has no box)
+            const float a0 = fmaf(lox, rf.ix, -rf.oix), a1 = fmaf(hix, rf.ix, -rf.oix);
+            const float b0 = fmaf(loy, rf.iy, -rf.oiy), b1 = fmaf(hiy, rf.iy, -rf.oiy);
+            const float c0 = fmaf(loz, rf.iz, -rf.oiz), c1 = fmaf(hiz, rf.iz, -rf.oiz);
+            const float n = fmaxf(fmaxf(fminf(a0, a1), fminf(b0, b1)), fmaxf(fminf(c0, c1), 0.0f));
+            const float f = fminf(fminf(fmaxf(a0, a1), fmaxf(b0, b1)), fminf(fmaxf(c0, c1), tlim));
+            m = __builtin_amdgcn_ballot_w64(n <= f) & mask;
+            if (m == 0) continue;
+        }
+        packet_walk_from<STATS, PH, UNI>(S, o, d, rf, code, m, rep, tMax, tlim, B, stk, stm, st, pk_nodes, pk_slots, ph, pp);
+    }
+}
 // the walk specialised on the packet's direction signs: one walk with the near / far columns of the
 // tile's octant when its active lanes agree on every axis, the general slab test otherwise
-template <bool STATS, bool PH = false>
+// CUTS: from the tile's cut (row, cap) instead of the root; pk_cuts counts its entry fetches (STATS)
+template <bool STATS, bool PH = false, bool CUTS = false>
 __device__ __forceinline__ void packet_closest(const SceneView& S, bool act, DV o, DV d, double tMax, Best& B,
                                                int* stk, uint64_t* stm, Stats& st, uint32_t& pk_nodes,
-                                               uint32_t& pk_slots, uint64_t* ph = nullptr) {
+                                               uint32_t& pk_slots, uint64_t* ph = nullptr,
+                                               const MfxCutEntry* row = nullptr, int cap = 0, uint32_t* pk_cuts = nullptr) {
     B = Best{tMax, -1, -1, false};
     const RayF rf = make_rayf(o, d);
     const uint64_t mask = __ballot(act);
@@ -1186,10 +1247,12 @@ __device__ __forceinline__ void packet_closest(const SceneView& S, bool act, DV 
     if (uni) {
         const int sx = nx ? 1 : 0, sy = ny ? 1 : 0, sz = nz ? 1 : 0;
         const PacketPlanes pp{sx, 1 - sx, 2 + sy, 3 - sy, 4 + sz, 5 - sz};
-        packet_walk<STATS, PH, true>(S, o, d, rf, mask, B, stk, stm, st, pk_nodes, pk_slots, ph, pp);
+        if constexpr (CUTS) packet_walk_cuts<STATS, PH, true>(S, o, d, rf, mask, B, stk, stm, st, pk_nodes, pk_slots, *pk_cuts, ph, pp, row, cap);
+        else packet_walk<STATS, PH, true>(S, o, d, rf, mask, B, stk, stm, st, pk_nodes, pk_slots, ph, pp);
     } else {
         const PacketPlanes pp{0, 1, 2, 3, 4, 5};
-        packet_walk<STATS, PH, false>(S, o, d, rf, mask, B, stk, stm, st, pk_nodes, pk_slots, ph, pp);
+        if constexpr (CUTS) packet_walk_cuts<STATS, PH, false>(S, o, d, rf, mask, B, stk, stm, st, pk_nodes, pk_slots, *pk_cuts, ph, pp, row, cap);
+        else packet_walk<STATS, PH, false>(S, o, d, rf, mask, B, stk, stm, st, pk_nodes, pk_slots, ph, pp);
     }
 }
 

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mfx_camera_cuts.h"
 #include "mfx_layout.h"
 
 #define WF_FREE 0
@@ -199,6 +200,11 @@ struct WfParams {
     const MfxLight* lights;  // [nlights] the device light table, pdf = (1 / area) / N
     int32_t nlights;
     uint8_t* vlt;            // [vertex][stride] a lit vertex's light (beside vmat; allocated with N >= 2 only)
+    // Camera cuts (mfx_camera_cuts.h): the context's table for the current camera and node image, rows
+    // [film tile ty * tiles_x + tx][cut_cap]. Set: a generation's camera rays run k_camera's CUTS instance,
+    // whose packets start from their tile's row; null: from the root.
+    const MfxCutEntry* cuts;
+    int32_t cut_cap;
 };
 #define WF_MAX_LIGHTS 64  // MFX_MAX_LIGHTS: a light index is 6 bits of k_shadow's pending flag word
 
@@ -268,8 +274,8 @@ struct WfLdsShape {
 hipError_t mfx_wf_kernel_occupancy(const WfLdsShape& s, int* blocks_per_cu);
 // resident blocks per CU of k_resolve's accumulator instance (ml: the several-light one)
 hipError_t mfx_wf_resolve_occupancy(bool ml, int* blocks_per_cu);
-// resident blocks per CU of k_camera (camera-ray packets)
-hipError_t mfx_cam_occupancy(int stack_size, int* blocks_per_cu);
+// resident blocks per CU of k_camera (camera-ray packets; cuts: its CUTS instance)
+hipError_t mfx_cam_occupancy(int stack_size, int* blocks_per_cu, bool cuts = false);
 // a ray queue's arrays (MFX_RAY_QUEUE): entries in the pool's shard ranges, counts per shard
 struct WfQueue {
     double *ox, *oy, *oz, *dx, *dy, *dz;

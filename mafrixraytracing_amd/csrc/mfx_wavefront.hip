@@ -755,7 +755,9 @@ __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
 #endif
 // LIST: the instance for a listed trace (adaptive sampling): a window's tile is one scalar load, and with
 // per-tile counts (WF_LIST_TILE_N) so is its count; a window past the tile's share has no active lane
-template <bool STATS, int LIST = WF_LIST_NONE>
+// CUTS: the packets start from their tile's cut (WfParams::cuts) instead of the root; the instance without
+// holds none of it
+template <bool STATS, int LIST = WF_LIST_NONE, bool CUTS = false>
 __global__ void __launch_bounds__(256, MFX_CAM_WAVES) k_camera(WfParams P) {
     extern __shared__ int lds_all[];
     const int lane = lane_id();
@@ -777,6 +779,7 @@ __global__ void __launch_bounds__(256, MFX_CAM_WAVES) k_camera(WfParams P) {
     uint32_t c_primary = 0;
     Stats st{0, 0, 0};
     uint32_t pk_nodes = 0, pk_slots = 0;  // STATS: the wave's own node and slot fetches (every lane counts them)
+    uint32_t pk_cuts = 0;                 // and, CUTS, its cut-entry fetches
 #if MFX_DIAG_STAMPS == 3
     // the wave's cycles per phase (window scan, camera ray, node steps, leaf tests, result writes) and
     // its node steps and leaf visits (scripts/camera_phases.py); the shipped build has none of it
@@ -804,6 +807,10 @@ __global__ void __launch_bounds__(256, MFX_CAM_WAVES) k_camera(WfParams P) {
         int x = 0, y = 0;
         int64_t smp = 0;
         path_pixel<LIST>(P, P.path_base + jw, x, y, smp);  // the window's first slot: its tile's corner
+        // the tile's row of the cut table (wave-uniform; read only by a window with an active lane)
+        const MfxCutEntry* row = nullptr;
+        if (CUTS)
+            row = P.cuts + (size_t)__builtin_amdgcn_readfirstlane((y >> 3) * ((P.width + 7) >> 3) + (x >> 3)) * (size_t)P.cut_cap;
         x += lane & 7;
         y += lane >> 3;
         // edge-tile padding starts no path
@@ -827,10 +834,11 @@ __global__ void __launch_bounds__(256, MFX_CAM_WAVES) k_camera(WfParams P) {
         Best B;
 #if MFX_DIAG_STAMPS == 3
         CAM_MARK(t_gen);
-        packet_closest<STATS, true>(S, act, o, d, 99999999., B, stk, stm, st, pk_nodes, pk_slots, ph);
+        packet_closest<STATS, true, CUTS>(S, act, o, d, 99999999., B, stk, stm, st, pk_nodes, pk_slots, ph, row, P.cut_cap, &pk_cuts);
         t_last = stamp();
 #else
-        packet_closest<STATS>(S, act, o, d, 99999999., B, stk, stm, st, pk_nodes, pk_slots);  // Integrators.fs:108
+        packet_closest<STATS, false, CUTS>(S, act, o, d, 99999999., B, stk, stm, st, pk_nodes, pk_slots, nullptr, row, P.cut_cap,
+                                           &pk_cuts);  // Integrators.fs:108
 #endif
         if (act) {
             if (B.found) {
@@ -864,6 +872,10 @@ __global__ void __launch_bounds__(256, MFX_CAM_WAVES) k_camera(WfParams P) {
         // packet fetches, once per wave (lane 0's count): mfx_ray_counts out[10], out[11]
         block_add<4>(cnt + 10, lane == 0 ? pk_nodes : 0u, red);
         block_add<4>(cnt + 11, lane == 0 ? pk_slots : 0u, red);
+#if MFX_DIAG_STAMPS != 3
+        // and the cut entries the wave read (32 B each): out[12]; not part of the fetch index above
+        if (CUTS) block_add<4>(cnt + 12, lane == 0 ? pk_cuts : 0u, red);
+#endif
     }
 }
 
@@ -1584,7 +1596,7 @@ static_assert(built_count(extend_built) == (MFX_NODE_F16 ? 64 : 60) &&
               "(k_shadow: 152 / 144 one-light instances, plus the several-light ones, ML: every spill, scene kind, "
               "queue and list of the 4-wave build without counters, 36, and the FP16 format of the 4 flat unlisted ones)");
 
-enum { WF_K_EXTEND, WF_K_SHADOW, WF_K_CAMERA };
+enum { WF_K_EXTEND, WF_K_SHADOW, WF_K_CAMERA, WF_K_CAMERA_CUTS };
 template <int KERNEL, int I>
 static const void* instance_at() {
     constexpr WfKey k = key_at(I);
@@ -1594,6 +1606,8 @@ static const void* instance_at() {
         return (const void*)k_shadow<k.stats, k.spill, k.waves, k.sk, k.queue, k.list, k.nf, k.ml>;
     else if constexpr (KERNEL == WF_K_CAMERA && camera_built(k))
         return (const void*)k_camera<k.stats, k.list>;
+    else if constexpr (KERNEL == WF_K_CAMERA_CUTS && camera_built(k))  // every k_camera instance has its CUTS twin
+        return (const void*)k_camera<k.stats, k.list, true>;
     else
         return nullptr;
 }
@@ -1605,7 +1619,11 @@ static const void* instance(const WfKey& k, std::index_sequence<I...>) {
 // a key's kernel (null: not built)
 static const void* extend_kernel(const WfKey& k) { return instance<WF_K_EXTEND>(k, std::make_index_sequence<WF_KEYS>{}); }
 static const void* shadow_kernel(const WfKey& k) { return instance<WF_K_SHADOW>(k, std::make_index_sequence<WF_KEYS>{}); }
-static const void* camera_kernel(const WfKey& k) { return instance<WF_K_CAMERA>(k, std::make_index_sequence<WF_KEYS>{}); }
+// (cuts: the twin that starts from the cut table, WfParams::cuts set; not a key field, k_camera alone has it)
+static const void* camera_kernel(const WfKey& k, bool cuts) {
+    return cuts ? instance<WF_K_CAMERA_CUTS>(k, std::make_index_sequence<WF_KEYS>{})
+                : instance<WF_K_CAMERA>(k, std::make_index_sequence<WF_KEYS>{});
+}
 
 // the key of k_extend or k_shadow holding shape s
 static WfKey shape_key(const WfLdsShape& s, bool stats, bool queue, bool start, int list, int waves) {
@@ -1635,8 +1653,8 @@ static size_t cam_lds_bytes(int stack_size) {
     return (size_t)4 * stack_size * (sizeof(int) + sizeof(uint64_t)) + 64 + sizeof(MfxCamera) + sizeof(SceneRefs);
 }
 
-hipError_t mfx_cam_occupancy(int stack_size, int* blocks_per_cu) {
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, camera_kernel(camera_key(false, WF_LIST_NONE)), 256,
+hipError_t mfx_cam_occupancy(int stack_size, int* blocks_per_cu, bool cuts) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, camera_kernel(camera_key(false, WF_LIST_NONE), cuts), 256,
                                                         cam_lds_bytes(stack_size));
 }
 
@@ -1657,7 +1675,7 @@ static hipError_t launch_iteration(const WfParams& P, int ext_grid, int shd_grid
                                    hipEvent_t* ev) {
     const int list = list_kind(P.ntiles, P.tile_n);
     if (!P.inst && P.start && P.cam_grid > 0) {  // camera rays as packets
-        launch(camera_kernel(camera_key(stats, list)), P.cam_grid, cam_lds_bytes(P.stack_size), st, P);
+        launch(camera_kernel(camera_key(stats, list), P.cuts != nullptr), P.cam_grid, cam_lds_bytes(P.stack_size), st, P);
     } else {
         const WfLdsShape s = lds_shape(P, false);
         const bool queue = P.qcount != nullptr, start = !queue && P.start;

@@ -378,8 +378,26 @@ class NativeContext:
         flags are bools, the rest ints."""
         out = np.zeros(len(LAUNCH_INFO_KEYS), dtype=np.int32)
         check(self.lib.mfx_launch_info(self._h, iptr(out), len(out)), "mfx_launch_info")
-        flags = ("spill_ext", "spill_shd", "lit_in_hit", "gray_light", "camera_packets", "shd_half")
+        flags = ("spill_ext", "spill_shd", "lit_in_hit", "gray_light", "camera_packets", "shd_half", "camera_cuts")
         return {k: bool(v) if k in flags else int(v) for k, v in zip(LAUNCH_INFO_KEYS, out)}
+
+    def camera_cut_info(self) -> dict:
+        """mfx_camera_cut_info: the last camera-cut build of the primary device."""
+        out = np.zeros(32)
+        check(self.lib.mfx_camera_cut_info(self._h, dptr(out)), "mfx_camera_cut_info")
+        return {"builds": int(out[0]), "build_ms": float(out[1]), "len_sum": int(out[2]), "len_max": int(out[3]),
+                "root_tiles": int(out[4]), "empty_tiles": int(out[5]), "tiles": int(out[6]), "cap": int(out[7]),
+                "hist": [int(v) for v in out[8:25]]}
+
+    def camera_cut_table(self, host: bool = False) -> np.ndarray:
+        """mfx_camera_cut_table: the camera-cut table for the current camera as bytes, [tiles][cut_cap][32];
+        host=True: the host twin's."""
+        n = C.c_int64()
+        check(self.lib.mfx_camera_cut_table(self._h, None, 0, C.byref(n), int(host)), "mfx_camera_cut_table")
+        out = np.zeros(n.value, dtype=np.uint8)
+        check(self.lib.mfx_camera_cut_table(self._h, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n), int(host)),
+              "mfx_camera_cut_table")
+        return out.reshape(-1, self.launch_info()["cut_cap"], 32)
 
     def light_info(self) -> np.ndarray:
         """mfx_light_info: [0] lights N, [1] 1 if the several-light kernel instances run, [2] bytes of the

@@ -10,4 +10,4 @@ OUT=${MFX_VARIANT_DIR:-$R/build_variants}  # (build_ab/: A/B candidates, scripts
 mkdir -p $OUT
 cd $SRC
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Wall -Wno-unused-result \
-  -I$R/include "$@" -shared -o $OUT/$NAME.so $(ls *.cpp *.hip | grep -v '^scene_digest\.cpp$') -ldl  # (scene_digest: a host tool with its own main)
+  -I$R/include "$@" -shared -o $OUT/$NAME.so $(ls *.cpp *.hip | grep -v -E '^(scene_digest|cut_check)\.cpp$') -ldl  # (scene_digest, cut_check: host tools with their own main)
