@@ -734,7 +734,11 @@ int mfx_camera_cut_table(mfx_ctx* ctx, void* out, int64_t cap_bytes, int64_t* nb
  * first): out[0] = tables built so far, out[1] = the last build's device time in ms (HIP events),
  * out[2] = the sum of its cut lengths, out[3] = the longest, out[4] = tiles whose cut is the root
  * alone, out[5] = tiles with an empty cut, out[6] = film tiles, out[7] = entries per tile,
- * out[8 + n] = tiles whose cut has n entries (n = 0 .. 16); the rest 0.                        */
+ * out[8 + n] = tiles whose cut has n entries (n = 0 .. 16); the per-tile slot cull, over the leaf
+ * entries the cuts took in: out[25] = their slots, out[26] = slots their entries no longer hold,
+ * out[27] = entries dropped whole, out[28] = entries narrowed (all 0 for a table built without the
+ * cull: one whose camera has served fewer than MFX_CAMERA_CUT_CULL_MIN_SAMPLES samples, 128 by
+ * default), out[29] = 1 if the current table was built with the cull; the rest 0.              */
 int mfx_camera_cut_info(mfx_ctx* ctx, double out[32]);
 
 /* ---- misc -------------------------------------------------------------------------------- */

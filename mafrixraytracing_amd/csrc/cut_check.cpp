@@ -8,7 +8,14 @@
 // pixel 16 jitters, the four pixel corners among them: the ray by k_camera's FP64 expressions, the BVH4
 // walked with the packet walk's FP32 slab test and no distance limit; every leaf reached must be covered by
 // an entry of its tile's cut (itself or an ancestor), and that entry's lb must not exceed the ray's FP32
-// entry distance to the entry's box. Exit status 1 on any failure.
+// entry distance to the entry's box. With the slot cull a leaf entry may hold a part of its leaf's slots, or
+// be dropped: a reached leaf under no internal entry has every slot put to the host's restatement of the exact
+// test (tri_hit64 / sphere_hit64, the ray's FP64 origin and direction, tMin 1e-6, tMax 99999999), and every
+// slot it accepts must lie in the kept range of a leaf entry of the tile's row: none may be lost. Besides the
+// soup and the mesh, scenes made against the cull for each film: triangles and rects with an edge through a
+// tile's corner ray, along a tile's side (its own and the widened one), edge-on to a ray of the tile (the
+// divisor changes sign across it; the camera lies on their plane), with a vertex at the camera, and nearly so.
+// Exit status 1 on any failure.
 #include <algorithm>
 #include <cfloat>
 #include <cinttypes>
@@ -101,6 +108,71 @@ std::vector<mfx_prim> soup(int n, uint64_t seed) {
     return v;
 }
 
+// Primitives placed against the slot cull for the camera `def` on a W x H film: per chosen tile, with P(px, py,
+// r) the point at r times the unnormalised direction through film point (px, py) (these points lie in planes
+// parallel to the film, so a segment between two of one r maps to a segment of the film),
+//  - a triangle with an edge through the tile's corner ray, and one with an edge through the widened corner's;
+//  - triangles with an edge along the tile's left side, along the widened left side and along its top side;
+//  - a rect with a side along the tile's right side;
+//  - edge-on triangles: their plane holds the camera position and the ray through the tile's middle (the
+//    divisor changes sign across the tile), exactly and lifted off that plane by 1e-12, 1e-9 and 1e-5;
+//  - triangles with a vertex at the camera position, and 1e-9 from it.
+// 60 random soup primitives give the BVH some depth.
+std::vector<mfx_prim> adversarial(const mfx_pinhole& def, int W, int H) {
+    MfxCamera cam;
+    mfx_derive_camera(def, cam);
+    std::vector<mfx_prim> v = soup(60, 61);
+    const auto P = [&](double px, double py, double r, double* out) {
+        const mfx_cut::V3 c = mfx_cut::film_dir(cam, px, py, W, H);
+        out[0] = cam.position[0] + r * c.x; out[1] = cam.position[1] + r * c.y; out[2] = cam.position[2] + r * c.z;
+    };
+    const auto tri = [&](const double* a, const double* b, const double* c) {
+        mfx_prim p;
+        std::memset(&p, 0, sizeof(p));
+        p.kind = MFX_PRIM_TRIANGLE;
+        p.material = (int)(v.size() % 3);
+        std::memcpy(p.p[0], a, 24); std::memcpy(p.p[1], b, 24); std::memcpy(p.p[2], c, 24);
+        v.push_back(p);
+    };
+    const int tiles_x = (W + 7) / 8, tiles_y = (H + 7) / 8;
+    const int picks[3][2] = {{0, 0}, {tiles_x / 2, tiles_y / 2}, {tiles_x - 1, tiles_y - 1}};  // the last one is padded
+    for (const auto& pk : picks) {
+        const double x0 = pk[0] * 8, y0 = pk[1] * 8, x1 = std::min<double>(x0 + 8, W), y1 = std::min<double>(y0 + 8, H);
+        const double xm = 0.5 * (x0 + x1), ym = 0.5 * (y0 + y1);
+        double a[3], b[3], c[3], d[3];
+        for (const double w : {0.0, 1.0}) {  // the tile's own corner, the widened one
+            P(x0 - w - 3, y0 - w - 2, 2.0, a); P(x0 - w + 3, y0 - w + 2, 2.0, b); P(x0 - w - 6, y0 - w + 7, 2.0, c);
+            tri(a, b, c);
+            tri(b, a, c);  // and facing the other way
+        }
+        for (const double w : {0.0, 1.0}) {  // along the left side, away from the tile and over it
+            P(x0 - w, y0 - 5, 2.5, a); P(x0 - w, y1 + 5, 2.5, b);
+            P(x0 - w - 9, ym, 2.5, c); tri(a, b, c);
+            P(x0 - w + 9, ym, 2.5, c); tri(a, b, c);
+        }
+        P(x0 - 4, y0, 3.0, a); P(x1 + 4, y0, 3.0, b); P(xm, y0 - 7, 3.0, c); tri(a, b, c);  // along the top side
+        {  // a rect beside the tile, one side along the tile's right side
+            mfx_prim p;
+            std::memset(&p, 0, sizeof(p));
+            p.kind = MFX_PRIM_RECT;
+            P(x1, y0, 2.2, a); P(x1 + 6, y0, 2.2, b); P(x1 + 6, y1, 2.2, c); P(x1, y1, 2.2, d);
+            std::memcpy(p.p[0], a, 24); std::memcpy(p.p[1], b, 24); std::memcpy(p.p[2], c, 24); std::memcpy(p.p[3], d, 24);
+            v.push_back(p);
+        }
+        for (const double lift : {0.0, 1e-12, 1e-9, 1e-5}) {  // edge-on: the plane through the camera and the middle ray
+            P(xm, ym, 1.5, a); P(xm, ym, 3.0, b); P(xm + 4, ym + 1, 2.0, c);
+            c[1] += lift;
+            tri(a, b, c);
+        }
+        for (const double off : {0.0, 1e-9}) {  // a vertex at the camera
+            a[0] = cam.position[0] + off; a[1] = cam.position[1]; a[2] = cam.position[2];
+            P(x0 - 2, y0 - 2, 2.0, b); P(x1 + 2, ym, 2.0, c);
+            tri(a, b, c);
+        }
+    }
+    return v;
+}
+
 bool load_prims(const char* path, std::vector<mfx_prim>& v) {
     FILE* f = std::fopen(path, "rb");
     if (!f) return false;
@@ -145,16 +217,86 @@ bool slab(const MfxNode& nd, int k, const RayF& r, float& n) {
 
 struct Totals {
     long long rays = 0, leaves = 0, uncovered = 0, lb_above = 0, tiles = 0, root = 0, empty = 0, multi = 0;
+    long long accepted = 0, lost = 0, slots_seen = 0, slots_culled = 0, dropped = 0, narrowed = 0;
 };
 
+// the entry of an internal node or the root; for a leaf's child word, the leaf entry that holds a part of
+// its slots (leaves are disjoint runs of slots, so at most one does)
 int find_entry(const MfxCutEntry* row, int cap, int code) {
-    for (int i = 0; i < cap && row[i].code != MFX_CUT_END; ++i)
+    for (int i = 0; i < cap && row[i].code != MFX_CUT_END; ++i) {
         if (row[i].code == code) return i;
+        if (code < 0 && row[i].code < 0) {
+            const int lc = ~code, ec = ~row[i].code;
+            if ((ec >> 3) >= (lc >> 3) && (ec >> 3) + (ec & 7) <= (lc >> 3) + (lc & 7)) return i;
+        }
+    }
     return -1;
 }
 
+// tri_hit64 / sphere_hit64 (mfx_trace_common.h) on the host: the same operations in the same order
+struct D3 {
+    double x, y, z;
+};
+D3 d3(const double* p) { return {p[0], p[1], p[2]}; }
+D3 vsub(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+double vdot(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+D3 vcross(D3 a, D3 v) { return {a.y * v.z - a.z * v.y, a.z * v.x - a.x * v.z, a.x * v.y - a.y * v.x}; }
+bool tri_hit64(const MfxSlot& s, D3 o, D3 d, double tMin) {
+    const D3 e1 = d3(s.b), e2 = d3(s.c);
+    const D3 s1 = vcross(d, e2);
+    const double divisor = vdot(s1, e1);
+    if (std::fabs(divisor) < 1e-6) return false;
+    const double inv = 1. / divisor;
+    const D3 dd = vsub(o, d3(s.a));
+    const double b1 = vdot(dd, s1) * inv;
+    if (b1 < 0. || b1 > 1.) return false;
+    const D3 s2 = vcross(dd, e1);
+    const double b2 = vdot(d, s2) * inv;
+    if (b2 < 0. || (b1 + b2) >= 1.) return false;
+    const double t = vdot(e2, s2) * inv;
+    return t > tMin;
+}
+bool sphere_hit64(const MfxSlot& s, D3 o, D3 d, double tMin, double tMax) {
+    const D3 oc = vsub(o, d3(s.a));
+    const double a = 1.;
+    const double b = 2.0 * vdot(oc, d);
+    const double c = vdot(oc, oc) - s.b[0] * s.b[0];
+    const double disc = b * b - 4.0 * a * c;
+    if (disc > 0) {
+        const double rd = std::sqrt(disc);
+        const double q = (b < 0.) ? -0.5 * (b - rd) : -0.5 * (b + rd);
+        const double t0 = q, t1 = c / q;
+        const double tmn = t0 < t1 ? t0 : t1, tmx = t0 > t1 ? t0 : t1;
+        if (tmn >= tMin && tmn < tMax) return true;
+        if (tmx > tMin && tmx < tMax) return true;
+    }
+    return false;
+}
+
+// a reached leaf under no internal entry: every slot the exact test accepts lies in the kept range of the
+// leaf's entry (cov, -1: the entry was dropped)
+void check_leaf_slots(const std::vector<MfxSlot>& slots, int child, const double* o, const double* d, const MfxCutEntry* row,
+                      int cov, Totals& t) {
+    const int lc = ~child, s0 = lc >> 3, n = (lc & 7) + 1;
+    int k0 = 0, k1 = 0;  // the kept range, as slot indices
+    if (cov >= 0) {
+        const int ec = ~row[cov].code;
+        k0 = ec >> 3;
+        k1 = k0 + (ec & 7) + 1;
+    }
+    for (int k = 0; k < n; ++k) {
+        const MfxSlot& sl = slots[s0 + k];
+        const int kind = (sl.info >> MFX_INFO_KIND_SHIFT) & 3;
+        const bool hit = kind == MFX_KIND_SPHERE ? sphere_hit64(sl, d3(o), d3(d), 1e-6, 99999999.) : tri_hit64(sl, d3(o), d3(d), 1e-6);
+        if (!hit) continue;
+        ++t.accepted;
+        if (s0 + k < k0 || s0 + k >= k1) ++t.lost;
+    }
+}
+
 // one ray against its tile's row
-void check_ray(const std::vector<MfxNode>& nodes, const RayF& r, const MfxCutEntry* row, int cap, Totals& t) {
+void check_ray(const std::vector<MfxNode>& nodes, const std::vector<MfxSlot>& slots, const RayF& r, const double* o,
+               const double* d, const MfxCutEntry* row, int cap, Totals& t) {
     struct Item {
         int node, cov;
     };
@@ -168,6 +310,7 @@ void check_ray(const std::vector<MfxNode>& nodes, const RayF& r, const MfxCutEnt
             float n = 0.f;
             if (!slab(nd, k, r, n)) continue;
             int cov = it.cov;
+            const bool above = cov < 0;  // no internal entry above this child
             if (cov < 0) {
                 cov = find_entry(row, cap, nd.child[k]);
                 if (cov >= 0 && !(row[cov].lb <= n)) ++t.lb_above;
@@ -176,7 +319,10 @@ void check_ray(const std::vector<MfxNode>& nodes, const RayF& r, const MfxCutEnt
                 stack.push_back({nd.child[k], cov});
             } else {
                 ++t.leaves;
-                if (cov < 0) ++t.uncovered;
+                // a leaf of its own: covered by what its entry keeps (a dropped entry keeps nothing); without
+                // the slot cull an entry is never dropped, and a missing one is a reached leaf not covered
+                if (above) check_leaf_slots(slots, nd.child[k], o, d, row, cov, t);
+                if (cov < 0 && !MFX_CUT_SLOT_CULL) ++t.uncovered;
             }
         }
     }
@@ -187,8 +333,10 @@ void check_case(const char* scene, const char* camname, const MfxHostScene& s, c
     const int tiles_x = (W + 7) / 8, tiles_y = (H + 7) / 8;
     std::vector<MfxCutEntry> table((size_t)tiles_x * tiles_y * cap);
     MfxCutStats st;
-    mfx_cut::table_host(s.nodes.data(), cam, W, H, cap, table.data(), st);
+    mfx_cut::table_host(s.nodes.data(), s.slots.data(), cam, W, H, cap, table.data(), st);
     Totals t;
+    t.slots_seen = (long long)st.slots_seen; t.slots_culled = (long long)st.slots_culled;
+    t.dropped = (long long)st.leaves_dropped; t.narrowed = (long long)st.leaves_narrowed;
     t.tiles = (long long)tiles_x * tiles_y;
     t.root = (long long)st.root_tiles;
     t.empty = (long long)st.empty_tiles;
@@ -211,16 +359,18 @@ void check_case(const char* scene, const char* camname, const MfxHostScene& s, c
                 if (l != 0.0)
                     for (int a = 0; a < 3; ++a) d[a] = d[a] / l;
                 ++t.rays;
-                check_ray(s.nodes, make_rayf(o, d), row, cap, t);
+                check_ray(s.nodes, s.slots, make_rayf(o, d), o, d, row, cap, t);
             }
         }
     std::printf("%s %s %dx%d cap=%d: tiles=%lld root=%lld empty=%lld multi=%lld mean_len=%.3f max_len=%llu rays=%lld leaves=%lld"
-                " uncovered=%lld lb_above=%lld\n",
+                " uncovered=%lld lb_above=%lld accepted=%lld lost=%lld slots_seen=%lld slots_culled=%lld dropped=%lld narrowed=%lld\n",
                 scene, camname, W, H, cap, t.tiles, t.root, t.empty, t.multi, (double)st.len_sum / (double)t.tiles, st.len_max,
-                t.rays, t.leaves, t.uncovered, t.lb_above);
+                t.rays, t.leaves, t.uncovered, t.lb_above, t.accepted, t.lost, t.slots_seen, t.slots_culled, t.dropped, t.narrowed);
     if (root_share) *root_share = (double)t.root / (double)t.tiles;
     all.rays += t.rays; all.leaves += t.leaves; all.uncovered += t.uncovered; all.lb_above += t.lb_above;
     all.tiles += t.tiles; all.root += t.root; all.empty += t.empty; all.multi += t.multi;
+    all.accepted += t.accepted; all.lost += t.lost; all.slots_seen += t.slots_seen; all.slots_culled += t.slots_culled;
+    all.dropped += t.dropped; all.narrowed += t.narrowed;
 }
 
 bool build(const std::vector<mfx_prim>& prims, const mfx_pinhole& cam, MfxHostScene& s) {
@@ -290,7 +440,7 @@ int distribution(const std::vector<mfx_prim>& prims, const mfx_pinhole& def, int
     for (const int cap : {MFX_CUT_CAP_MAX, MFX_CUT_CAP_DEFAULT}) {
         std::vector<MfxCutEntry> table((size_t)tiles * cap);
         MfxCutStats st;
-        mfx_cut::table_host(s.nodes.data(), cam, W, H, cap, table.data(), st);
+        mfx_cut::table_host(s.nodes.data(), s.slots.data(), cam, W, H, cap, table.data(), st);
         long long internal = 0, entries = 0;
         for (const MfxCutEntry& e : table)
             if (e.code != MFX_CUT_END) {
@@ -302,6 +452,11 @@ int distribution(const std::vector<mfx_prim>& prims, const mfx_pinhole& def, int
                     entries ? (double)internal / (double)entries : 0.0);
         for (int n = 0; n <= cap; ++n) std::printf(" %d:%llu", n, st.hist[n]);
         std::printf("\n");
+        // the slot cull: (tile, leaf-entry slot) pairs the cuts took in, the share their entries no longer hold
+        std::printf("%dx%d cap=%d slot_cull=%d leaf_entry_slots=%llu culled=%llu culled_share=%.4f entries_dropped=%llu"
+                    " entries_narrowed=%llu\n",
+                    W, H, cap, MFX_CUT_SLOT_CULL, st.slots_seen, st.slots_culled,
+                    st.slots_seen ? (double)st.slots_culled / (double)st.slots_seen : 0.0, st.leaves_dropped, st.leaves_narrowed);
     }
     return 0;
 }
@@ -325,11 +480,23 @@ int main(int argc, char** argv) {
     }
     Totals all;
     int bad = check_scene("soup_600", soup(600, 600), soup_cam, false, all);
+    bad += check_scene("adv_40x24", adversarial(soup_cam, 40, 24), soup_cam, false, all);
+    bad += check_scene("adv_17x9", adversarial(soup_cam, 17, 9), soup_cam, false, all);
     if (!mesh.empty()) bad += check_scene("mesh", mesh, spot_cam, true, all);
-    std::printf("total: rays=%lld leaves=%lld uncovered=%lld lb_above=%lld tiles=%lld root=%lld empty=%lld multi=%lld\n", all.rays,
-                all.leaves, all.uncovered, all.lb_above, all.tiles, all.root, all.empty, all.multi);
+    std::printf("total: rays=%lld leaves=%lld uncovered=%lld lb_above=%lld tiles=%lld root=%lld empty=%lld multi=%lld accepted=%lld"
+                " lost=%lld slots_seen=%lld slots_culled=%lld dropped=%lld narrowed=%lld\n",
+                all.rays, all.leaves, all.uncovered, all.lb_above, all.tiles, all.root, all.empty, all.multi, all.accepted, all.lost,
+                all.slots_seen, all.slots_culled, all.dropped, all.narrowed);
     if (all.uncovered || all.lb_above) {
         std::printf("FAIL: a reached leaf is not covered, or an entry's lb is above a ray's entry distance\n");
+        ++bad;
+    }
+    if (all.lost) {
+        std::printf("FAIL: a slot the exact test accepts lies outside its tile's kept ranges\n");
+        ++bad;
+    }
+    if (all.accepted == 0 || (MFX_CUT_SLOT_CULL && (all.slots_culled == 0 || all.dropped == 0 || all.narrowed == 0))) {
+        std::printf("FAIL: vacuous (no slot accepted, or the slot cull culled, dropped or narrowed nothing)\n");
         ++bad;
     }
     if (all.empty == 0 || all.multi == 0 || all.leaves == 0) {

@@ -88,6 +88,7 @@ static CreateEnv read_create_env() {
     v.camera_cuts = num("MFX_CAMERA_CUTS");
     v.camera_cut_cap = num("MFX_CAMERA_CUT_CAP");
     v.camera_cut_min_samples = num("MFX_CAMERA_CUT_MIN_SAMPLES");
+    v.camera_cut_cull_min_samples = num("MFX_CAMERA_CUT_CULL_MIN_SAMPLES");
     v.pool_fail_once = num("MFX_POOL_FAIL_ONCE");
     v.adaptive_check = num("MFX_ADAPTIVE_CHECK");
     v.iter_events = num("MFX_ITER_EVENTS");
@@ -233,6 +234,7 @@ static int scene_shapes(mfx_ctx* c) {
             c->cuts.on = env.camera_cuts.value_or(1) != 0;
             c->cuts.cap = std::max(1, std::min(env.camera_cut_cap.value_or(MFX_CUT_CAP_DEFAULT), MFX_CUT_CAP_MAX));
             c->cuts.min_samples = std::max(1, env.camera_cut_min_samples.value_or(MFX_CUT_MIN_SAMPLES));
+            c->cuts.cull_min_samples = std::max(1, env.camera_cut_cull_min_samples.value_or(MFX_CUT_CULL_MIN_SAMPLES));
             CK(mfx_cam_occupancy(c->stack_size, &cb, c->cuts.on));
             if (env.cam_blocks) cb = std::min(cb, std::max(1, *env.cam_blocks));
             c->wf_cam_grid = prop.multiProcessorCount * std::max(1, std::min(cb, 8));
@@ -789,12 +791,12 @@ int mfx_camera_cut_table(mfx_ctx* c, void* out, int64_t cap_bytes, int64_t* nbyt
     if (host) {
         std::vector<MfxCutEntry> t(tiles * c->cuts.cap);
         MfxCutStats st;
-        mfx_cut::table_host(c->host.nodes.data(), c->host.camera, c->host.width, c->host.height, c->cuts.cap, t.data(), st);
+        mfx_cut::table_host(c->host.nodes.data(), c->host.slots.data(), c->host.camera, c->host.width, c->host.height, c->cuts.cap, t.data(), st);
         std::memcpy(out, t.data(), bytes);
         return MFX_OK;
     }
     HIPCHECK(hipSetDevice(c->device));
-    MFX_TRY(cuts_ensure(c));
+    MFX_TRY(cuts_ensure(c, INT64_MAX));  // (the table with the slot cull, as the host twin's)
     HIPCHECK(hipMemcpyAsync(out, c->cuts.table, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(hipStreamSynchronize(c->stream));
     return MFX_OK;
@@ -815,6 +817,11 @@ int mfx_camera_cut_info(mfx_ctx* c, double out[32]) {
     out[6] = (double)((int64_t)((c->host.width + 7) / 8) * ((c->host.height + 7) / 8));
     out[7] = (double)K.cap;
     for (int n = 0; n <= MFX_CUT_CAP_MAX; ++n) out[8 + n] = (double)K.last.hist[n];
+    out[25] = (double)K.last.slots_seen;
+    out[26] = (double)K.last.slots_culled;
+    out[27] = (double)K.last.leaves_dropped;
+    out[28] = (double)K.last.leaves_narrowed;
+    out[29] = K.culled ? 1.0 : 0.0;
     return MFX_OK;
 }
 

@@ -41,8 +41,8 @@ hipError_t mfx_gpu_build_images(const float* prim_box, const float* cent, const 
 
 // The camera cuts of a flat scene's node image for the camera in device memory (mfx_camera_cuts.h), enqueued on
 // st: table[tiles_y * tiles_x][cap] by the routine the host twin (mfx_cut::table_host) runs, so the same
-// bytes; stats_dev is zeroed and summed over the tiles.
-hipError_t mfx_build_cut_table(const MfxNode* nodes, const MfxCamera* cam_dev, int W, int H, int cap, MfxCutEntry* table,
-                               MfxCutStats* stats_dev, hipStream_t st);
+// bytes; stats_dev is zeroed and summed over the tiles. slots: the image's slots, for the per-tile slot cull.
+hipError_t mfx_build_cut_table(const MfxNode* nodes, const MfxSlot* slots, const MfxCamera* cam_dev, int W, int H, int cap,
+                               MfxCutEntry* table, MfxCutStats* stats_dev, hipStream_t st);
 
 #endif

@@ -706,18 +706,24 @@ hipError_t mfx_gpu_build_images(const float* prim_box, const float* cent, const 
 }
 
 // ---- the camera cuts (mfx_camera_cuts.h): one thread per film tile runs the routine the host twin runs ----
-__global__ void __launch_bounds__(64) k_cut_table(const MfxNode* __restrict__ nodes, const MfxCamera* __restrict__ cam, int W, int H,
-                                                  int tiles_x, int ntiles, int cap, MfxCutEntry* __restrict__ table,
-                                                  MfxCutStats* __restrict__ stats) {
+__global__ void __launch_bounds__(64) k_cut_table(const MfxNode* __restrict__ nodes, const MfxSlot* __restrict__ slots,
+                                                  const MfxCamera* __restrict__ cam, int W, int H, int tiles_x, int ntiles, int cap,
+                                                  MfxCutEntry* __restrict__ table, MfxCutStats* __restrict__ stats) {
     __shared__ MfxCutEntry lists[MFX_CUT_CAP_MAX * 64];  // the threads' working lists, entry i of thread t at [i * 64 + t]
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = t < ntiles;
     int n = -1;
     bool root = false;
+    unsigned tally[4] = {0, 0, 0, 0};  // the slot cull's counts (MfxCutStats::slots_seen ..)
     if (valid) {
         MfxCutEntry* row = table + (size_t)t * cap;
-        n = mfx_cut::tile_cut(nodes, *cam, W, H, t % tiles_x, t / tiles_x, cap, row, lists + threadIdx.x, 64);
+        n = mfx_cut::tile_cut(nodes, slots, *cam, W, H, t % tiles_x, t / tiles_x, cap, row, lists + threadIdx.x, 64, tally);
         root = n == 1 && row[0].code == 0;
+    }
+    for (int k = 0; k < 4; ++k) {  // (the four counts are consecutive words of MfxCutStats)
+        unsigned v = tally[k];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if (threadIdx.x == 0 && v) atomicAdd(&stats->slots_seen + k, (unsigned long long)v);
     }
     // the statistics: summed over the wave (a block is one wave), one atomic per counter and wave (an atomic
     // per tile on the same few words serialises the whole launch)
@@ -741,13 +747,13 @@ __global__ void __launch_bounds__(64) k_cut_table(const MfxNode* __restrict__ no
     }
 }
 
-hipError_t mfx_build_cut_table(const MfxNode* nodes, const MfxCamera* cam_dev, int W, int H, int cap, MfxCutEntry* table,
-                               MfxCutStats* stats_dev, hipStream_t st) {
+hipError_t mfx_build_cut_table(const MfxNode* nodes, const MfxSlot* slots, const MfxCamera* cam_dev, int W, int H, int cap,
+                               MfxCutEntry* table, MfxCutStats* stats_dev, hipStream_t st) {
     const int tiles_x = (W + 7) / 8, ntiles = tiles_x * ((H + 7) / 8);
     if (cap < 1 || cap > MFX_CUT_CAP_MAX || ntiles < 1) return hipErrorInvalidValue;
     const hipError_t e = hipMemsetAsync(stats_dev, 0, sizeof(MfxCutStats), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_cut_table, dim3((ntiles + 63) / 64), dim3(64), 0, st, nodes, cam_dev, W, H, tiles_x, ntiles, cap, table,
-                       stats_dev);
+    hipLaunchKernelGGL(k_cut_table, dim3((ntiles + 63) / 64), dim3(64), 0, st, nodes, slots, cam_dev, W, H, tiles_x, ntiles, cap,
+                       table, stats_dev);
     return hipGetLastError();
 }

@@ -306,7 +306,7 @@ struct CreateEnv {
     using Int = std::optional<int>;
     bool node_f32 = false, diag_iter = false, no_gray_light = false, no_lit_in_hit = false;  // set at all
     Int mega_waves, shadow_target_blocks, stack_lds, ntop, slot_lds, shadow_waves, blocks_per_cu, camera_packets, cam_blocks;
-    Int camera_cuts, camera_cut_cap, camera_cut_min_samples;
+    Int camera_cuts, camera_cut_cap, camera_cut_min_samples, camera_cut_cull_min_samples;
     Int pool_fail_once, adaptive_check, iter_events, queue_from, qchunk, ray_queue, mega_chunk, shd_half, chunk;
     std::optional<int64_t> pool;
 };
@@ -318,6 +318,11 @@ struct CamCuts {
     bool on = true;                  // MFX_CAMERA_CUTS=0: off
     int cap = MFX_CUT_CAP_DEFAULT;   // MFX_CAMERA_CUT_CAP
     int min_samples = MFX_CUT_MIN_SAMPLES;  // a trace of fewer samples does not pay a build (MFX_CAMERA_CUT_MIN_SAMPLES)
+    // the slot cull triples the build's time, so a table is built with it once its camera has served this many
+    // samples, the coming trace's included (MFX_CAMERA_CUT_CULL_MIN_SAMPLES): a camera that stays pays it once
+    int cull_min_samples = MFX_CUT_CULL_MIN_SAMPLES;
+    int64_t cam_samples = 0;         // samples traced with the table's camera and image (saturating)
+    bool culled = false;             // the table was built with the slot cull
     DevBuf<MfxCutEntry> table;       // [tiles_y * tiles_x][cap]
     DevBuf<MfxCutStats> stats;
     size_t entries = 0;              // allocated
@@ -487,7 +492,7 @@ int whole_film_single_device(const mfx_ctx* c, const char* who);
 // mfx_trace.cpp
 int wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, TraceMode mode = {});
 bool cuts_apply(const mfx_ctx* c);
-int cuts_ensure(mfx_ctx* c);
+int cuts_ensure(mfx_ctx* c, int64_t ns);
 int cuts_read_stats(mfx_ctx* c);
 int dev_trace_accumulate(mfx_ctx* c, int32_t spp, int64_t sample_base, ResolveSplit* split = nullptr);
 int settle_queue_auto(mfx_ctx* c);

@@ -162,9 +162,17 @@ bool mfxh::cuts_apply(const mfx_ctx* c) { return c->host.inst.empty() && c->wf_c
 
 // The device's table for its current camera and node image, built on its stream if it is another's
 // (context creation, a camera change, a scene rebuild): every later launch on the stream sees it.
-int mfxh::cuts_ensure(mfx_ctx* c) {
+// ns: the samples of the trace that asks. The slot cull makes the build three times as long (DESIGN.md §7, round
+// 10), so the table is built with it only once its camera has served cull_min_samples samples, this trace's
+// included: a camera that moves before every trace gets the plain table, one that stays gets the culled one
+// with the trace that crosses the threshold and keeps it.
+int mfxh::cuts_ensure(mfx_ctx* c, int64_t ns) {
     CamCuts& K = c->cuts;
-    if (K.valid && K.image_gen == c->image_gen && std::memcmp(&K.cam, &c->host.camera, sizeof(MfxCamera)) == 0) return MFX_OK;
+    const bool same = K.valid && K.image_gen == c->image_gen && std::memcmp(&K.cam, &c->host.camera, sizeof(MfxCamera)) == 0;
+    if (!same) K.cam_samples = 0;
+    K.cam_samples = ns > INT64_MAX - K.cam_samples ? INT64_MAX : K.cam_samples + std::max<int64_t>(ns, 0);
+    const bool cull = K.cam_samples >= K.cull_min_samples;
+    if (same && (K.culled || !cull)) return MFX_OK;
     const size_t tiles = (size_t)((c->host.width + 7) / 8) * (size_t)((c->host.height + 7) / 8);
     if (K.entries < tiles * K.cap) {
         HIP_TRY(K.table.alloc(tiles * K.cap), _e == hipErrorOutOfMemory ? MFX_E_NOMEM : MFX_E_DEVICE, "camera cuts: ");
@@ -177,10 +185,11 @@ int mfxh::cuts_ensure(mfx_ctx* c) {
     }
     K.valid = false;
     HIPCHECK(hipEventRecord(K.e0, c->stream));
-    HIPCHECK(mfx_build_cut_table(c->d_nodes, c->d_cam, c->host.width, c->host.height, K.cap, K.table, K.stats, c->stream));
+    HIPCHECK(mfx_build_cut_table(c->d_nodes, cull ? (const MfxSlot*)c->d_slots : nullptr, c->d_cam, c->host.width, c->host.height, K.cap, K.table, K.stats, c->stream));
     HIPCHECK(hipEventRecord(K.e1, c->stream));
     K.cam = c->host.camera;
     K.image_gen = c->image_gen;
+    K.culled = cull;
     K.valid = true;
     K.builds += 1;
     K.last_read = false;
@@ -285,7 +294,7 @@ int mfxh::wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, TraceMode mode) 
         const CamCuts& K = c->cuts;
         const bool have = K.valid && K.image_gen == c->image_gen && std::memcmp(&K.cam, &c->host.camera, sizeof(MfxCamera)) == 0;
         if (have || ns >= K.min_samples) {
-            MFX_TRY(cuts_ensure(c));
+            MFX_TRY(cuts_ensure(c, ns));
             P.cuts = K.table;
             P.cut_cap = K.cap;
         }

@@ -1184,6 +1184,9 @@ __device__ __forceinline__ void packet_walk(const SceneView& S, DV o, DV d, cons
 #ifndef MFX_CUT_LB_CULL
 #define MFX_CUT_LB_CULL 1  // 0 (A/B builds): no cull by lb; every entry's box is still tested against the lanes' limits
 #endif
+#ifndef MFX_CUT_EMPTY_SKIP
+#define MFX_CUT_EMPTY_SKIP 1  // 0 (A/B builds): a window of a tile with an empty cut still makes its camera rays
+#endif
 // The walk started from the tile's cut (mfx_camera_cuts.h; DESIGN.md §3, "Camera cuts") instead of the
 // root: row[0 .. cap) are the tile's entries by ascending lb, MFX_CUT_END after the last. An entry is one
 // 32-B scalar load (the next one is asked for before this one is walked). Its box is the one its parent

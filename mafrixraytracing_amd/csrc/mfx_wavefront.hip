@@ -817,8 +817,14 @@ __global__ void __launch_bounds__(256, MFX_CAM_WAVES) k_camera(WfParams P) {
         const bool act = j < P.total && x < P.width && y < P.height;
         if (!__any(act)) continue;
         CAM_MARK(t_scan);
+        // A tile whose cut is empty: its widened pyramid misses every box, so every camera ray of the window
+        // misses whatever its jitter; the miss needs no key, no draw and no ray (one scalar load decides,
+        // the first the walk would issue)
+        // (wave-uniform: the packet below finds no lane and returns, and the lanes write their miss)
+        const bool seen = !(CUTS && MFX_CUT_EMPTY_SKIP) || row->code != MFX_CUT_END;
+        if (act && !seen) c_primary++;
         DV o = dv(0, 0, 0), d = dv(0, 0, 1);
-        if (act) {  // PixelIntegrator.Sample (Integrators.fs:167-169) + GetRay (Camera.fs:134-139)
+        if (act && seen) {  // PixelIntegrator.Sample (Integrators.fs:167-169) + GetRay (Camera.fs:134-139)
             const int64_t pixel = (int64_t)x * P.height + y;  // Color[w,h] x-major
             const int64_t gsample = path_gsample<LIST>(P, smp);
             const uint64_t key = path_key(P.seed, (uint64_t)pixel, (uint64_t)gsample);
@@ -834,10 +840,10 @@ __global__ void __launch_bounds__(256, MFX_CAM_WAVES) k_camera(WfParams P) {
         Best B;
 #if MFX_DIAG_STAMPS == 3
         CAM_MARK(t_gen);
-        packet_closest<STATS, true, CUTS>(S, act, o, d, 99999999., B, stk, stm, st, pk_nodes, pk_slots, ph, row, P.cut_cap, &pk_cuts);
+        packet_closest<STATS, true, CUTS>(S, act && seen, o, d, 99999999., B, stk, stm, st, pk_nodes, pk_slots, ph, row, P.cut_cap, &pk_cuts);
         t_last = stamp();
 #else
-        packet_closest<STATS, false, CUTS>(S, act, o, d, 99999999., B, stk, stm, st, pk_nodes, pk_slots, nullptr, row, P.cut_cap,
+        packet_closest<STATS, false, CUTS>(S, act && seen, o, d, 99999999., B, stk, stm, st, pk_nodes, pk_slots, nullptr, row, P.cut_cap,
                                            &pk_cuts);  // Integrators.fs:108
 #endif
         if (act) {

@@ -387,7 +387,8 @@ class NativeContext:
         check(self.lib.mfx_camera_cut_info(self._h, dptr(out)), "mfx_camera_cut_info")
         return {"builds": int(out[0]), "build_ms": float(out[1]), "len_sum": int(out[2]), "len_max": int(out[3]),
                 "root_tiles": int(out[4]), "empty_tiles": int(out[5]), "tiles": int(out[6]), "cap": int(out[7]),
-                "hist": [int(v) for v in out[8:25]]}
+                "hist": [int(v) for v in out[8:25]], "slots_seen": int(out[25]), "slots_culled": int(out[26]),
+                "leaves_dropped": int(out[27]), "leaves_narrowed": int(out[28]), "culled": bool(out[29])}
 
     def camera_cut_table(self, host: bool = False) -> np.ndarray:
         """mfx_camera_cut_table: the camera-cut table for the current camera as bytes, [tiles][cut_cap][32];
