@@ -168,6 +168,25 @@ type MfxDenoiseVarCfg =
     val mutable sigmaLuma : float
     val mutable lumaFloor : float
 
+/// mfx_texture (16 B): width * height RGBA8 texels, rows top to bottom (rgba: a pinned byte array's address)
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type MfxTexture =
+    val mutable rgba : nativeint
+    val mutable width : int32
+    val mutable height : int32
+
+/// mfx_prim_uv (56 B): a primitive's texture (-1: untextured), reserved 0, and (u, v) of its corners p0, p1, p2
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type MfxPrimUv =
+    val mutable texture : int32
+    val mutable reserved : int32
+    val mutable u0 : float
+    val mutable v0 : float
+    val mutable u1 : float
+    val mutable v1 : float
+    val mutable u2 : float
+    val mutable v2 : float
+
 // ---- entry points --------------------------------------------------------------------------------
 
 module Api =
@@ -176,6 +195,11 @@ module Api =
     // several area lights, one picked per path vertex (the lights replace scene.light; instances: 0n, 0 for a flat scene)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
     extern int mfx_create_lights(MfxSceneDesc& scene, MfxQuadLight[] lights, int nlights, nativeint instances, int ninstances, MfxOptions& opt, nativeint& ctx)
+    // albedo textures: mfx_create_lights with textures and one MfxPrimUv per entry of scene.prims (no textured primitive: that call itself)
+    [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
+    extern int mfx_create_textured(MfxSceneDesc& scene, MfxQuadLight[] lights, int nlights, nativeint instances, int ninstances, MfxTexture[] textures, int ntextures, MfxPrimUv[] primUv, MfxOptions& opt, nativeint& ctx)
+    [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
+    extern int mfx_texture_info(nativeint ctx, float[] out8)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
     extern void mfx_destroy(nativeint ctx)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]

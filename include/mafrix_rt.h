@@ -245,6 +245,82 @@ int mfx_light_info(mfx_ctx* ctx, double out[8]);
  * out[nlights][4] = area, 1 / area, pdf_n, 0. The same refusals as mfx_create_lights' for the lights. */
 int mfx_light_table(const mfx_quad_light* lights, int32_t nlights, double* out);
 
+/* ---- albedo textures (ABI 6, additive; an extension: the reference's materials are one colour each) ------
+ * A primitive may carry a UV map and a texture; at every path vertex on it the material's albedo is
+ * multiplied by one texel, looked up by the nearest-texel rule below. A lookup is an exact table read and
+ * the only arithmetic is the texel's index, stated in + - * / floor, so a host statement
+ * (mafrixraytracing_amd/textures.py) and the kernels agree bit for bit. Every material stays Lambertian.
+ * All FP64, one rounding per operation, no contraction; dot(a,b) = (a0*b0 + a1*b1) + a2*b2.
+ *
+ * Inputs. mfx_texture: `rgba` is width * height texels of 4 bytes, rows top to bottom; alpha is ignored and
+ * the bytes are taken as linear (a caller who wants sRGB decodes before the call). mfx_prim_uv: one per
+ * entry of scene->prims; texture == -1: the primitive is untextured; uv[i] belongs to corner p[i]. A rect
+ * uses the map of its first three corners for the whole rect (exact for a parallelogram with an affine
+ * layout, which is what OBJ quads are). A sphere must have texture == -1.
+ *
+ * The UV record. Each *world* primitive (after instance expansion: the template's corners plus the offset, so
+ * every instance has its own records) gets 8 doubles, computed on the host at creation from its world corners
+ * v0, v1, v2:
+ *  1. e1 = v1 - v0, e2 = v2 - v0;
+ *  2. d11 = dot(e1,e1), d12 = dot(e1,e2), d22 = dot(e2,e2);
+ *  3. det = d11*d22 - d12*d12;
+ *  4. for w in (u, v), with w0, w1, w2 the corners' coordinates: dw1 = w1 - w0, dw2 = w2 - w0;
+ *     a = (d22*dw1 - d12*dw2)/det; b = (d11*dw2 - d12*dw1)/det; g[c] = e1[c]*a + e2[c]*b;
+ *     cw = w0 - dot(v0, g);
+ *  5. the record is gu[3], cu, gv[3], cv;
+ *  6. if det == 0, or any of the eight values is not finite, the record is 0,0,0,u0, 0,0,0,v0: a degenerate
+ *     primitive shows the texel of its first corner.
+ * At a path vertex, hp being the hit point that starts the shadow ray, on a primitive with a W x H texture:
+ *     u = dot(hp, gu) + cu, v = dot(hp, gv) + cv;
+ *     tu = u - floor(u); xi = (int)floor(tu * (double)W) clamped into [0, W-1] (tu is exactly 1.0 for a tiny
+ *     negative u); yi likewise with tv and H; row = (H-1) - yi (OBJ's v points up);
+ *     id = base_t + row*W + xi, base_t being the texture's offset in the concatenation of all textures' texels.
+ * The albedo at that vertex: a[c] = albedo[mat][c] * ((double)texel[id][c] / 255.0); on an untextured primitive
+ * albedo[mat][c] as ever. A 255 byte gives a factor of exactly 1.0: an all-white texture changes no bit.
+ * Everything else of the vertex is unchanged. mfx_aov's planes [4..6] take the same a at the first hit;
+ * mfx_denoise, mfx_denoise_var and mfx_temporal run unchanged on those features.                          */
+typedef struct mfx_texture {
+    const uint8_t* rgba;
+    int32_t width, height; /* 1 .. 16384 each */
+} mfx_texture; /* 16 bytes */
+typedef struct mfx_prim_uv {
+    int32_t texture;  /* index into `textures`, or -1 */
+    int32_t reserved;
+    double uv[3][2];  /* (u, v) of p[0], p[1], p[2] */
+} mfx_prim_uv; /* 56 bytes */
+#define MFX_MAX_TEXTURES 4096
+#define MFX_MAX_TEXTURE_DIM 16384
+
+/* mfx_create_lights with textures: lights and instances exactly as there; prim_uv[scene->nprims].
+ * ntextures == 0, or every texture == -1, is bit for bit and kernel for kernel the call without textures: the
+ * same mfx_launch_info, pool bytes and mfx_build_info digest (the UV table and the texels are arrays of their
+ * own; the digest does not cover them). Otherwise the context runs the textured instances of k_shadow,
+ * k_resolve and mfx_aov's kernel, always the wavefront pipeline (one-sample calls included), and its path
+ * pool keeps 4 bytes more per path vertex: the vertex's texel id. The texels are copied to the device at
+ * creation and stay there across an mfx_set_camera rebuild (the records depend on the primitives alone).
+ * MFX_E_INVALID, decided on the host before any device is touched, the message naming the first offender:
+ * ntextures < 0 or > MFX_MAX_TEXTURES, or NULL textures with ntextures > 0; a width or height outside
+ * [1, MFX_MAX_TEXTURE_DIM]; more than 2^31 - 2 texels in all (these three from the sizes alone, before any
+ * texel or pointer is looked at); a NULL rgba; NULL prim_uv with ntextures > 0; a texture index outside
+ * [-1, ntextures); a textured sphere; a non-finite uv of a textured primitive; with any textured primitive,
+ * MFX_F_MEGAKERNEL or MFX_F_COUNT_STATS (those kernel instances are built without textures).             */
+int mfx_create_textured(const mfx_scene_desc* scene, const mfx_quad_light* lights, int32_t nlights,
+                        const mfx_instance* instances, int32_t ninstances, const mfx_texture* textures,
+                        int32_t ntextures, const mfx_prim_uv* prim_uv, const mfx_options* opt, mfx_ctx** out);
+/* out[0] = textures, out[1] = 1 if the textured kernel instances run, out[2] = bytes of texels on the device,
+ * out[3] = bytes of the UV table (64 per world primitive, plus 4 for its texture index), out[4] = bytes per
+ * path slot the textures add to the pool, out[5] / out[6] = resident blocks per CU of the k_shadow /
+ * k_resolve instance in use, out[7] = 0. A context without textured primitives reports 0 in [0..4].        */
+int mfx_texture_info(mfx_ctx* ctx, double out[8]);
+/* Host-only (no device needed): the UV records of prims[0..nprims) as given (no instance expansion), by the
+ * code creation runs; out[nprims][8]. A primitive with texture == -1, or a sphere, gets eight zeros.       */
+int mfx_uv_table(const mfx_prim* prims, int64_t nprims, const mfx_prim_uv* prim_uv, double* out);
+/* Host-only: the texel rule. id_out[k] = the id of uv[k] in texture `texture` of the concatenation of
+ * textures[0..ntextures) (only the sizes are read: rgba may be anything). MFX_E_INVALID: the size refusals
+ * of mfx_create_textured, or a texture index outside [0, ntextures).                                       */
+int mfx_texel_index(const mfx_texture* textures, int32_t ntextures, int32_t texture, int64_t n, const double* uv,
+                    uint32_t* id_out);
+
 /* ---- the camera (an extension of the ABI: the reference's PinholeCamera has mutable position /
  * topleft / coord, Camera.fs:122-133, and Film.Reset exists for a camera move). Additive in ABI 6. ---- */
 

@@ -28,6 +28,8 @@ MFX_F_IN_FLIGHT = 128
 MFX_INSTANCE_VERBATIM = 1
 MFX_MAX_DEVICES = 64
 MFX_MAX_LIGHTS = 64
+MFX_MAX_TEXTURES = 4096
+MFX_MAX_TEXTURE_DIM = 16384
 MFX_DN_SRC_HOST = 0
 MFX_DN_SRC_ACCUM = 1
 MFX_DN_SRC_ADAPTIVE = 2
@@ -78,6 +80,16 @@ class MfxInstance(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MfxTexture(C.Structure):
+    """mfx_texture: width * height RGBA8 texels, rows top to bottom."""
+    _fields_ = [("rgba", C.POINTER(C.c_uint8)), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class MfxPrimUv(C.Structure):
+    """mfx_prim_uv: a primitive's texture (-1: none) and the (u, v) of its first three corners."""
+    _fields_ = [("texture", C.c_int32), ("reserved", C.c_int32), ("uv", (C.c_double * 2) * 3)]
+
+
 class MfxAdaptive(C.Structure):
     """mfx_adaptive: the schedule and threshold of mfx_sample_adaptive."""
     _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("step_spp", C.c_int32), ("reserved", C.c_int32),
@@ -112,6 +124,8 @@ class MfxTemporalCfg(C.Structure):
 
 assert C.sizeof(MfxPrim) == 104
 assert C.sizeof(MfxInstance) == 48
+assert C.sizeof(MfxTexture) == 16
+assert C.sizeof(MfxPrimUv) == 56
 assert C.sizeof(MfxAdaptive) == 32
 assert C.sizeof(MfxAdaptiveResume) == 32
 assert C.sizeof(MfxDenoiseCfg) == 56
@@ -125,6 +139,9 @@ assert PRIM_DTYPE.itemsize == 104
 INSTANCE_DTYPE = np.dtype([("first", "<i8"), ("count", "<i8"), ("offset", "<f8", (3,)), ("flags", "<i4"),
                            ("reserved", "<i4")], align=True)
 assert INSTANCE_DTYPE.itemsize == 48
+# mfx_prim_uv: texture index (-1: untextured), (u, v) of p[0], p[1], p[2]
+PRIM_UV_DTYPE = np.dtype([("texture", "<i4"), ("reserved", "<i4"), ("uv", "<f8", (3, 2))], align=True)
+assert PRIM_UV_DTYPE.itemsize == 56
 
 
 class SceneArrays:
@@ -138,8 +155,12 @@ class SceneArrays:
 
     def __init__(self, prims: np.ndarray, albedo: np.ndarray, light: dict, camera: dict,
                  width: int, height: int, max_depth: int = 3, instancing=None, two_level: bool = False,
-                 lights=None):
+                 lights=None, textures=None, prim_uv=None):
         self.prims = np.ascontiguousarray(prims, dtype=PRIM_DTYPE)
+        # albedo textures ((H, W, 4) uint8 arrays, rows top to bottom) and the primitives' maps (PRIM_UV_DTYPE,
+        # one per entry of `prims`; mfx_create_textured), or None: an untextured scene
+        self.textures = [np.ascontiguousarray(t, dtype=np.uint8) for t in textures] if textures is not None else None
+        self.prim_uv = np.ascontiguousarray(prim_uv, dtype=PRIM_UV_DTYPE) if prim_uv is not None else None
         self.two_level = bool(two_level)
         # every area light of the scene, in order (light dicts; mfx_create_lights), or None: `light` alone
         self.lights = list(lights) if lights is not None else None
@@ -177,12 +198,12 @@ class SceneArrays:
 
     def with_film(self, width: int, height: int) -> "SceneArrays":
         return SceneArrays(self.prims, self.albedo, self.light, self.camera, width, height, self.max_depth,
-                           self.instancing, self.two_level, self.lights)
+                           self.instancing, self.two_level, self.lights, self.textures, self.prim_uv)
 
     def flat(self) -> "SceneArrays":
         """The same scene without its instancing (the reference's flat primitive list)."""
         return SceneArrays(self.prims, self.albedo, self.light, self.camera, self.width, self.height,
-                           self.max_depth, lights=self.lights)
+                           self.max_depth, lights=self.lights, textures=self.textures, prim_uv=self.prim_uv)
 
 
 def quad_lights(lights):
@@ -207,6 +228,47 @@ def light_table(lights) -> np.ndarray:
     return out[:len(lights)]
 
 
+def texture_structs(textures):
+    """A ctypes array of MfxTexture over (H, W, 4) uint8 arrays, and the arrays it points into (keep both
+    alive for the call)."""
+    keep = [np.ascontiguousarray(t, dtype=np.uint8) for t in textures]
+    arr = (MfxTexture * max(1, len(keep)))()
+    for k, t in enumerate(keep):
+        if t.ndim != 3 or t.shape[2] != 4:
+            raise ValueError(f"texture {k}: expected an (H, W, 4) uint8 array, got shape {t.shape}")
+        arr[k].rgba = t.ctypes.data_as(C.POINTER(C.c_uint8))
+        arr[k].height, arr[k].width = t.shape[0], t.shape[1]
+    return arr, keep
+
+
+def uv_table(prims, prim_uv) -> np.ndarray:
+    """Host-only: (n, 8) UV records gu[3], cu, gv[3], cv of `prims` as context creation computes them
+    (mfx_uv_table; textures.uv_table is the Python statement of the same)."""
+    lib = load_library()
+    pr = np.ascontiguousarray(prims, dtype=PRIM_DTYPE)
+    uv = np.ascontiguousarray(prim_uv, dtype=PRIM_UV_DTYPE)
+    if len(pr) != len(uv):
+        raise ValueError("one prim_uv entry per primitive")
+    out = np.zeros((max(1, len(pr)), 8))
+    check(lib.mfx_uv_table(pr.ctypes.data_as(C.POINTER(MfxPrim)), len(pr), uv.ctypes.data_as(C.POINTER(MfxPrimUv)),
+                           dptr(out)), "mfx_uv_table")
+    return out[:len(pr)]
+
+
+def texel_index(sizes, texture: int, uv) -> np.ndarray:
+    """Host-only: the texel ids of uv (n, 2) in texture `texture` of textures with (height, width) `sizes`
+    (mfx_texel_index: only the sizes are read; textures.texel_index is the Python statement of the same)."""
+    lib = load_library()
+    arr = (MfxTexture * max(1, len(sizes)))()
+    for k, (h, w) in enumerate(sizes):
+        arr[k].height, arr[k].width = int(h), int(w)
+    uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(-1, 2)
+    out = np.zeros(max(1, len(uv)), dtype=np.uint32)
+    check(lib.mfx_texel_index(arr, len(sizes), texture, len(uv), dptr(uv), out.ctypes.data_as(C.POINTER(C.c_uint32))),
+          "mfx_texel_index")
+    return out[:len(uv)]
+
+
 _P = C.POINTER
 _dp = _P(C.c_double)
 _ip = _P(C.c_int32)
@@ -219,6 +281,11 @@ def _bind(lib, strict: bool = True):
                                            _P(C.c_void_p)]),
         "mfx_create_lights": (C.c_int, [_P(MfxSceneDesc), _P(MfxQuadLight), C.c_int32, _P(MfxInstance), C.c_int32,
                                         _P(MfxOptions), _P(C.c_void_p)]),
+        "mfx_create_textured": (C.c_int, [_P(MfxSceneDesc), _P(MfxQuadLight), C.c_int32, _P(MfxInstance), C.c_int32,
+                                          _P(MfxTexture), C.c_int32, _P(MfxPrimUv), _P(MfxOptions), _P(C.c_void_p)]),
+        "mfx_texture_info": (C.c_int, [C.c_void_p, _dp]),
+        "mfx_uv_table": (C.c_int, [_P(MfxPrim), C.c_int64, _P(MfxPrimUv), _dp]),
+        "mfx_texel_index": (C.c_int, [_P(MfxTexture), C.c_int32, C.c_int32, C.c_int64, _dp, _P(C.c_uint32)]),
         "mfx_light_info": (C.c_int, [C.c_void_p, _dp]),
         "mfx_light_table": (C.c_int, [_P(MfxQuadLight), C.c_int32, _dp]),
         "mfx_expand_instances": (C.c_int, [_P(MfxPrim), C.c_int64, _P(MfxInstance), C.c_int32, _P(MfxPrim),
@@ -279,7 +346,7 @@ def _bind(lib, strict: bool = True):
 
 
 EXPORTED_SYMBOLS = [
-    "mfx_create", "mfx_create_instanced", "mfx_create_lights", "mfx_light_info", "mfx_light_table", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_sample_adaptive_resume", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_temporal", "mfx_pinhole_derive", "mfx_camera_info", "mfx_set_camera", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
+    "mfx_create", "mfx_create_instanced", "mfx_create_lights", "mfx_light_info", "mfx_light_table", "mfx_create_textured", "mfx_texture_info", "mfx_uv_table", "mfx_texel_index", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_sample_adaptive_resume", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_temporal", "mfx_pinhole_derive", "mfx_camera_info", "mfx_set_camera", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
     "mfx_film_mean", "mfx_stats",
     "mfx_trace_accumulate", "mfx_accum_clear", "mfx_accum_reduce", "mfx_accum_device_ptr", "mfx_accum_attach", "mfx_accum_read_mean",
     "mfx_sync", "mfx_stream", "mfx_ray_counts", "mfx_last_trace_ms", "mfx_trace_timing", "mfx_ray_counts_total", "mfx_closest_hit", "mfx_any_hit", "mfx_ref_leaves",

@@ -142,6 +142,23 @@ static int scene_upload(mfx_ctx* c) {
     return MFX_OK;
 }
 
+// The tables of a textured context in HBM (ctx_setup, once per device: they outlive an mfx_set_camera
+// rebuild). The texels come straight from the caller's arrays (c->tex.src, valid while creation runs).
+static int texture_upload(mfx_ctx* c) {
+    Textures& t = c->tex;
+    if (!t.host.on) return MFX_OK;
+    if (!t.src) return fail(MFX_E_STATE, "mfx_create_textured: no texture source");
+    CK(upload(t.d_uvrec, t.host.uvrec));
+    CK(upload(t.d_ptex, t.host.ptex));
+    CK(upload(t.d_desc, t.host.desc));
+    CK(t.d_texels.alloc((size_t)std::max<int64_t>(1, t.host.ntexels)));
+    for (size_t k = 0; k < t.host.desc.size(); ++k) {
+        const MfxTexDesc& d = t.host.desc[k];
+        CK(hipMemcpy(t.d_texels.get() + d.base, t.src[k].rgba, (size_t)d.width * d.height * 4, hipMemcpyHostToDevice));
+    }
+    return MFX_OK;
+}
+
 // Occupancy-derived launch shapes of the scene in c->host (its stack bound, node and slot counts,
 // instances), and the buffers sized by them; with the context's device current
 static int scene_shapes(mfx_ctx* c) {
@@ -169,7 +186,7 @@ static int scene_shapes(mfx_ctx* c) {
     // spilled), and ntop top nodes and nslot slots beside them
     auto blocks = [&](bool shd, int nlds, int ntop = 0, int nslot = 0) {
         const WfLdsShape s{shd, nlds < c->stack_size, c->d_nodes_h != nullptr, nlds, ntop, (int)c->host.inst.size(), nslot,
-                           shd && wf_multi_light(c)};
+                           shd && wf_multi_light(c), shd && wf_textured(c)};
         int b = 0;
         const hipError_t e = mfx_wf_kernel_occupancy(s, &b);
         if (e != hipSuccess && qerr == hipSuccess) qerr = e;
@@ -213,7 +230,7 @@ static int scene_shapes(mfx_ctx* c) {
         // waves per SIMD: more registers, no spills (C2 / C5 +2 %); with 4 it keeps the 4-wave one
         A.shadow_waves = sbpc <= 3 ? 3 : 4;
         if (env.shadow_waves) A.shadow_waves = *env.shadow_waves == 3 ? 3 : 4;
-        if (wf_multi_light(c)) A.shadow_waves = 4;  // the several-light instances are the 4-wave build's only
+        if (wf_multi_light(c) || wf_textured(c)) A.shadow_waves = 4;  // the several-light and textured instances are the 4-wave build's only
         if (A.shadow_waves == 3) sbpc = std::min(sbpc, 3);
         if (c->diag_iter)
             fprintf(stderr,
@@ -264,6 +281,7 @@ static int ctx_setup(mfx_ctx* c) {
     CK(c->ev0.create());
     CK(c->ev1.create());
     MFX_TRY(scene_upload(c));
+    MFX_TRY(texture_upload(c));
     const size_t npix = (size_t)c->npix, plane = sizeof(double) * npix;
     CK(c->d_accum_own.alloc(3 * npix));
     c->d_accum = c->d_accum_own;
@@ -344,10 +362,17 @@ static hipError_t repeated_device_setup(mfx_ctx* c) {
 static_assert(WF_MAX_LIGHTS == MFX_MAX_LIGHTS, "the kernels' light index width is the ABI's bound");
 
 // lights (mfx_create_lights): the list that replaces scene->light (null: scene->light, N = 1)
+// tex (mfx_create_textured): the prepared textures of a scene with a textured primitive, with the caller's
+// arrays they were prepared from (null: no textures)
 static int create_impl(const mfx_scene_desc* scene, const mfx_instance* instances, int32_t ninstances,
-                       const mfx_options* opt, mfx_ctx** out, const mfx_quad_light* lights = nullptr, int32_t nlights = 0) {
+                       const mfx_options* opt, mfx_ctx** out, const mfx_quad_light* lights = nullptr, int32_t nlights = 0,
+                       const MfxTexHost* tex = nullptr, const mfx_texture* textures = nullptr,
+                       const mfx_prim_uv* prim_uv = nullptr) {
     if (!scene || !opt || !out) return fail(MFX_E_INVALID, "mfx_create: null argument");
     *out = nullptr;
+    // the megakernel and the counting instances of the trace kernels are built without textures
+    if (tex && (opt->flags & (MFX_F_MEGAKERNEL | MFX_F_COUNT_STATS)))
+        return fail(MFX_E_INVALID, "mfx_create_textured: MFX_F_MEGAKERNEL and MFX_F_COUNT_STATS need an untextured scene");
     std::vector<MfxLight> prepared;  // the lights' one validation: mfx_build_scene takes the result
     if (lights) {  // on the host, before any device is asked for
         std::string lerr;
@@ -393,6 +418,7 @@ static int create_impl(const mfx_scene_desc* scene, const mfx_instance* instance
         k.albedo.assign(scene->albedo, scene->albedo + 3 * (size_t)scene->nmat);
         if (instances) k.instances.assign(instances, instances + ninstances);
         if (lights) k.lights.assign(lights, lights + nlights);
+        if (tex) k.prim_uv.assign(prim_uv, prim_uv + scene->nprims);
         k.desc = *scene;
         k.desc.prims = nullptr;
         k.desc.albedo = nullptr;
@@ -417,7 +443,14 @@ static int create_impl(const mfx_scene_desc* scene, const mfx_instance* instance
         d->band_count = rows ? opt->part_count * G : G;
         d->api_part_count = opt->part_count;
     };
+    // textured: every device gets the tables (ctx_setup uploads them from the caller's arrays)
+    auto with_textures = [&](mfx_ctx* d) {
+        if (!tex) return;
+        d->tex.host = *tex;
+        d->tex.src = textures;
+    };
     init(c.get(), 0);
+    with_textures(c.get());
     c->ahead.k = opt->render_ahead;
     c->multi.device_list = opt->ndevices > 0;
     MFX_TRY(ctx_setup(c.get()));
@@ -430,6 +463,7 @@ static int create_impl(const mfx_scene_desc* scene, const mfx_instance* instance
             c->multi.peers.emplace_back(p);
             p->host = c->host;
             init(p, g);
+            with_textures(p);
             th.emplace_back([p, g, &prc, &perr] {
                 prc[g - 1] = ctx_setup(p);
                 if (prc[g - 1]) perr[g - 1] = mfx_last_error();  // this thread's message
@@ -459,6 +493,7 @@ static int create_impl(const mfx_scene_desc* scene, const mfx_instance* instance
                 return fail(MFX_E_DEVICE, std::string("mfx_create: device reduce setup: ") + hipGetErrorString(e));
         }
     }
+    for (mfx_ctx* d : devs_of(c.get())) d->tex.src = nullptr;  // the caller's arrays are the caller's again
     *out = c.release();
     return MFX_OK;
 }
@@ -660,6 +695,47 @@ int mfx_create_lights(const mfx_scene_desc* scene, const mfx_quad_light* lights,
     return create_impl(scene, instances, flat ? 0 : ninstances, opt, out, lights, nlights);
 }
 
+int mfx_create_textured(const mfx_scene_desc* scene, const mfx_quad_light* lights, int32_t nlights,
+                        const mfx_instance* instances, int32_t ninstances, const mfx_texture* textures,
+                        int32_t ntextures, const mfx_prim_uv* prim_uv, const mfx_options* opt, mfx_ctx** out) {
+    if (!scene || !opt || !out) return fail(MFX_E_INVALID, "mfx_create_textured: null argument");
+    const bool flat = !instances && ninstances == 0;
+    if (!flat && (!instances || ninstances < 1)) return fail(MFX_E_INVALID, "mfx_create_textured: no instances");
+    MfxTexHost tex;  // on the host, before any device is asked for
+    std::string err;
+    if (!mfx_prepare_textures(scene, flat ? nullptr : instances, flat ? 0 : ninstances, textures, ntextures, prim_uv, tex, err))
+        return fail(MFX_E_INVALID, "mfx_create_textured: " + err);
+    // no textured primitive: the call without textures, kernel for kernel
+    if (!tex.on) return mfx_create_lights(scene, lights, nlights, instances, ninstances, opt, out);
+    if (!lights || nlights < 1 || nlights > MFX_MAX_LIGHTS)
+        return fail(MFX_E_INVALID, "mfx_create_textured: nlights must be 1 .. MFX_MAX_LIGHTS with a light array");
+    return create_impl(scene, instances, flat ? 0 : ninstances, opt, out, lights, nlights, &tex, textures, prim_uv);
+}
+
+int mfx_texture_info(mfx_ctx* c, double out[8]) {
+    if (!c || !out) return fail(MFX_E_INVALID, "mfx_texture_info: null argument");
+    const bool tx = wf_textured(c), ml = wf_multi_light(c);
+    const WfParams& A = c->pool.params;
+    HIPCHECK(hipSetDevice(c->device));
+    const WfLdsShape s{true, A.stack_lds_shd < c->stack_size, c->d_nodes_h != nullptr, A.stack_lds_shd, A.ntop_shd,
+                       (int)c->host.inst.size(), A.nslot_shd, ml, tx};
+    int sb = 0, rb = 0;
+    HIPCHECK(mfx_wf_kernel_occupancy(s, &sb));
+    if (A.shadow_waves == 3) sb = std::min(sb, 3);  // (the 3-wave build: scene_shapes)
+    HIPCHECK(mfx_wf_resolve_occupancy(ml, &rb, tx));
+    const MfxTexHost& h = c->tex.host;
+    const double v[8] = {tx ? (double)h.desc.size() : 0.0,
+                         tx ? 1.0 : 0.0,
+                         tx ? (double)h.ntexels * 4.0 : 0.0,
+                         tx ? (double)(h.uvrec.size() * sizeof(double) + h.ptex.size() * sizeof(int32_t)) : 0.0,
+                         tx ? (double)WF_TEXEL_BYTES_PER_SLOT(c->host.max_depth + 1) : 0.0,
+                         (double)sb,
+                         (double)rb,
+                         0.0};
+    std::copy(v, v + 8, out);
+    return MFX_OK;
+}
+
 int mfx_light_table(const mfx_quad_light* lights, int32_t nlights, double* out) {
     if (!out) return fail(MFX_E_INVALID, "mfx_light_table: null argument");
     std::vector<MfxLight> t;
@@ -680,11 +756,11 @@ int mfx_light_info(mfx_ctx* c, double out[8]) {
     const WfParams& A = c->pool.params;
     HIPCHECK(hipSetDevice(c->device));
     const WfLdsShape s{true, A.stack_lds_shd < c->stack_size, c->d_nodes_h != nullptr, A.stack_lds_shd, A.ntop_shd,
-                       (int)c->host.inst.size(), A.nslot_shd, ml};
+                       (int)c->host.inst.size(), A.nslot_shd, ml, wf_textured(c)};
     int sb = 0, rb = 0;
     HIPCHECK(mfx_wf_kernel_occupancy(s, &sb));
     if (A.shadow_waves == 3) sb = std::min(sb, 3);  // (the 3-wave build: scene_shapes)
-    HIPCHECK(mfx_wf_resolve_occupancy(ml, &rb));
+    HIPCHECK(mfx_wf_resolve_occupancy(ml, &rb, wf_textured(c)));
     const double v[8] = {(double)c->host.lights.size(), ml ? 1.0 : 0.0, ml ? (double)(c->host.lights.size() * sizeof(MfxLight)) : 0.0,
                          ml ? (double)WF_LIGHT_BYTES_PER_SLOT(c->host.max_depth + 1) : 0.0, (double)sb, (double)rb, 0.0, 0.0};
     std::copy(v, v + 8, out);

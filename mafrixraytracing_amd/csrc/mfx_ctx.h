@@ -281,6 +281,7 @@ struct KeptScene {
     std::vector<double> albedo;
     std::vector<mfx_instance> instances;
     std::vector<mfx_quad_light> lights;  // mfx_create_lights' list (empty: desc.light)
+    std::vector<mfx_prim_uv> prim_uv;    // mfx_create_textured's maps of a textured context (56 B per primitive; else empty)
     mfx_scene_desc desc{};   // prims / albedo point nowhere: set from the vectors at use
     bool instanced = false;  // created by mfx_create_instanced
     bool flatten = false;    // the choice creation made for an instanced scene
@@ -336,6 +337,18 @@ struct CamCuts {
     MfxCutStats last{};              // the last build's statistics, read back by mfx_launch_info
     bool last_read = false;
     float last_ms = 0.f;
+};
+
+// Albedo textures (mfx_create_textured), per device: the tables the textured kernel instances read. They
+// depend on the primitives alone, not on the camera, so an mfx_set_camera rebuild leaves them where they are.
+struct Textures {
+    MfxTexHost host;                 // descriptors, UV table, texture per world primitive
+    DevBuf<double> d_uvrec;
+    DevBuf<int32_t> d_ptex;
+    DevBuf<MfxTexDesc> d_desc;
+    DevBuf<uint32_t> d_texels;       // every texture's texels, one after the other
+    const mfx_texture* src = nullptr;  // the caller's textures: set while creation uploads them, null afterwards
+    MfxTexTables tables() const { return host.on ? MfxTexTables{d_uvrec, d_ptex, d_desc, d_texels} : MfxTexTables{}; }
 };
 
 // Multi-device (primary context only)
@@ -433,6 +446,7 @@ struct __attribute__((visibility("hidden"))) mfx_ctx {
     mfxh::Temporal tp;
     mfxh::Readback rb;
     mfxh::Multi multi;
+    mfxh::Textures tex;
 
     // the RCCL communicators, then the peers, then this device current; the members release themselves
     ~mfx_ctx();
@@ -457,10 +471,15 @@ inline int band_rows(const mfx_ctx* d) {
 // pipeline for every trace, a light-index plane in the pool
 inline bool wf_multi_light(const mfx_ctx* c) { return c->host.lights.size() >= 2; }
 
+// albedo textures (mfx_create_textured with a textured primitive): the TX instances of k_shadow, k_resolve
+// and k_aov, the wavefront pipeline for every trace, a texel-id plane in the pool
+inline bool wf_textured(const mfx_ctx* c) { return c->tex.host.on; }
+
 // bytes of one path slot of the wavefront pool (ray queues included)
 inline size_t pool_slot_bytes(const mfx_ctx* c) {
     const int nv = c->host.max_depth + 1;  // vertices per path
-    return WF_DOUBLES_PER_SLOT(nv) * 8 + WF_WORDS_PER_SLOT(nv) * 4 + (wf_multi_light(c) ? WF_LIGHT_BYTES_PER_SLOT(nv) : 0);
+    return WF_DOUBLES_PER_SLOT(nv) * 8 + WF_WORDS_PER_SLOT(nv) * 4 + (wf_multi_light(c) ? WF_LIGHT_BYTES_PER_SLOT(nv) : 0) +
+           (wf_textured(c) ? WF_TEXEL_BYTES_PER_SLOT(nv) : 0);
 }
 
 // the scene images' device pointers of a kernel parameter struct (WfParams, TraceParams, AovParams, QueryParams)

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "mfx_layout.h"
+#include "mfx_texture.h"
 
 #define MFX_AOV_PLANES 8  // normal xyz, hit t, albedo rgb, hit fraction
 
@@ -28,6 +29,7 @@ struct AovParams {
     int32_t stack_size;       // LDS traversal stack entries per lane
     double* feat;             // [MFX_AOV_PLANES][w*h], x-major pixels
     double* out;              // null, or [w*h][MFX_AOV_PLANES] (the caller's layout)
+    MfxTexTables tx;          // albedo textures (all null without: the untextured instances run)
 };
 
 // k_atrous: one iteration of the edge-avoiding a-trous filter (the rule: include/mafrix_rt.h)

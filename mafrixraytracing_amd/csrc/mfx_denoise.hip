@@ -24,7 +24,9 @@
 // registers. The ray is the path's own camera ray (k_camera / trace_kernel: key pixel x*h + y, draws
 // 0 and 1), the hit Bvh.Hit(ray, 1e-6, 99999999.) by the per-lane walk of closest_kernel.
 // ----------------------------------------------------------------------------------------------
-template <bool INST>
+// TX: the instances for albedo textures (mfx_create_textured): the albedo planes take the material's albedo
+// times the texel of the hit point, by the rule and the functions the path vertices use (mfx_texture.h).
+template <bool INST, bool TX = false>
 __global__ void __launch_bounds__(256) k_aov(AovParams P) {
     extern __shared__ int lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -60,9 +62,26 @@ __global__ void __launch_bounds__(256) k_aov(AovParams P) {
         f[1] = f[1] + nm.y;
         f[2] = f[2] + nm.z;
         f[3] = f[3] + B.t;
-        f[4] = f[4] + sh.albedo[0];
-        f[5] = f[5] + sh.albedo[1];
-        f[6] = f[6] + sh.albedo[2];
+        double a0 = sh.albedo[0], a1 = sh.albedo[1], a2 = sh.albedo[2];
+        if constexpr (TX) {
+            const int prim = sh.prim_kind >> 2;
+            const int tex = P.tx.ptex[prim];
+            if (tex >= 0) {
+                const DV hp = vadd(o, vmul(d, B.t));  // Ray.PointAtParameter: the point k_extend stores
+                const double* r = P.tx.uvrec + (int64_t)MFX_UV_RECORD_DOUBLES * prim;
+                const double h3[3] = {hp.x, hp.y, hp.z};
+                const double rec[8] = {r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]};
+                double tu, tv;
+                mfx_tx_uv(rec, h3, tu, tv);
+                const uint32_t texel = P.tx.texels[mfx_tx_texel(P.tx.desc[tex], tu, tv)];
+                a0 = mfx_tx_albedo(a0, texel, 0);
+                a1 = mfx_tx_albedo(a1, texel, 1);
+                a2 = mfx_tx_albedo(a2, texel, 2);
+            }
+        }
+        f[4] = f[4] + a0;
+        f[5] = f[5] + a1;
+        f[6] = f[6] + a2;
         f[7] = f[7] + 1.0;
     }
     const double n = (double)P.spp;
@@ -395,6 +414,12 @@ static inline unsigned dn_grid(int64_t n, int block) { return (unsigned)((n + bl
 hipError_t mfx_launch_aov(const AovParams& P, hipStream_t st) {
     const size_t lds = (size_t)4 * P.stack_size * 64 * sizeof(int);  // mfx_launch_query's: a column per lane
     const dim3 g(dn_grid((int64_t)P.width * P.height, 256));
+    if (P.tx.texels) {  // albedo textures: the TX instances
+        if (!P.tx.uvrec || !P.tx.ptex || !P.tx.desc) return hipErrorInvalidValue;
+        if (P.inst) hipLaunchKernelGGL((k_aov<true, true>), g, dim3(256), lds, st, P);
+        else hipLaunchKernelGGL((k_aov<false, true>), g, dim3(256), lds, st, P);
+        return hipGetLastError();
+    }
     if (P.inst) hipLaunchKernelGGL(k_aov<true>, g, dim3(256), lds, st, P);
     else hipLaunchKernelGGL(k_aov<false>, g, dim3(256), lds, st, P);
     return hipGetLastError();

@@ -68,6 +68,7 @@ extern "C" int mfx_aov(mfx_ctx* c, int32_t spp, int64_t sample_base, double* out
     P.stack_size = c->stack_size;
     P.feat = dn.feat;
     P.out = out ? dn.feat_out.get() : nullptr;
+    P.tx = c->tex.tables();  // albedo textures: k_aov's TX instances (all null without)
     HIPCHECK(hipEventRecord(dn.ev0, c->stream));
     HIPCHECK(mfx_launch_aov(P, c->stream));
     HIPCHECK(hipEventRecord(dn.ev1, c->stream));

@@ -7,6 +7,7 @@
 
 #include "../../include/mafrix_rt.h"
 #include "mfx_layout.h"
+#include "mfx_texture.h"
 
 struct MfxHostScene {
     // reference heap-BVH leaf grouping (BvhNode.fs:24-61)
@@ -63,6 +64,24 @@ bool mfx_build_scene(const mfx_scene_desc* d, MfxHostScene& s, std::string& err,
 // area and pdf = (1 / area) / N. False with `err` set: a count outside 1 .. MFX_MAX_LIGHTS, a non-finite
 // field (err names the light's index), and with N >= 2 an area that is 0 or not finite.
 bool mfx_prepare_lights(const mfx_quad_light* lights, int nlights, std::vector<MfxLight>& out, std::string& err);
+// Albedo textures of a context (mfx_create_textured; mfx_texture.cpp), as the host prepares them: beside the
+// scene images, never part of them (mfx_scene_digest does not cover them, MfxShade and the slots are as ever).
+struct MfxTexHost {
+    std::vector<MfxTexDesc> desc;  // per texture: its first texel in the concatenation, width, height
+    std::vector<double> uvrec;     // [world primitives][8] the UV records (zeros for an untextured primitive)
+    std::vector<int32_t> ptex;     // [world primitives] the primitive's texture, -1: untextured
+    int64_t ntexels = 0;
+    bool on = false;               // some world primitive is textured: the textured kernel instances run
+};
+// The descriptors of textures[0..ntextures), from the sizes alone. False with `err` naming the first offender:
+// a count outside 0 .. MFX_MAX_TEXTURES, a width or height outside 1 .. MFX_MAX_TEXTURE_DIM, too many texels.
+bool mfx_texture_descs(const mfx_texture* textures, int ntextures, std::vector<MfxTexDesc>& desc, int64_t& ntexels,
+                       std::string& err);
+// Everything mfx_create_textured refuses about textures and maps, then the UV table of the world primitives
+// (scene->prims, or their expansion by `instances`). out.on == false: an untextured scene.
+bool mfx_prepare_textures(const mfx_scene_desc* scene, const mfx_instance* instances, int ninstances,
+                          const mfx_texture* textures, int ntextures, const mfx_prim_uv* prim_uv, MfxTexHost& out,
+                          std::string& err);
 // PinholeCamera's constructor (Camera.fs:122-133), or with c.derived the fields as they are.
 void mfx_derive_camera(const mfx_pinhole& c, MfxCamera& cam);
 // The widening mfx_build_scene would give s's boxes with the camera at pos: (float)ldexp(R + T, -19), and

@@ -61,6 +61,7 @@ static int wf_ensure_pool(mfx_ctx* c, int32_t pool, bool queues) {
     A.vls = (double*)take(P * 8 * 2 * nv);
     A.vmat = (WfMat*)take(P * sizeof(WfMat) * nv);
     A.vlt = wf_multi_light(c) ? (uint8_t*)take(P * WF_LIGHT_BYTES_PER_SLOT(nv)) : nullptr;  // (in pool_slot_bytes)
+    A.vtex = wf_textured(c) ? (uint32_t*)take(P * WF_TEXEL_BYTES_PER_SLOT(nv)) : nullptr;  // (in pool_slot_bytes)
     A.vstride = (int64_t)P;
     A.rn = (uint32_t*)take(P * 4);
     A.depth = (int32_t*)take(P * 4);
@@ -148,6 +149,8 @@ static void fill_scene_params(mfx_ctx* c, WfParams& P) {
     // several lights: the ML instances' table (set: mfx_wf_iteration and mfx_wf_resolve launch them)
     P.lights = wf_multi_light(c) ? c->d_lights.get() : nullptr;
     P.nlights = wf_multi_light(c) ? (int32_t)c->host.lights.size() : 0;
+    // albedo textures: the TX instances' tables (vtex set, by wf_ensure_pool: the launchers run them)
+    P.tx = c->tex.tables();
     P.cam_dev = c->d_cam;
     P.refs_dev = c->d_refs;
     P.gray_light = wf_gray_light(c);
@@ -405,7 +408,8 @@ int mfxh::dev_trace_accumulate(mfx_ctx* c, int32_t spp, int64_t sample_base, Res
     // is exact, and its per-path arithmetic is the wavefront's, so the bits are the same; it does
     // not pay the wavefront's per-bounce launches over a 2 M-path frame (r02e: 1.7 vs 7.9 ms at 1080p).
     // (several lights: always the wavefront, as under MFX_F_WAVEFRONT; creation refused MFX_F_MEGAKERNEL)
-    c->mega_last = !wf_multi_light(c) && ((c->flags & MFX_F_MEGAKERNEL) != 0 || (ns == 1 && (c->flags & MFX_F_WAVEFRONT) == 0));
+    // (albedo textures: likewise)
+    c->mega_last = !wf_multi_light(c) && !wf_textured(c) && ((c->flags & MFX_F_MEGAKERNEL) != 0 || (ns == 1 && (c->flags & MFX_F_WAVEFRONT) == 0));
     if (ns == 0) {  // this partition has no sample in the call: zero rays in zero device time
         HIPCHECK(hipEventRecord(c->ev0, c->stream));
         HIPCHECK(hipEventRecord(c->ev1, c->stream));

@@ -30,6 +30,7 @@
 
 #include "mfx_camera_cuts.h"
 #include "mfx_layout.h"
+#include "mfx_texture.h"
 
 #define WF_FREE 0
 #define WF_NEED_EXT 1
@@ -205,6 +206,12 @@ struct WfParams {
     // whose packets start from their tile's row; null: from the root.
     const MfxCutEntry* cuts;
     int32_t cut_cap;
+    // Albedo textures (mfx_create_textured with a textured primitive; otherwise all null, and none of the
+    // untextured kernel instances reads them). They run the TX instances of k_shadow and k_resolve: at a
+    // vertex k_shadow computes the texel id of the hit point by the rule of mfx_texture.h (MFX_TEXEL_NONE
+    // on an untextured primitive) and stores it in vtex, where k_resolve finds the texel its albedo takes.
+    MfxTexTables tx;
+    uint32_t* vtex;          // [vertex][stride] the vertex's texel id (beside vmat; allocated in textured contexts only)
 };
 #define WF_MAX_LIGHTS 64  // MFX_MAX_LIGHTS: a light index is 6 bits of k_shadow's pending flag word
 
@@ -245,6 +252,8 @@ hipError_t mfx_wf_tile_check(const TileCheckParams& C, hipStream_t st);
 #define WF_QUEUE_BYTES_PER_SLOT (MFX_RAY_QUEUE ? 6 * 8 + 7 * 4 : 0)
 // several lights: one byte per vertex more, the lit vertices' light indices (WfParams::vlt)
 #define WF_LIGHT_BYTES_PER_SLOT(nvert) (nvert)
+// albedo textures: four bytes per vertex more, the vertices' texel ids (WfParams::vtex)
+#define WF_TEXEL_BYTES_PER_SLOT(nvert) (4 * (nvert))
 
 #ifndef WF_STACK_LDS
 #define WF_STACK_LDS 16  // traversal stack entries per lane kept in LDS (deeper ones spill to HBM/L2)
@@ -269,11 +278,12 @@ struct WfLdsShape {
     int ninst;      // the scene's instances (0: a flat scene), min(ninst, WF_INST_LDS) records of them in LDS
     int nslot;      // slots' test prefixes
     bool ml;        // k_shadow's several-light instance (WfParams::lights set; the same LDS footprint)
+    bool tx;        // k_shadow's textured instance (WfParams::vtex set; its table pointers take 32 B of LDS more)
 };
 // resident blocks per CU of the kernel instance that holds shape s
 hipError_t mfx_wf_kernel_occupancy(const WfLdsShape& s, int* blocks_per_cu);
-// resident blocks per CU of k_resolve's accumulator instance (ml: the several-light one)
-hipError_t mfx_wf_resolve_occupancy(bool ml, int* blocks_per_cu);
+// resident blocks per CU of k_resolve's accumulator instance (ml: the several-light one, tx: the textured one)
+hipError_t mfx_wf_resolve_occupancy(bool ml, int* blocks_per_cu, bool tx = false);
 // resident blocks per CU of k_camera (camera-ray packets; cuts: its CUTS instance)
 hipError_t mfx_cam_occupancy(int stack_size, int* blocks_per_cu, bool cuts = false);
 // a ray queue's arrays (MFX_RAY_QUEUE): entries in the pool's shard ranges, counts per shard

@@ -911,6 +911,13 @@ struct PixParams {
     int32_t ntiles;
 };
 static_assert(sizeof(PixParams) == 72, "PixParams: k_shadow's LDS layout");
+// k_shadow's textured instances keep these in LDS after the scene references
+struct TxShd {
+    const double* uvrec;
+    const int32_t* ptex;
+    const MfxTexDesc* desc;
+    uint32_t* vtex;
+};
 // k_shadow's array pointers in its LDS (after the light)
 struct ShdPtrs {
     double *ox, *oy, *oz, *dx, *dy, *dz, *vei, *vls;
@@ -942,7 +949,13 @@ struct ShdPtrs {
 // footprint, and with it the blocks per CU, are the one-light instance's. A template parameter, not a
 // branch on the count: the one-light instances hold none of this (r04c: one run-time branch in the leaf
 // test cost 1.8 to 4 %).
-template <bool STATS, bool SPILL, int WAVES, int SK, bool Q, int LIST = WF_LIST_NONE, int NF = MFX_NF_ANY, bool ML = false>
+// TX: the instances for albedo textures (mfx_create_textured): after the shade record, the lane of a
+// textured primitive loads its 64-B UV record and its texture's descriptor, computes the texel id of the
+// hit point (mfx_texture.h) and stores it in P.vtex beside the vertex's material, all before the sampler
+// runs, so the record is dead by then; an untextured primitive stores MFX_TEXEL_NONE. The table pointers
+// lie in 32 B of LDS after the scene references (TxShd). A template parameter for ML's reason.
+template <bool STATS, bool SPILL, int WAVES, int SK, bool Q, int LIST = WF_LIST_NONE, int NF = MFX_NF_ANY, bool ML = false,
+          bool TX = false>
 __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
     constexpr bool INST = SK == WF_SK_INST, SLDS = SK == WF_SK_SLDS;
     extern __shared__ int lds_all[];
@@ -973,6 +986,10 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
     SceneRefs* refs_lds = (SceneRefs*)((PixParams*)((ShdPtrs*)(light_lds + 1) + 1) + 1);
     if (threadIdx.x == 2)  // (from device memory: kernel arguments beside `nodes` would be loaded with it)
         *refs_lds = SceneRefs{(const int32_t*)P.refs_dev[0], (const uint8_t*)P.refs_dev[1]};
+    [[maybe_unused]] const TxShd& X = *(const TxShd*)(refs_lds + 1);  // TX: after the scene references
+    if constexpr (TX) {
+        if (threadIdx.x == 4) *(TxShd*)(refs_lds + 1) = TxShd{P.tx.uvrec, P.tx.ptex, P.tx.desc, P.vtex};
+    }
     if (threadIdx.x == 1) {
         PixParams px;
         px.path_base = P.path_base; px.base_q = P.base_q; px.base_smp = P.base_smp; px.sample_base = P.sample_base;
@@ -1090,6 +1107,20 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
                     if ((sh.prim_kind & 3) == MFX_KIND_SPHERE) nm = vnormalize(vsub(hp, ld3(sh.n)));  // Sphere.fs:39-43
                     else nm = ld3(sh.n);
                     mat = sh.material;
+                    if constexpr (TX) {  // the vertex's texel id (v: this vertex's index, as below)
+                        const int prim = sh.prim_kind >> 2;
+                        const int tex = X.ptex[prim];
+                        uint32_t id = MFX_TEXEL_NONE;
+                        if (tex >= 0) {
+                            const double* r = X.uvrec + (int64_t)MFX_UV_RECORD_DOUBLES * prim;
+                            const double h3[3] = {hp.x, hp.y, hp.z};
+                            const double rec[8] = {r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]};
+                            double tu, tv;
+                            mfx_tx_uv(rec, h3, tu, tv);
+                            id = mfx_tx_texel(X.desc[tex], tu, tv);
+                        }
+                        X.vtex[(int64_t)(P.max_depth - (dw & 0xff)) * P.vstride + jr] = id;
+                    }
                     // the key k_extend derived for the path's camera ray (same expressions), derived
                     // again at every vertex from the path's slot instead of stored (8 B written at the
                     // first vertex and read at every later one: C2 +0.5 %, r05m)
@@ -1294,8 +1325,14 @@ struct PathRec {
     double ei[WF_RES_VERTS], cs[WF_RES_VERTS], so[WF_RES_VERTS];
     int mat[WF_RES_VERTS];
     int lt[WF_RES_VERTS];  // ML: a lit vertex's light (P.vlt); the one-light instances never touch it
+    uint32_t tx[WF_RES_VERTS];  // TX: the vertex's texel (MFX_TEXEL_NONE: untextured); the untextured instances never touch it
 };
-template <bool ML>
+// TX: the vertex's texel, gathered through its id (P.vtex); MFX_TEXEL_NONE stands for an untextured vertex
+__device__ __forceinline__ uint32_t load_texel(const WfParams& P, int64_t at) {
+    const uint32_t id = P.vtex[at];
+    return id == MFX_TEXEL_NONE ? MFX_TEXEL_NONE : P.tx.texels[id];
+}
+template <bool ML, bool TX>
 __device__ __forceinline__ void load_path(const WfParams& P, int64_t j, int mask, PathRec& R) {
     R.mask = mask;
     if (mask == 0) return;
@@ -1304,9 +1341,11 @@ __device__ __forceinline__ void load_path(const WfParams& P, int64_t j, int mask
     for (int v = 0; v < WF_RES_VERTS; ++v) {
         R.ei[v] = 0.0; R.cs[v] = 0.0; R.so[v] = 0.0; R.mat[v] = 0;
         if constexpr (ML) R.lt[v] = 0;
+        if constexpr (TX) R.tx[v] = MFX_TEXEL_NONE;
         if (v <= top) {
             R.ei[v] = P.vei[v * P.vstride + j];
             R.mat[v] = P.vmat[v * P.vstride + j];
+            if constexpr (TX) R.tx[v] = load_texel(P, v * P.vstride + j);
             if ((mask >> v) & 1) {
                 const double* vl = P.vls + (int64_t)(2 * v) * P.vstride + j;
                 R.cs[v] = vl[0];  // (a gray light: a_v itself)
@@ -1323,15 +1362,26 @@ __device__ __forceinline__ void load_path(const WfParams& P, int64_t j, int mask
 //   f  <- (a_v + f) * c_v                             (Integrators.fs:135-136, pdf = 1)
 // ML (several lights): the lit vertex's light lt selects I and pdf_n from the kernel's LDS table
 // lt_lds[light][4] = I[0..2], pdf_n; the same expression, one rounding per operation. Never gray.
-template <bool ML>
+// TX (albedo textures): the albedo is the material's times the vertex's texel, a[c] = al[c] * (byte_c / 255.0)
+// (mfx_texture.h); a texel whose three bytes are 255, MFX_TEXEL_NONE among them, leaves it as it is, which
+// is what the product gives (byte / 255.0 is exactly 1.0).
+template <bool ML, bool TX>
 __device__ __forceinline__ void fold_vertex(const WfParams& P, bool lit, double ei, int mat, double cs, double so,
                                             const double* alb_lds, double& fx, double& fy, double& fz,
-                                            const double* lt_lds, int lt) {
+                                            const double* lt_lds, int lt, uint32_t texel) {
     [[maybe_unused]] const MfxLight& LT = P.light;
     const double* al = mat < WF_RES_MAT_LDS ? alb_lds + 3 * mat : P.albedo + 3 * mat;
-    const double cx = TWOPI * (ei * (INVPI * al[0]));
-    const double cy = TWOPI * (ei * (INVPI * al[1]));
-    const double cz = TWOPI * (ei * (INVPI * al[2]));
+    double a0 = al[0], a1 = al[1], a2 = al[2];
+    if constexpr (TX) {
+        if ((texel & 0xffffffu) != 0xffffffu) {
+            a0 = mfx_tx_albedo(a0, texel, 0);
+            a1 = mfx_tx_albedo(a1, texel, 1);
+            a2 = mfx_tx_albedo(a2, texel, 2);
+        }
+    }
+    const double cx = TWOPI * (ei * (INVPI * a0));
+    const double cy = TWOPI * (ei * (INVPI * a1));
+    const double cz = TWOPI * (ei * (INVPI * a2));
     double ax = 0.0, ay = 0.0, az = 0.0;
     if constexpr (ML) {
         if (lit) {
@@ -1351,7 +1401,7 @@ __device__ __forceinline__ void fold_vertex(const WfParams& P, bool lit, double 
     fy = (ay + fy) * cy;
     fz = (az + fz) * cz;
 }
-template <bool ML>
+template <bool ML, bool TX>
 __device__ __forceinline__ void fold_path(const WfParams& P, int64_t j, const PathRec& R, const double* alb_lds,
                                           double& fx, double& fy, double& fz, const double* lt_lds) {
     const int top = 31 - __builtin_clz(R.mask);
@@ -1359,15 +1409,18 @@ __device__ __forceinline__ void fold_path(const WfParams& P, int64_t j, const Pa
     for (int v = top; v >= WF_RES_VERTS; --v) {
         const bool lit = (R.mask >> v) & 1;
         const double* vl = P.vls + (int64_t)(2 * v) * P.vstride + j;
-        fold_vertex<ML>(P, lit, P.vei[v * P.vstride + j], P.vmat[v * P.vstride + j], lit ? vl[0] : 0.0,
-                        lit ? vl[P.vstride] : 0.0, alb_lds, fx, fy, fz, lt_lds,
-                        (ML && lit) ? P.vlt[v * P.vstride + j] & (WF_MAX_LIGHTS - 1) : 0);
+        uint32_t texel = MFX_TEXEL_NONE;
+        if constexpr (TX) texel = load_texel(P, v * P.vstride + j);
+        fold_vertex<ML, TX>(P, lit, P.vei[v * P.vstride + j], P.vmat[v * P.vstride + j], lit ? vl[0] : 0.0,
+                            lit ? vl[P.vstride] : 0.0, alb_lds, fx, fy, fz, lt_lds,
+                            (ML && lit) ? P.vlt[v * P.vstride + j] & (WF_MAX_LIGHTS - 1) : 0, texel);
     }
     // the batched ones, indices known at compile time (the records stay in registers)
 #pragma unroll
     for (int v = WF_RES_VERTS - 1; v >= 0; --v)
         if (v <= top)
-            fold_vertex<ML>(P, (R.mask >> v) & 1, R.ei[v], R.mat[v], R.cs[v], R.so[v], alb_lds, fx, fy, fz, lt_lds, ML ? R.lt[v] : 0);
+            fold_vertex<ML, TX>(P, (R.mask >> v) & 1, R.ei[v], R.mat[v], R.cs[v], R.so[v], alb_lds, fx, fy, fz, lt_lds,
+                                ML ? R.lt[v] : 0, TX ? R.tx[v] : MFX_TEXEL_NONE);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1399,7 +1452,9 @@ __device__ __forceinline__ void fold_path(const WfParams& P, int64_t j, const Pa
 #define WF_RES_MOMENTS 2
 // ML: the instances for several lights: every light's intensity and pdf_n in LDS (2 KB for 64 lights),
 // indexed by the light a lit vertex recorded (P.vlt); the one-light instances carry none of it
-template <int MODE, bool ML = false>
+// TX: the instances for albedo textures: every vertex's texel, gathered through the id k_shadow<TX> stored
+// (P.vtex), scales its albedo; the untextured instances carry none of it
+template <int MODE, bool ML = false, bool TX = false>
 __global__ void __launch_bounds__(256) k_resolve(WfParams P) {
     constexpr bool FRAMES = MODE == WF_RES_FRAMES, MOM = MODE == WF_RES_MOMENTS;
     __shared__ double alb[3 * WF_RES_MAT_LDS];
@@ -1470,12 +1525,12 @@ __global__ void __launch_bounds__(256) k_resolve(WfParams P) {
         }
         PathRec R[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) load_path<ML>(P, jv[u], mask[u], R[u]);
+        for (int u = 0; u < U; ++u) load_path<ML, TX>(P, jv[u], mask[u], R[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (!in[u]) continue;
             double fx = 0.0, fy = 0.0, fz = 0.0;
-            if (R[u].mask) fold_path<ML>(P, jv[u], R[u], alb, fx, fy, fz, lt_lds);
+            if (R[u].mask) fold_path<ML, TX>(P, jv[u], R[u], alb, fx, fy, fz, lt_lds);
             if (FRAMES) {
                 ax = ax + (0.0 + fx) / 1.0;
                 ay = ay + (0.0 + fy) / 1.0;
@@ -1518,7 +1573,7 @@ static size_t wf_lds_bytes(const WfLdsShape& s) {
     const size_t stacks = (size_t)s.ntop * sizeof(MfxNode) + (size_t)std::min(s.ninst, WF_INST_LDS) * sizeof(MfxInstance) +
                           (size_t)s.nslot * 80 + (size_t)4 * s.stack_lds * 64 * sizeof(int);
     return s.shadow ? stacks + 4 * PendShd::BYTES + 64 + 4 * 2 * WF_SHD_LIST * sizeof(int) + sizeof(MfxLight) + sizeof(ShdPtrs) +
-                          sizeof(PixParams) + sizeof(SceneRefs)
+                          sizeof(PixParams) + sizeof(SceneRefs) + (s.tx ? sizeof(TxShd) : 0)
                     : stacks + 4 * WF_EXT_PEND * sizeof(int) + 64;
 }
 
@@ -1533,11 +1588,12 @@ struct WfKey {
     int nf;     // MFX_NF_*
     int waves;  // k_shadow's build: 3 or 4 waves per SIMD
     bool ml;    // k_shadow's several-light instance (WfParams::lights)
+    bool tx;    // k_shadow's textured instance (WfParams::vtex)
 };
 // a key's number, and the key of a number: the one place a field passes between run time and compile time
-constexpr int WF_KEYS = 2 * 2 * 2 * 3 * 2 * 2 * 3 * 3 * 2;
+constexpr int WF_KEYS = 2 * 2 * 2 * 2 * 3 * 2 * 2 * 3 * 3 * 2;
 static constexpr int key_index(const WfKey& k) {
-    return (((((((k.ml * 2 + k.stats) * 2 + k.spill) * 3 + k.sk) * 2 + k.queue) * 2 + k.start) * 3 + k.list) * 3 + k.nf) * 2 +
+    return ((((((((k.tx * 2 + k.ml) * 2 + k.stats) * 2 + k.spill) * 3 + k.sk) * 2 + k.queue) * 2 + k.start) * 3 + k.list) * 3 + k.nf) * 2 +
            (k.waves - 3);
 }
 static constexpr WfKey key_at(int i) {
@@ -1550,7 +1606,8 @@ static constexpr WfKey key_at(int i) {
     k.sk = i % 3, i /= 3;
     k.spill = i % 2, i /= 2;
     k.stats = i % 2, i /= 2;
-    k.ml = i;
+    k.ml = i % 2, i /= 2;
+    k.tx = i;
     return k;
 }
 
@@ -1584,12 +1641,16 @@ static constexpr bool nf_built(const WfKey& k) {
 // (a queue's entries are never FREE slots; only the iteration that starts paths maps them through a list)
 // (several lights, ml: k_shadow alone reads a light, and its ML instances are the 4-wave build without
 // the traversal counters: contexts with several lights refuse MFX_F_COUNT_STATS and take the 4-wave build)
+// (albedo textures, tx: as ml, k_shadow alone computes a texel id, in the 4-wave build without counters, and
+// in both ml states: textured contexts refuse MFX_F_COUNT_STATS too)
 static constexpr bool extend_built(const WfKey& k) {
-    return !k.ml && k.waves == 4 && nf_built(k) && (k.queue ? !k.start && !k.list : k.start || !k.list);
+    return !k.ml && !k.tx && k.waves == 4 && nf_built(k) && (k.queue ? !k.start && !k.list : k.start || !k.list);
 }
-static constexpr bool shadow_built(const WfKey& k) { return !k.start && nf_built(k) && (!k.ml || (!k.stats && k.waves == 4)); }
+static constexpr bool shadow_built(const WfKey& k) {
+    return !k.start && nf_built(k) && ((!k.ml && !k.tx) || (!k.stats && k.waves == 4));
+}
 static constexpr bool camera_built(const WfKey& k) {
-    return !k.ml && !k.spill && k.sk == WF_SK_FLAT && !k.queue && k.start && k.nf == MFX_NF_ANY && k.waves == 4;
+    return !k.ml && !k.tx && !k.spill && k.sk == WF_SK_FLAT && !k.queue && k.start && k.nf == MFX_NF_ANY && k.waves == 4;
 }
 static constexpr int built_count(bool (*built)(const WfKey&)) {
     int n = 0;
@@ -1597,10 +1658,11 @@ static constexpr int built_count(bool (*built)(const WfKey&)) {
     return n;
 }
 static_assert(built_count(extend_built) == (MFX_NODE_F16 ? 64 : 60) &&
-                  built_count(shadow_built) == (MFX_NODE_F16 ? 152 + 40 : 144 + 36) && built_count(camera_built) == 6,
+                  built_count(shadow_built) == (MFX_NODE_F16 ? 152 + 3 * 40 : 144 + 3 * 36) && built_count(camera_built) == 6,
               "a new instance is a decision: every one is a kernel to compile, and an occupancy to ask about "
               "(k_shadow: 152 / 144 one-light instances, plus the several-light ones, ML: every spill, scene kind, "
-              "queue and list of the 4-wave build without counters, 36, and the FP16 format of the 4 flat unlisted ones)");
+              "queue and list of the 4-wave build without counters, 36, and the FP16 format of the 4 flat unlisted ones; "
+              "the textured ones, TX, are as many again in each ML state)");
 
 enum { WF_K_EXTEND, WF_K_SHADOW, WF_K_CAMERA, WF_K_CAMERA_CUTS };
 template <int KERNEL, int I>
@@ -1609,7 +1671,7 @@ static const void* instance_at() {
     if constexpr (KERNEL == WF_K_EXTEND && extend_built(k))
         return (const void*)k_extend<k.stats, k.spill, k.sk, k.queue, k.start, k.list, k.nf>;
     else if constexpr (KERNEL == WF_K_SHADOW && shadow_built(k))
-        return (const void*)k_shadow<k.stats, k.spill, k.waves, k.sk, k.queue, k.list, k.nf, k.ml>;
+        return (const void*)k_shadow<k.stats, k.spill, k.waves, k.sk, k.queue, k.list, k.nf, k.ml, k.tx>;
     else if constexpr (KERNEL == WF_K_CAMERA && camera_built(k))
         return (const void*)k_camera<k.stats, k.list>;
     else if constexpr (KERNEL == WF_K_CAMERA_CUTS && camera_built(k))  // every k_camera instance has its CUTS twin
@@ -1633,11 +1695,11 @@ static const void* camera_kernel(const WfKey& k, bool cuts) {
 
 // the key of k_extend or k_shadow holding shape s
 static WfKey shape_key(const WfLdsShape& s, bool stats, bool queue, bool start, int list, int waves) {
-    WfKey k{stats, s.spill, scene_kind(s.ninst > 0, s.nslot), queue, start, list, MFX_NF_ANY, waves, s.shadow && s.ml};
+    WfKey k{stats, s.spill, scene_kind(s.ninst > 0, s.nslot), queue, start, list, MFX_NF_ANY, waves, s.shadow && s.ml, s.shadow && s.tx};
     if (wf_nf_fixed(k)) k.nf = s.fp16 ? MFX_NF_H : MFX_NF_F32;
     return k;
 }
-static WfKey camera_key(bool stats, int list) { return {stats, false, WF_SK_FLAT, false, true, list, MFX_NF_ANY, 4, false}; }
+static WfKey camera_key(bool stats, int list) { return {stats, false, WF_SK_FLAT, false, true, list, MFX_NF_ANY, 4, false, false}; }
 
 // The query asks the instance a launch of the shape runs, with two deliberate differences: the 4-wave
 // k_shadow whatever the context's build (scene_shapes chooses the 3-wave build from the answer), and, for
@@ -1674,7 +1736,8 @@ static void launch(const void* kernel, int grid, size_t lds, hipStream_t st, con
 static WfLdsShape lds_shape(const WfParams& P, bool shadow) {
     const int stack_lds = shadow ? P.stack_lds_shd : P.stack_lds_ext;
     return {shadow, stack_lds < P.stack_size, wf_fp16(P), stack_lds, shadow ? P.ntop_shd : P.ntop_ext,
-            P.inst ? P.ninst_lds : 0, shadow ? P.nslot_shd : P.nslot_ext, shadow && P.lights != nullptr};
+            P.inst ? P.ninst_lds : 0, shadow ? P.nslot_shd : P.nslot_ext, shadow && P.lights != nullptr,
+            shadow && P.vtex != nullptr};
 }
 
 static hipError_t launch_iteration(const WfParams& P, int ext_grid, int shd_grid, bool stats, hipStream_t st,
@@ -1694,7 +1757,7 @@ static hipError_t launch_iteration(const WfParams& P, int ext_grid, int shd_grid
     const WfLdsShape s = lds_shape(P, true);
     const bool queue = P.qslot || P.ncount;
     const void* shd = shadow_kernel(shape_key(s, stats, queue, false, list, shadow_build(P.shadow_waves)));
-    if (!shd) return hipErrorInvalidValue;  // (several lights with counters or the 3-wave build: refused at creation)
+    if (!shd) return hipErrorInvalidValue;  // (several lights or textures with counters or the 3-wave build: refused at creation)
     launch(shd, shd_grid, wf_lds_bytes(s), st, P);
     return hipSuccess;
 }
@@ -1703,6 +1766,8 @@ hipError_t mfx_wf_iteration(const WfParams& P, int ext_grid, int shd_grid, bool 
                             hipEvent_t* ev) {
     // several lights: the table, its count and the index plane go together (k_shadow<ML> writes vlt)
     if (P.lights && (!P.vlt || P.nlights < 2 || P.nlights > WF_MAX_LIGHTS || P.gray_light || stats)) return hipErrorInvalidValue;
+    // albedo textures: the id plane and the tables go together (k_shadow<TX> reads the tables and writes vtex)
+    if (P.vtex && (!P.tx.uvrec || !P.tx.ptex || !P.tx.desc || !P.tx.texels || stats)) return hipErrorInvalidValue;
     // the chunk heads and, beside them (WF_CTL_Q0 / WF_CTL_Q1), the next queue's shard counts
     unsigned long long* z = P.ctl;
     size_t nz = WF_NCTL;
@@ -1717,31 +1782,34 @@ hipError_t mfx_wf_iteration(const WfParams& P, int ext_grid, int shd_grid, bool 
     return hipGetLastError();
 }
 
+// k_resolve's instance of a mode: several lights (ML) and albedo textures (TX) each have one
+template <int MODE>
+static const void* resolve_kernel(bool ml, bool tx) {
+    return ml ? (tx ? (const void*)k_resolve<MODE, true, true> : (const void*)k_resolve<MODE, true, false>)
+              : (tx ? (const void*)k_resolve<MODE, false, true> : (const void*)k_resolve<MODE, false, false>);
+}
+static hipError_t launch_resolve(const void* kernel, int64_t threads, hipStream_t st, const WfParams& P) {
+    void* args[] = {const_cast<WfParams*>(&P)};
+    const hipError_t e = hipLaunchKernel(kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), args, 0, st);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
 hipError_t mfx_wf_resolve(const WfParams& P, hipStream_t st) {
     const bool ml = P.lights != nullptr;  // several lights: the ML instance of each mode
+    const bool tx = P.vtex != nullptr;    // albedo textures: the TX instance
     if (ml && (!P.vlt || P.nlights < 2 || P.nlights > WF_MAX_LIGHTS || P.gray_light)) return hipErrorInvalidValue;
+    if (tx && !P.tx.texels) return hipErrorInvalidValue;
     if (P.mom || P.ntiles > 0) {  // the adaptive sampler's passes: the moments instance (a listed trace runs no other)
         if (!P.mom || P.film || P.res_ntx > 0) return hipErrorInvalidValue;
         const int64_t n = P.ntiles > 0 ? (int64_t)P.ntiles * 64 : (int64_t)((P.width + 7) >> 3) * P.band_rows * 64;
-        if (ml) hipLaunchKernelGGL((k_resolve<WF_RES_MOMENTS, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P);
-        else hipLaunchKernelGGL(k_resolve<WF_RES_MOMENTS>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P);
-        return hipGetLastError();
+        return launch_resolve(resolve_kernel<WF_RES_MOMENTS>(ml, tx), n, st, P);
     }
     const int64_t per_sample = (int64_t)(P.res_ntx > 0 ? P.res_ntx : (P.width + 7) >> 3) * P.band_rows * 64;
-    const dim3 grid((unsigned)((per_sample + 255) / 256));
-    if (ml) {
-        if (P.film) hipLaunchKernelGGL((k_resolve<WF_RES_FRAMES, true>), grid, dim3(256), 0, st, P);
-        else hipLaunchKernelGGL((k_resolve<WF_RES_ACCUM, true>), grid, dim3(256), 0, st, P);
-        return hipGetLastError();
-    }
-    if (P.film) hipLaunchKernelGGL(k_resolve<WF_RES_FRAMES>, dim3((unsigned)((per_sample + 255) / 256)), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL(k_resolve<WF_RES_ACCUM>, dim3((unsigned)((per_sample + 255) / 256)), dim3(256), 0, st, P);
-    return hipGetLastError();
+    return launch_resolve(P.film ? resolve_kernel<WF_RES_FRAMES>(ml, tx) : resolve_kernel<WF_RES_ACCUM>(ml, tx), per_sample, st, P);
 }
 
-hipError_t mfx_wf_resolve_occupancy(bool ml, int* blocks_per_cu) {
-    return ml ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_resolve<WF_RES_ACCUM, true>, 256, 0)
-              : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_resolve<WF_RES_ACCUM>, 256, 0);
+hipError_t mfx_wf_resolve_occupancy(bool ml, int* blocks_per_cu, bool tx) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, resolve_kernel<WF_RES_ACCUM>(ml, tx), 256, 0);
 }
 
 // ------------------------------------------------------------------------------------------------

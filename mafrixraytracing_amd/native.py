@@ -12,8 +12,8 @@ import numpy as np
 
 from .abi import (INSTANCING_KEYS, LAUNCH_INFO_KEYS, MFX_DN_SRC_ACCUM, MFX_DN_SRC_ADAPTIVE, MFX_DN_SRC_HOST,
                   MFX_DN_SRC_TEMPORAL, MFX_F_NONE, MFX_F_TWO_LEVEL, MfxAdaptive, MfxAdaptiveResume, MfxDenoiseCfg,
-                  MfxDenoiseVarCfg, MfxInstance, MfxOptions, MfxTemporalCfg, SceneArrays, check, dptr, iptr, load_library,
-                  pinhole_struct, quad_lights)
+                  MfxDenoiseVarCfg, MfxInstance, MfxOptions, MfxPrimUv, MfxTemporalCfg, PRIM_UV_DTYPE, SceneArrays, check, dptr,
+                  iptr, load_library, pinhole_struct, quad_lights, texture_structs)
 from .denoise import DenoiseConfig, DenoiseVarConfig
 from .temporal import TemporalConfig
 
@@ -26,7 +26,8 @@ class NativeContext:
 
     def __init__(self, arrays: SceneArrays, seed: int = DEFAULT_SEED, device: int = 0, flags: int = MFX_F_NONE,
                  part_index: int = 0, part_count: int = 1, devices: list[int] | None = None,
-                 instancing: bool = True, render_ahead: int = 0, lights: list | None = None):
+                 instancing: bool = True, render_ahead: int = 0, lights: list | None = None,
+                 textures: list | None = None, prim_uv: np.ndarray | None = None):
         """devices: drive this list of HIP devices from one context (mfx_options.devices; the
         library's own RCCL reduce sums them into devices[0]); None: the single `device`.
         instancing: a scene with instancing data is created through mfx_create_instanced (two-level
@@ -36,7 +37,12 @@ class NativeContext:
         lights: a list of light dicts (scene_io's shape: p, normal, intensity) creates the context through
         mfx_create_lights (one light picked per path vertex, the image is the lights' sum; they replace
         arrays.light). Pass arrays.lights for a scene loaded with all_lights=True. None: mfx_create /
-        mfx_create_instanced with arrays.light alone, whatever arrays.lights holds."""
+        mfx_create_instanced with arrays.light alone, whatever arrays.lights holds.
+        textures, prim_uv: albedo textures ((H, W, 4) uint8 arrays, rows top to bottom) and the primitives' maps
+        (abi.PRIM_UV_DTYPE, one per primitive the context is created from: the templates of an instanced
+        scene, the world list otherwise) create the context through mfx_create_textured, with `lights` or
+        arrays.light. Pass arrays.textures and arrays.prim_uv for a scene loaded with textures=True. None:
+        an untextured context, whatever arrays holds."""
         self.lib = load_library()
         self.arrays = arrays
         self.w, self.h = arrays.width, arrays.height
@@ -51,7 +57,20 @@ class NativeContext:
                          devices=C.cast(self._devs, C.POINTER(C.c_int32)) if devices else None)
         h = C.c_void_p()
         self.lights = list(lights) if lights is not None else None
-        if self.lights is not None:
+        if textures is not None or prim_uv is not None:
+            ls = self.lights if self.lights is not None else [arrays.light]
+            self._lights = quad_lights(ls)
+            self._inst = arrays.instancing[1] if inst else None
+            ip = self._inst.ctypes.data_as(C.POINTER(MfxInstance)) if inst else None
+            self._tex, self._tex_keep = texture_structs(textures or [])
+            self._uv = np.ascontiguousarray(prim_uv, dtype=PRIM_UV_DTYPE) if prim_uv is not None else None
+            if self._uv is not None and len(self._uv) != self._desc.nprims:
+                raise ValueError(f"prim_uv has {len(self._uv)} entries for {self._desc.nprims} primitives")
+            up = self._uv.ctypes.data_as(C.POINTER(MfxPrimUv)) if self._uv is not None else None
+            check(self.lib.mfx_create_textured(C.byref(self._desc), self._lights, len(ls), ip,
+                                               len(self._inst) if inst else 0, self._tex, len(self._tex_keep), up,
+                                               C.byref(opt), C.byref(h)), "mfx_create_textured")
+        elif self.lights is not None:
             self._lights = quad_lights(self.lights)
             self._inst = arrays.instancing[1] if inst else None
             ip = self._inst.ctypes.data_as(C.POINTER(MfxInstance)) if inst else None
@@ -406,6 +425,14 @@ class NativeContext:
         per CU of the k_shadow / k_resolve instance in use; the rest 0."""
         out = np.zeros(8)
         check(self.lib.mfx_light_info(self._h, dptr(out)), "mfx_light_info")
+        return out
+
+    def texture_info(self) -> np.ndarray:
+        """mfx_texture_info: [0] textures, [1] 1 if the textured kernel instances run, [2] bytes of texels,
+        [3] bytes of the UV table, [4] bytes per path slot the textures add to the pool, [5] / [6] resident
+        blocks per CU of the k_shadow / k_resolve instance in use; [7] 0."""
+        out = np.zeros(8)
+        check(self.lib.mfx_texture_info(self._h, dptr(out)), "mfx_texture_info")
         return out
 
     def instancing_info(self) -> dict:

@@ -15,6 +15,13 @@ OBJ inputs produce the same primitive list, in the same order, with the same mat
     NewAreaLight(trig1.v0, trig1.v1, trig1.v2, trig2.v2, trig1.normal, I) (Scene.fs:180-194).
   * Camera defaults fov 60 / aspect 1.333 (Scene.fs:61-62), film defaults 800x800 (:203-204).
 
+Albedo textures (an extension; textures=True on load_obj, load_mtl, InitSceneState and
+load_scene_file): `vt` lines and the faces' `v/vt` indices are kept, an MTL's `map_Kd` is read (a `.npy` holding an
+(H, W, 3 or 4) uint8 array, or an image through PIL when it imports), and a face whose material has a map
+and whose corners all have a `vt` carries them into SceneArrays.textures / prim_uv (mfx_create_textured).
+A shapelist or instances element replaces the material, as ever, and keeps the face's map. Without
+textures=True nothing of this is read and every result is what it was.
+
 Documented extensions: `vt`/`vn`/`o`/`s` lines are accepted and ignored
 (an `o` name may contain dots, which FindModel's `model.group` split rejects), trailing whitespace/CR is trimmed from group names (the
 FParsec grammar as shipped rejects the bundled meshes — SURVEY.md §0.4); a `.npz` mesh
@@ -36,7 +43,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .abi import (INSTANCE_DTYPE, MFX_INSTANCE_VERBATIM, MFX_PRIM_RECT, MFX_PRIM_SPHERE, MFX_PRIM_TRIANGLE,
-                  PRIM_DTYPE, SceneArrays)
+                  PRIM_DTYPE, PRIM_UV_DTYPE, SceneArrays)
 
 
 class SceneError(ValueError):
@@ -51,6 +58,11 @@ class MaterialManager:
 
     def __init__(self):
         self.materials: list[tuple[float, float, float]] = []
+        # albedo textures read so far (textures=True loads): (H, W, 4) uint8 arrays, the file each came from,
+        # and the texture of a material whose MTL entry has a map_Kd
+        self.textures: list[np.ndarray] = []
+        self.texture_files: dict[str, int] = {}
+        self.material_texture: dict[int, int] = {}
 
     @classmethod
     def GetManager(cls) -> "MaterialManager":
@@ -96,6 +108,26 @@ class Prim:
     kind: int
     pts: tuple
     material: int
+    uv: tuple | None = None  # textures=True: the (u, v) of the first three corners of a face with a map
+    texture: int = -1        # and its texture (MaterialManager.textures)
+
+
+def load_texture(path: str) -> np.ndarray:
+    """An albedo map as an (H, W, 4) uint8 array, rows top to bottom: a `.npy` of shape (H, W, 3 or 4), or an
+    image file through PIL. The bytes are taken as they are (linear)."""
+    if path.endswith(".npy"):
+        a = np.load(path, allow_pickle=False)
+    else:
+        try:
+            from PIL import Image
+        except ImportError as e:
+            raise SceneError(f"{path}: reading an image map_Kd needs PIL (a .npy map does not)") from e
+        a = np.asarray(Image.open(path).convert("RGBA"))
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4):
+        raise SceneError(f"{path}: a texture must be an (H, W, 3 or 4) uint8 array, got {a.dtype} {a.shape}")
+    out = np.full((a.shape[0], a.shape[1], 4), 255, dtype=np.uint8)
+    out[..., :a.shape[2]] = a
+    return out
 
 
 @dataclass
@@ -105,16 +137,25 @@ class ObjState:
     groups: dict = field(default_factory=lambda: {"default": []})
 
 
-def load_mtl(path: str, manager: MaterialManager) -> dict:
-    """LoadObjMtl (Obj_Mtl.fs:199-217): each `newmtl` becomes Lambertian(Ka) in the manager."""
+def load_mtl(path: str, manager: MaterialManager, textures: bool = False) -> dict:
+    """LoadObjMtl (Obj_Mtl.fs:199-217): each `newmtl` becomes Lambertian(Ka) in the manager.
+    textures: a material's `map_Kd` file (relative to the MTL) is read into manager.textures, once per file,
+    and recorded as the material's texture (manager.material_texture)."""
     refs: dict[str, int] = {}
     name = None
     ka = (0.0, 0.0, 0.0)
+    kd_map = None
     started = False
 
     def flush():
         if started:
             refs[name] = manager.Add(ka)
+            if kd_map is not None:
+                full = os.path.abspath(os.path.join(os.path.dirname(path), kd_map))
+                if full not in manager.texture_files:
+                    manager.texture_files[full] = len(manager.textures)
+                    manager.textures.append(load_texture(full))
+                manager.material_texture[refs[name]] = manager.texture_files[full]
 
     with open(path, "r", encoding="utf-8", errors="replace") as f:
         for raw in f:
@@ -124,9 +165,11 @@ def load_mtl(path: str, manager: MaterialManager) -> dict:
             tok = line.split()
             if tok[0] == "newmtl":
                 flush()
-                started, name, ka = True, line[len("newmtl"):].strip(), (0.0, 0.0, 0.0)
+                started, name, ka, kd_map = True, line[len("newmtl"):].strip(), (0.0, 0.0, 0.0), None
             elif tok[0] == "Ka" and len(tok) >= 4:
                 ka = (float(tok[1]), float(tok[2]), float(tok[3]))
+            elif textures and tok[0] == "map_Kd" and len(tok) >= 2:
+                kd_map = tok[-1]  # (options such as -s come before the file name)
     flush()
     return refs
 
@@ -135,11 +178,14 @@ def _vi(i: int, n: int) -> int:
     return i - 1 if i > 0 else n + i  # VertexReferencing.VI, ObjModelLoader.fs:63-64
 
 
-def load_obj(path: str, manager: MaterialManager) -> ObjState:
-    """LoadObjModel (ObjModelLoader.fs:306-340) plus the documented grammar extensions."""
+def load_obj(path: str, manager: MaterialManager, textures: bool = False) -> ObjState:
+    """LoadObjModel (ObjModelLoader.fs:306-340) plus the documented grammar extensions.
+    textures: keep `vt` and the faces' `v/vt` indices, and read the MTL's map_Kd (a `.npz` mesh carries no
+    UVs: its primitives stay untextured)."""
     if path.endswith(".npz"):
         return load_npz_mesh(path, manager)
     st = ObjState()
+    vts: list = []
     with open(path, "r", encoding="utf-8", errors="replace") as f:
         lines = f.read().split("\n")
     # the reference loads the first mtllib before replaying statements (:317-330)
@@ -148,7 +194,7 @@ def load_obj(path: str, manager: MaterialManager) -> ObjState:
         tok = raw.split()
         if tok and tok[0] == "mtllib":
             mtl_path = os.path.join(os.path.dirname(path), tok[1])
-            mtl_refs = load_mtl(mtl_path, manager)
+            mtl_refs = load_mtl(mtl_path, manager, textures)
             break
     usemtl = "white"
     cur = "default"
@@ -162,6 +208,10 @@ def load_obj(path: str, manager: MaterialManager) -> ObjState:
             if len(tok) < 4:
                 raise SceneError(f"{path}: vertex needs 3 coordinates: {line!r}")
             st.vertices.append((float(tok[1]), float(tok[2]), float(tok[3])))
+        elif key == "vt" and textures:
+            if len(tok) < 3:
+                raise SceneError(f"{path}: vt needs 2 coordinates: {line!r}")
+            vts.append((float(tok[1]), float(tok[2])))
         elif key in ("vt", "vn", "s", "o", "mtllib", "maplib", "usemap"):
             continue
         elif key == "g":
@@ -174,10 +224,16 @@ def load_obj(path: str, manager: MaterialManager) -> ObjState:
             n = len(st.vertices)
             pts = tuple(st.vertices[_vi(i, n)] for i in refs)
             mat = mtl_refs.get(usemtl, 0)
+            uv, tex = None, -1
+            if textures and mat in manager.material_texture:
+                parts = [t.split("/") for t in tok[1:]]
+                if all(len(q) >= 2 and q[1] for q in parts):  # every corner has a vt: the first three map the face
+                    uv = tuple(vts[_vi(int(q[1]), len(vts))] for q in parts[:3])
+                    tex = manager.material_texture[mat]
             if len(pts) == 3:
-                st.groups[cur].append(Prim(MFX_PRIM_TRIANGLE, pts, mat))
+                st.groups[cur].append(Prim(MFX_PRIM_TRIANGLE, pts, mat, uv, tex))
             elif len(pts) == 4:
-                st.groups[cur].append(Prim(MFX_PRIM_RECT, pts, mat))
+                st.groups[cur].append(Prim(MFX_PRIM_RECT, pts, mat, uv, tex))
             else:
                 raise SceneError(f"{path}: face with {len(pts)} vertices (only 3 or 4 supported)")
     return st
@@ -259,6 +315,8 @@ class SceneState:
     templates: dict = field(default_factory=dict)
     # InitSceneState(all_lights=True): every <Light> element in document order (None: `light` alone)
     lights: list | None = None
+    # InitSceneState(textures=True): SceneArrays gets the manager's textures and the primitives' maps
+    textures: bool = False
 
     def arrays(self, max_depth: int = 3, width: int | None = None, height: int | None = None) -> SceneArrays:
         inst = None
@@ -277,7 +335,20 @@ class SceneState:
                     tmpl.extend(self.prims[start:start + count])
             inst = (_prim_array(tmpl), np.array(rows, dtype=INSTANCE_DTYPE))
         return SceneArrays(_prim_array(self.prims), self.manager.albedo_table(), self.light, self.camera,
-                           width or self.width, height or self.height, max_depth, instancing=inst, lights=self.lights)
+                           width or self.width, height or self.height, max_depth, instancing=inst, lights=self.lights,
+                           textures=list(self.manager.textures) if self.textures else None,
+                           prim_uv=prim_uv_array(self.prims) if self.textures else None)
+
+
+def prim_uv_array(plist) -> np.ndarray:
+    """abi.PRIM_UV_DTYPE maps of a list of Prim (texture -1 and zeros for a primitive without a map)."""
+    out = np.zeros(len(plist), dtype=PRIM_UV_DTYPE)
+    out["texture"] = -1
+    for k, p in enumerate(plist):
+        if p.texture >= 0 and p.uv is not None:
+            out[k]["texture"] = p.texture
+            out[k]["uv"] = p.uv
+    return out
 
 
 def _prim_array(plist) -> np.ndarray:
@@ -299,7 +370,7 @@ def translate(p: Prim, off) -> Prim:
     if p.kind == MFX_PRIM_SPHERE:
         c = p.pts[0]
         return Prim(p.kind, ((c[0] + off[0], c[1] + off[1], c[2] + off[2]), p.pts[1]), p.material)
-    return Prim(p.kind, tuple((q[0] + off[0], q[1] + off[1], q[2] + off[2]) for q in p.pts), p.material)
+    return Prim(p.kind, tuple((q[0] + off[0], q[1] + off[1], q[2] + off[2]) for q in p.pts), p.material, p.uv, p.texture)
 
 
 def _find_model(ref: str, models: dict):
@@ -324,12 +395,15 @@ RELEASE_FALLBACK_LIGHT = {
 
 
 def InitSceneState(xml_text: str, base_dir: str = ".", manager: MaterialManager | None = None,
-                   light_fallback: str = "debug", all_lights: bool = False) -> SceneState:
+                   light_fallback: str = "debug", all_lights: bool = False, textures: bool = False) -> SceneState:
     """InitSceneState (Scene.fs:265-271): parse XML *text*, version must be 0.1.
 
     all_lights: with True, every <Light type="area"> element becomes a light, in document order
     (SceneState.lights; a context then picks one per path vertex, mfx_create_lights). The default keeps
     the reference's behaviour: the last <Light> element wins (Scene.fs:247).
+
+    textures: with True, the models' `vt` coordinates and map_Kd textures are read and SceneState.arrays()
+    carries them (SceneArrays.textures, prim_uv; mfx_create_textured). The default reads neither.
 
     light_fallback: what a light group whose first primitive is not a Rect does. "debug" (the
     default) raises SceneError, as the reference's Debug build does at `assert(false)`
@@ -376,7 +450,7 @@ def InitSceneState(xml_text: str, base_dir: str = ".", manager: MaterialManager 
                 fname = a.get("value")
             else:
                 raise SceneError(f"unknown model argument {a.get('name')!r}")
-        models[n.get("name")] = load_obj(os.path.join(base_dir, fname), mgr)
+        models[n.get("name")] = load_obj(os.path.join(base_dir, fname), mgr, textures)
     # Light (Scene.fs:179-199)
     def parse_light(ln):
         if ln is None or ln.get("type") != "area":
@@ -451,7 +525,7 @@ def InitSceneState(xml_text: str, base_dir: str = ".", manager: MaterialManager 
                     raise SceneError(f"unknown instances argument {nm!r}")
             key = (ref, mat)
             if key not in templates:
-                templates[key] = [Prim(p.kind, p.pts, mat) for p in _find_model(ref, models)]
+                templates[key] = [Prim(p.kind, p.pts, mat, p.uv, p.texture) for p in _find_model(ref, models)]
             for off in offs:
                 segments.append(("instance", key, off, len(prims), len(templates[key])))
                 prims.extend(translate(p, off) for p in templates[key])
@@ -466,7 +540,7 @@ def InitSceneState(xml_text: str, base_dir: str = ".", manager: MaterialManager 
                 else:
                     raise SceneError(f"unknown shape argument {a.get('name')!r}")
             for p in _find_model(ref, models):
-                prims.append(Prim(p.kind, p.pts, mat))
+                prims.append(Prim(p.kind, p.pts, mat, p.uv, p.texture))
         elif t == "sphere":  # extension
             c, r, mat = (0.0, 0.0, 0.0), 1.0, 0
             for a in s:
@@ -489,16 +563,16 @@ def InitSceneState(xml_text: str, base_dir: str = ".", manager: MaterialManager 
     for p in prims:
         if not (0 <= p.material < len(mgr.materials)):
             raise SceneError(f"material index {p.material} out of range (manager has {len(mgr.materials)})")
-    return SceneState(cam, light, w, h, prims, mgr, segments, templates, lights)
+    return SceneState(cam, light, w, h, prims, mgr, segments, templates, lights, textures)
 
 
 def load_scene_file(path: str, fresh_manager: bool = True, light_fallback: str = "debug", all_lights: bool = False,
-                    **kw) -> SceneArrays:
+                    textures: bool = False, **kw) -> SceneArrays:
     """Convenience: XML file -> SceneArrays, with a fresh MaterialManager (the reference's
     manager is process-global; a fresh one gives the index space of a first load)."""
     with open(path, "r", encoding="utf-8") as f:
         text = f.read()
     mgr = MaterialManager() if fresh_manager else None
     st = InitSceneState(text, base_dir=os.path.dirname(os.path.abspath(path)), manager=mgr,
-                        light_fallback=light_fallback, all_lights=all_lights)
+                        light_fallback=light_fallback, all_lights=all_lights, textures=textures)
     return st.arrays(**kw)

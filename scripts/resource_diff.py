@@ -4,7 +4,10 @@ ones only one log has. Instances are matched by demangled name; a trailing templ
 commit added with the default `false` (k_extend / k_shadow / k_camera LIST) is dropped, and
 k_resolve<false / true> is k_resolve<0 / 1> (bool FRAMES became int MODE).
 
-Usage: python scripts/resource_diff.py OLD.log NEW.log [--markdown]"""
+With --strip-false every trailing `false` template argument is dropped on both sides, which matches instances
+across commits that added parameters defaulting to false (k_shadow ML and TX, k_resolve ML and TX, k_aov TX).
+
+Usage: python scripts/resource_diff.py OLD.log NEW.log [--markdown] [--strip-false]"""
 import re
 import subprocess
 import sys
@@ -14,15 +17,18 @@ NARGS = {"k_extend": 5, "k_shadow": 5, "k_camera": 1}  # template arguments befo
 
 
 def normalise(name):
-    name = name.replace("(WfParams)", "").replace("void ", "")
+    name = name.replace("(WfParams)", "").replace("(AovParams)", "").replace("void ", "")
     m = re.match(r"(\w+)<(.*)>$", name)
     if not m:
         return name
     fn, args = m.group(1), [a.strip() for a in m.group(2).split(",")]
-    if fn == "k_resolve":
+    if fn == "k_resolve" and "--strip-false" not in sys.argv:
         args = [{"false": "0", "true": "1"}.get(a, a) for a in args]
     if fn in NARGS and len(args) == NARGS[fn] + 1 and args[-1] == "false":
         args = args[:-1]
+    if "--strip-false" in sys.argv:  # any number of trailing `false` arguments (parameters added with that default)
+        while args and args[-1] == "false":
+            args = args[:-1]
     return f"{fn}<{', '.join(args)}>"
 
 
