@@ -31,7 +31,7 @@ static int adaptive_alloc(mfx_ctx* c, int64_t ntiles) {
 // MFX_ADAPTIVE_CHECK=1 (debug): a pass's list as the device compacted it — n entries, strictly
 // ascending, every one a tile of the film (list_tile_xy, the function the kernels map it with)
 static int adaptive_check_list(mfx_ctx* c, const int32_t* d_list, int32_t n, int32_t prev_n) {
-    const unsigned tiles_x = (unsigned)(c->host.width + 7) / 8, tiles_y = (unsigned)(c->host.height + 7) / 8;
+    const unsigned tiles_x = (unsigned)(c->scene.host.width + 7) / 8, tiles_y = (unsigned)(c->scene.host.height + 7) / 8;
     if (n < 0 || n > prev_n) return fail(MFX_E_DEVICE, "mfx_sample_adaptive: active tile count out of range");
     std::vector<int32_t> h((size_t)n);
     if (n > 0) HIPCHECK(hipMemcpy(h.data(), d_list, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
@@ -54,7 +54,7 @@ extern "C" int mfx_sample_adaptive(mfx_ctx* c, const mfx_adaptive* a, double* fr
         return fail(MFX_E_STATE, "mfx_sample_adaptive runs the wavefront pipeline (context has MFX_F_MEGAKERNEL)");
     HIPCHECK(hipSetDevice(c->device));
     MFX_TRY(ahead_break(c));  // it moves the sample sequence past held frames
-    const int W = c->host.width, H = c->host.height;
+    const int W = c->scene.host.width, H = c->scene.host.height;
     const int64_t nt64 = (int64_t)((W + 7) / 8) * ((H + 7) / 8);
     const int32_t ntiles = (int32_t)nt64;
     MFX_TRY(adaptive_alloc(c, nt64));
@@ -163,7 +163,7 @@ extern "C" int mfx_sample_adaptive_resume(mfx_ctx* c, const mfx_adaptive_resume*
                                  "mfx_accum_clear or mfx_accum_attach since)");
     if (c->next_sample != ad.B + ad.R)
         return fail(MFX_E_STATE, "mfx_sample_adaptive_resume: samples were drawn since the adaptive result (next_sample moved)");
-    const int W = c->host.width, H = c->host.height;
+    const int W = c->scene.host.width, H = c->scene.host.height;
     const int32_t ntiles = (int32_t)((int64_t)((W + 7) / 8) * ((H + 7) / 8));
     {
         std::vector<int32_t> all((size_t)ntiles);

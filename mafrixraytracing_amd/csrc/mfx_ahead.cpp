@@ -186,7 +186,7 @@ static int ahead_launch(mfx_ctx* c, int xi, int64_t base, int src, double count0
 // whole tile rows (band_tile_row: the even groups' rows and the odd groups' rows, each 8 rows every
 // 2 * band_count * 8) plus the film's partial last tile row if it owns it.
 static int copy_band_rgba(const mfx_ctx* d, uint8_t* dst, const uint8_t* src, hipStream_t st) {
-    const int W = d->host.width, H = d->host.height;
+    const int W = d->scene.host.width, H = d->scene.host.height;
     const size_t row = 4 * (size_t)W;
     if (d->band_count == 1) {
         HIPCHECK(hipMemcpyAsync(dst, src, row * (size_t)H, hipMemcpyDeviceToHost, st));
@@ -319,7 +319,7 @@ extern "C" int mfx_render_rgba8(mfx_ctx* c, int32_t spp, uint8_t* rgba) {
     c->ahead.dfilm_buf = -1;  // d_film moves on
     for (mfx_ctx* d : devs_of(c)) {
         HIPCHECK(hipSetDevice(d->device));
-        HIPCHECK(mfx_launch_film_post(d->d_accum, d->d_film, c->host.width, c->host.height, (double)spp, c->frame_count, 1,
+        HIPCHECK(mfx_launch_film_post(d->d_accum, d->d_film, c->scene.host.width, c->scene.host.height, (double)spp, c->frame_count, 1,
                                       rgba ? d->d_rgba.get() : nullptr, d->stream));
         if (rgba) MFX_TRY(copy_band_rgba(d, rgba, d->d_rgba, d->stream));
     }

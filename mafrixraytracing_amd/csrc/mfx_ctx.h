@@ -1,5 +1,5 @@
 // mfx_ctx.h — the context behind the extern "C" boundary, shared by its translation units
-// (mfx_api.cpp, mfx_trace.cpp, mfx_readback.cpp, mfx_ahead.cpp, mfx_adaptive.cpp,
+// (mfx_api.cpp, mfx_create.cpp, mfx_trace.cpp, mfx_readback.cpp, mfx_ahead.cpp, mfx_adaptive.cpp,
 // mfx_denoise_api.cpp, mfx_query.cpp). Internal: never included from include/.
 // Ownership: a GPU resource is a member (DevBuf, HostBuf, Event, Stream) of the struct of the
 // feature that uses it, and nothing is freed by hand. A feature that allocates at its first call is
@@ -175,8 +175,7 @@ const Rccl* rccl();  // null: it could not be loaded
 // The wavefront pipeline's path-slot pool and ray queues: a frame's paths run in generations of at
 // most `max` paths (mfx_wavefront.h), every iteration one bounce of every live path
 struct WfPool {
-    WfParams params{};        // what holds from trace to trace: the pool's arrays (wf_ensure_pool) and the launch
-                              // shapes (ctx_setup: stack_lds_*, ntop_*, nslot_*, shadow_waves)
+    WfParams params{};        // what holds from trace to trace: the pool's arrays (wf_ensure_pool)
     DevBuf<char> mem;
     int32_t slots = 0;
     size_t bytes = 0;         // bytes of mem
@@ -300,7 +299,7 @@ struct Readback {
 };
 
 // The MFX_* variables that shape a context's launches, as the environment held them when the context was
-// created (read_create_env, mfx_api.cpp: the one place that reads them; unset: no value). What they mean,
+// created (read_create_env, mfx_create.cpp: the one place that reads them; unset: no value). What they mean,
 // their clamps and their defaults are where they are used: scene_upload, scene_shapes, ctx_setup and the
 // two wf_* rules below. A rebuild under mfx_set_camera uses these values, not the environment's.
 struct CreateEnv {
@@ -328,7 +327,7 @@ struct CamCuts {
     DevBuf<MfxCutStats> stats;
     size_t entries = 0;              // allocated
     // what the table was built for: mfx_set_camera changes the camera exactly when cam_epoch moves (on
-    // every device of a list), and every scene_upload takes a new image_gen
+    // every device of a list), and every installed scene_upload takes a new image_gen
     bool valid = false;
     MfxCamera cam{};
     uint64_t image_gen = 0;
@@ -340,7 +339,8 @@ struct CamCuts {
 };
 
 // Albedo textures (mfx_create_textured), per device: the tables the textured kernel instances read. They
-// depend on the primitives alone, not on the camera, so an mfx_set_camera rebuild leaves them where they are.
+// depend on the primitives alone, not on the camera, so they are no part of SceneImages: an mfx_set_camera
+// rebuild leaves them where they are.
 struct Textures {
     MfxTexHost host;                 // descriptors, UV table, texture per world primitive
     DevBuf<double> d_uvrec;
@@ -349,6 +349,47 @@ struct Textures {
     DevBuf<uint32_t> d_texels;       // every texture's texels, one after the other
     const mfx_texture* src = nullptr;  // the caller's textures: set while creation uploads them, null afterwards
     MfxTexTables tables() const { return host.on ? MfxTexTables{d_uvrec, d_ptex, d_desc, d_texels} : MfxTexTables{}; }
+};
+
+// What scene_shapes chooses for k_extend (ext) and k_shadow (shd): wf_trace copies it into a trace's WfParams
+struct LaunchShapes {
+    int stack_lds_ext = 0, stack_lds_shd = 0;  // traversal stack entries per lane in LDS; the rest in d_spill
+    int ntop_ext = 0, ntop_shd = 0;            // top BVH nodes in LDS
+    int nslot_ext = 0, nslot_shd = 0;          // slots in LDS (all of a small scene's, or 0)
+    int shadow_waves = 0;                      // k_shadow instance: 3 or 4 waves per SIMD
+};
+
+// Everything a device holds that the host scene determines: the scene's images in HBM (scene_upload) and the
+// launch shapes and buffers sized by it (scene_shapes; both mfx_create.cpp). Creation fills the context's own;
+// an mfx_set_camera rebuild fills fresh ones for every device and moves them in once all have succeeded, so
+// whatever the two functions write belongs here and nowhere else.
+struct SceneImages {
+    MfxHostScene host;
+    DevBuf<MfxNode> d_nodes;
+    DevBuf<MfxSlot> d_slots;
+    DevBuf<MfxNodeH> d_nodes_h;  // MFX_NODE_F16 builds: the FP16 copy of d_nodes (per-lane kernels)
+    DevBuf<int32_t> d_slot_ref;
+    DevBuf<uint8_t> d_ref_blob;
+    DevBuf<MfxShade> d_shade;
+    DevBuf<MfxInstance> d_inst;  // two-level scenes only
+    DevBuf<double> d_albedo;     // [nmat][3]
+    DevBuf<MfxLight> d_light;    // the light (k_shadow reads it into LDS)
+    DevBuf<MfxLight> d_lights;   // several lights: the table k_shadow<ML> gathers from (null with one light)
+    DevBuf<MfxCamera> d_cam;     // the camera (k_camera reads it into LDS)
+    DevBuf<const void*> d_refs;  // {d_slot_ref, d_ref_blob} (k_shadow reads them into LDS)
+    int stack_size = 1;          // the traversal stack bound
+    // launch shapes (scene_shapes)
+    LaunchShapes shapes;
+    int grid = 0;
+    int wf_ext_grid = 0, wf_shd_grid = 0;
+    int wf_cam_grid = 0;  // > 0: camera rays as packets (k_camera; MFX_CAMERA_PACKETS=0 turns it off)
+    int mega_waves = 1;   // megakernel instance: 4 (128-VGPR budget) or 1 (mfx_kernels.hip)
+    DevBuf<int32_t> d_spill;     // deep traversal-stack entries [spill_deep][spill_lanes]
+    int spill_deep = 0, spill_lanes = 0;
+    DevBuf<double> d_vscratch;   // megakernel: per-lane vertex records [max_depth + 1][6][grid * 256]
+    // several lights (mfx_create_lights, N >= 2): the ML instances of k_shadow and k_resolve, the wavefront
+    // pipeline for every trace, a light-index plane in the pool
+    bool multi_light() const { return host.lights.size() >= 2; }
 };
 
 // Multi-device (primary context only)
@@ -371,14 +412,7 @@ struct Multi {
 struct __attribute__((visibility("hidden"))) mfx_ctx {
     int device = 0;
     mfxh::Stream stream;
-    MfxHostScene host;
-    mfxh::DevBuf<MfxNode> d_nodes;
-    mfxh::DevBuf<MfxSlot> d_slots;
-    mfxh::DevBuf<MfxNodeH> d_nodes_h;  // MFX_NODE_F16 builds: the FP16 copy of d_nodes (per-lane kernels)
-    mfxh::DevBuf<int32_t> d_slot_ref;
-    mfxh::DevBuf<uint8_t> d_ref_blob;
-    mfxh::DevBuf<MfxShade> d_shade;
-    mfxh::DevBuf<MfxInstance> d_inst;  // two-level scenes only
+    mfxh::SceneImages scene;   // the scene in HBM and the launch shapes it determines
     double* d_accum = nullptr;         // [3][npix] the active accumulator: d_accum_own, or the caller's
                                        // (mfx_accum_attach; never owned)
     mfxh::DevBuf<double> d_accum_own;
@@ -401,11 +435,9 @@ struct __attribute__((visibility("hidden"))) mfx_ctx {
     double frame_count = 0.0;
     uint64_t cam_epoch = 0;    // 0 after create, +1 per mfx_set_camera that changed the camera (primary)
     int64_t cam_rebuilds = 0;  // of which had to build the images again
-    uint64_t image_gen = 0;    // +1 per scene_upload on this device (a new node image)
+    uint64_t image_gen = 0;    // +1 per SceneImages installed on this device (a new node image)
     mfxh::CamCuts cuts;
     mfxh::KeptScene kept;      // (primary)
-    int grid = 0;
-    int stack_size = 1;
     int64_t npix = 0;
     mfxh::Event ev0, ev1;
     bool ev_valid = false;
@@ -415,21 +447,9 @@ struct __attribute__((visibility("hidden"))) mfx_ctx {
     int generations = 0;
     bool mega_last = false;
     bool cam_last = false;  // the last wavefront trace ran its camera rays as packets (k_camera)
-    // launch shapes (ctx_setup)
-    int wf_ext_grid = 0, wf_shd_grid = 0;
-    int wf_cam_grid = 0;  // > 0: camera rays as packets (k_camera; MFX_CAMERA_PACKETS=0 turns it off)
     int wf_chunk = 256;  // slots per chunk fetch (a multiple of 64; r04j: 256 against 1024, C2 64 spp +1 %, 8 spp +6 %)
     bool wf_shd_half = true;  // k_shadow takes half chunks in place on frames of at most 2^25 paths (MFX_SHD_HALF)
     int mega_chunk = 0;   // megakernel: paths a wave takes per atomic (0: by the call's size)
-    int mega_waves = 1;   // megakernel instance: 4 (128-VGPR budget) or 1 (mfx_kernels.hip)
-    mfxh::DevBuf<int32_t> d_spill;      // deep traversal-stack entries [spill_deep][spill_lanes]
-    int spill_deep = 0, spill_lanes = 0;
-    mfxh::DevBuf<double> d_vscratch;   // megakernel: per-lane vertex records [max_depth + 1][6][grid * 256]
-    mfxh::DevBuf<double> d_albedo;      // [nmat][3]
-    mfxh::DevBuf<MfxLight> d_light;     // the light (k_shadow reads it into LDS)
-    mfxh::DevBuf<MfxLight> d_lights;    // several lights: the table k_shadow<ML> gathers from (null with one light)
-    mfxh::DevBuf<MfxCamera> d_cam;      // the camera (k_camera reads it into LDS)
-    mfxh::DevBuf<const void*> d_refs;   // {d_slot_ref, d_ref_blob} (k_shadow reads them into LDS)
     bool rep_valid = false;          // the last call was served from held frames, or was mfx_sample_adaptive
                                      // (several traces): its stats are rep_*
     double rep_counts[16] = {0};
@@ -463,13 +483,12 @@ inline std::vector<mfx_ctx*> devs_of(mfx_ctx* c) {
 
 // tile rows of the film in a device's band (its image partition)
 inline int band_rows(const mfx_ctx* d) {
-    const int tr = (d->host.height + 7) / 8;
+    const int tr = (d->scene.host.height + 7) / 8;
     return band_row_count(d->band_index, d->band_count, tr);
 }
 
-// several lights (mfx_create_lights, N >= 2): the ML instances of k_shadow and k_resolve, the wavefront
-// pipeline for every trace, a light-index plane in the pool
-inline bool wf_multi_light(const mfx_ctx* c) { return c->host.lights.size() >= 2; }
+// several lights (SceneImages::multi_light)
+inline bool wf_multi_light(const mfx_ctx* c) { return c->scene.multi_light(); }
 
 // albedo textures (mfx_create_textured with a textured primitive): the TX instances of k_shadow, k_resolve
 // and k_aov, the wavefront pipeline for every trace, a texel-id plane in the pool
@@ -477,7 +496,7 @@ inline bool wf_textured(const mfx_ctx* c) { return c->tex.host.on; }
 
 // bytes of one path slot of the wavefront pool (ray queues included)
 inline size_t pool_slot_bytes(const mfx_ctx* c) {
-    const int nv = c->host.max_depth + 1;  // vertices per path
+    const int nv = c->scene.host.max_depth + 1;  // vertices per path
     return WF_DOUBLES_PER_SLOT(nv) * 8 + WF_WORDS_PER_SLOT(nv) * 4 + (wf_multi_light(c) ? WF_LIGHT_BYTES_PER_SLOT(nv) : 0) +
            (wf_textured(c) ? WF_TEXEL_BYTES_PER_SLOT(nv) : 0);
 }
@@ -485,25 +504,34 @@ inline size_t pool_slot_bytes(const mfx_ctx* c) {
 // the scene images' device pointers of a kernel parameter struct (WfParams, TraceParams, AovParams, QueryParams)
 template <typename P>
 void fill_scene_ptrs(const mfx_ctx* c, P& p) {
-    p.nodes = c->d_nodes;
-    p.slots = c->d_slots;
-    p.slot_ref = c->d_slot_ref;
-    p.ref_blob = c->d_ref_blob;
-    p.shade = c->d_shade;
-    p.inst = c->d_inst;
-    p.tslack = c->host.tslack;
+    const SceneImages& s = c->scene;
+    p.nodes = s.d_nodes;
+    p.slots = s.d_slots;
+    p.slot_ref = s.d_slot_ref;
+    p.ref_blob = s.d_ref_blob;
+    p.shade = s.d_shade;
+    p.inst = s.d_inst;
+    p.tslack = s.host.tslack;
 }
 
 // a gray light (bitwise equal intensities): k_shadow records a lit vertex's direct term itself
 inline bool wf_gray_light(const mfx_ctx* c) {
-    const double* I = c->host.light.color;
+    const double* I = c->scene.host.light.color;
     return std::memcmp(&I[0], &I[1], sizeof(double)) == 0 && std::memcmp(&I[0], &I[2], sizeof(double)) == 0 &&
            !c->env.no_gray_light && !wf_multi_light(c);  // (several lights: the term depends on the picked one)
 }
 // in place, a HIT state word carries the path's lit mask (WfParams.lit_in_hit)
 inline bool wf_lit_in_hit(const mfx_ctx* c) {
-    return c->host.max_depth <= 3 && c->host.shade.size() <= ((size_t)1 << 25) && !c->env.no_lit_in_hit;
+    const MfxHostScene& h = c->scene.host;
+    return h.max_depth <= 3 && h.shade.size() <= ((size_t)1 << 25) && !c->env.no_lit_in_hit;
 }
+
+// mfx_create.cpp
+// the LDS shape of k_extend or (shd) k_shadow over the scene images `s` of a context (textured: wf_textured) with
+// nlds stack entries per lane in LDS (the rest spilled), and ntop top nodes and nslot slots beside them
+WfLdsShape wf_lds_shape(const SceneImages& s, bool textured, bool shd, int nlds, int ntop = 0, int nslot = 0);
+bool flatten_instances(const mfx_scene_desc* scene, const mfx_instance* instances, int32_t ninstances, int32_t flags,
+                       size_t device_free = 0);
 
 // MFX_OK, or MFX_E_STATE for a call that needs one device and the whole film and sample set
 int whole_film_single_device(const mfx_ctx* c, const char* who);

@@ -59,13 +59,13 @@ extern "C" int mfx_aov(mfx_ctx* c, int32_t spp, int64_t sample_base, double* out
     AovParams P;
     std::memset(&P, 0, sizeof(P));
     fill_scene_ptrs(c, P);
-    P.cam = c->host.camera;
+    P.cam = c->scene.host.camera;
     P.seed = c->seed;
     P.sample_base = sample_base;
     P.spp = spp;
-    P.width = c->host.width;
-    P.height = c->host.height;
-    P.stack_size = c->stack_size;
+    P.width = c->scene.host.width;
+    P.height = c->scene.host.height;
+    P.stack_size = c->scene.stack_size;
     P.feat = dn.feat;
     P.out = out ? dn.feat_out.get() : nullptr;
     P.tx = c->tex.tables();  // albedo textures: k_aov's TX instances (all null without)
@@ -107,7 +107,7 @@ extern "C" int mfx_denoise(mfx_ctx* c, const mfx_denoise_cfg* a, const double* c
     HIPCHECK(hipSetDevice(c->device));
     for (int k = 0; k < 2; ++k) MFX_TRY(dn_alloc(dn.buf[k], 3 * (size_t)c->npix, "mfx_denoise"));
     MFX_TRY(dn_events(c));
-    const int W = c->host.width, H = c->host.height;
+    const int W = c->scene.host.width, H = c->scene.host.height;
     if (a->source == MFX_DN_SRC_HOST)  // staged through the x-major frame buffer, before the timed part
         HIPCHECK(hipMemcpyAsync(c->d_frame, color_in, 4 * sizeof(double) * (size_t)c->npix, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipEventRecord(dn.ev0, c->stream));
@@ -178,7 +178,7 @@ extern "C" int mfx_denoise_var(mfx_ctx* c, const mfx_denoise_var_cfg* a, const d
         MFX_TRY(dn_alloc(dn.var[k], (size_t)c->npix, "mfx_denoise_var"));
     }
     MFX_TRY(dn_events(c));
-    const int W = c->host.width, H = c->host.height;
+    const int W = c->scene.host.width, H = c->scene.host.height;
     if (host) {  // staged before the timed part: the frame through the x-major frame buffer, the variance as the plane it is
         HIPCHECK(hipMemcpyAsync(c->d_frame, color_in, 4 * sizeof(double) * (size_t)c->npix, hipMemcpyHostToDevice, c->stream));
         HIPCHECK(hipMemcpyAsync(dn.var[0], variance_in, sizeof(double) * (size_t)c->npix, hipMemcpyHostToDevice, c->stream));
@@ -259,7 +259,7 @@ extern "C" int mfx_temporal(mfx_ctx* c, const mfx_temporal_cfg* a, const double*
         return fail(MFX_E_NOMEM, "mfx_temporal: its device buffers could not be allocated");
     }
     MFX_TRY(dn_events(c));
-    const int W = c->host.width, H = c->host.height;
+    const int W = c->scene.host.width, H = c->scene.host.height;
     if (host) {  // staged before the timed part, as mfx_denoise_var's
         HIPCHECK(hipMemcpyAsync(c->d_frame, color_in, 4 * sizeof(double) * npix, hipMemcpyHostToDevice, c->stream));
         HIPCHECK(hipMemcpyAsync(dn.var[0], variance_in, sizeof(double) * npix, hipMemcpyHostToDevice, c->stream));
@@ -281,8 +281,8 @@ extern "C" int mfx_temporal(mfx_ctx* c, const mfx_temporal_cfg* a, const double*
     P.hist = have ? tp.hist[tp.cur].get() : nullptr;
     P.hist_out = tp.hist[dst];
     P.accepted = tp.accepted;
-    P.cam = c->host.camera;
-    P.hcam = have ? tp.cam : c->host.camera;
+    P.cam = c->scene.host.camera;
+    P.hcam = have ? tp.cam : c->scene.host.camera;
     P.width = W;
     P.height = H;
     P.tol_depth2 = a->tol_depth * a->tol_depth;
@@ -291,7 +291,7 @@ extern "C" int mfx_temporal(mfx_ctx* c, const mfx_temporal_cfg* a, const double*
     HIPCHECK(mfx_launch_temporal(P, c->stream));
     // the history is now the merged result in the current view (the buffers swap by index: no copy)
     tp.cur = dst;
-    tp.cam = c->host.camera;
+    tp.cam = c->scene.host.camera;
     tp.epoch = c->cam_epoch;
     const double* hist = tp.hist[dst];
     if (out || rgba)

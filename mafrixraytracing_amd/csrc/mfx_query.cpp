@@ -40,7 +40,7 @@ static int run_query(mfx_ctx* c, int64_t n, const double* rays, double tmin, dou
     Q.n = n;
     Q.tmin = tmin;
     Q.tmax = tmax;
-    Q.stack_size = c->stack_size;
+    Q.stack_size = c->scene.stack_size;
     QCHECK("query: ", mfx_launch_query(Q, shadow, c->stream));
     QCHECK("query: ", hipStreamSynchronize(c->stream));
     if (shadow) {
@@ -69,10 +69,10 @@ int mfx_ref_leaves(mfx_ctx* c, int32_t* indices_out, int32_t* leaf_first_out, in
                    int32_t* nleaves_out) {
     if (!c || !indices_out || !leaf_first_out || !leaf_count_out || !nleaves_out)
         return fail(MFX_E_INVALID, "null argument");
-    std::copy(c->host.ref_indices.begin(), c->host.ref_indices.end(), indices_out);
-    std::copy(c->host.leaf_first.begin(), c->host.leaf_first.end(), leaf_first_out);
-    std::copy(c->host.leaf_count.begin(), c->host.leaf_count.end(), leaf_count_out);
-    *nleaves_out = (int32_t)c->host.leaf_first.size();
+    std::copy(c->scene.host.ref_indices.begin(), c->scene.host.ref_indices.end(), indices_out);
+    std::copy(c->scene.host.leaf_first.begin(), c->scene.host.leaf_first.end(), leaf_first_out);
+    std::copy(c->scene.host.leaf_count.begin(), c->scene.host.leaf_count.end(), leaf_count_out);
+    *nleaves_out = (int32_t)c->scene.host.leaf_first.size();
     return MFX_OK;
 }
 

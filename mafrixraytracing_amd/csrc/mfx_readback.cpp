@@ -160,7 +160,7 @@ static int sample_banded(mfx_ctx* c, int32_t spp, double* frame) {
     // the unbanded path 33.7 (a lone process: 8 x 1 32.1, unbanded 32.7, r06b)
     int nb = 4;
     if (const char* e = getenv("MFX_SAMPLE_BANDS")) nb = std::min(kStageChunks, atoi(e));
-    const int W = c->host.width, H = c->host.height;
+    const int W = c->scene.host.width, H = c->scene.host.height;
     nb = std::min(nb, (W + 7) / 8);
     // the means staged as interleaved RGB (MFX_SAMPLE_RGBA=1: the whole RGBA frame, A/B knob): the
     // host writes alpha while it copies, so the DMA carries 49.8 MB of C2's 66 MB frame

@@ -12,7 +12,7 @@ static int wf_ensure_pool(mfx_ctx* c, int32_t pool, bool queues) {
     WfPool& wp = c->pool;
     if (pool <= wp.slots && (!queues || wp.queues)) return MFX_OK;
     const size_t P = (size_t)pool;
-    const int nv = c->host.max_depth + 1;  // vertices per path
+    const int nv = c->scene.host.max_depth + 1;  // vertices per path
     const size_t per_slot = pool_slot_bytes(c) - (queues ? 0 : WF_QUEUE_BYTES_PER_SLOT);
     const size_t bytes = P * per_slot + 64 * 256;
     // leave the runtime its headroom (kernel scratch is allocated at launch, and the runtime gives
@@ -124,8 +124,8 @@ static void wf_queue_views(mfx_ctx* c, WfParams& P, int d) {
 template <typename P>
 static void fill_trace_params(mfx_ctx* c, P& p, int64_t sample_base) {
     fill_scene_ptrs(c, p);
-    p.light = c->host.light;
-    p.cam = c->host.camera;
+    p.light = c->scene.host.light;
+    p.cam = c->scene.host.camera;
     p.accum = c->d_accum;
     c->adp.accum_valid = false;  // a trace adds to it (mfx_sample_adaptive sets the flag after its own)
     p.seed = c->seed;
@@ -135,33 +135,41 @@ static void fill_trace_params(mfx_ctx* c, P& p, int64_t sample_base) {
     p.band_index = c->band_index;
     p.band_count = c->band_count;
     p.band_rows = band_rows(c);
-    p.width = c->host.width;
-    p.height = c->host.height;
-    p.max_depth = c->host.max_depth;
-    p.stack_size = c->stack_size;
+    p.width = c->scene.host.width;
+    p.height = c->scene.host.height;
+    p.max_depth = c->scene.host.max_depth;
+    p.stack_size = c->scene.stack_size;
 }
 
 static void fill_scene_params(mfx_ctx* c, WfParams& P) {
 #if MFX_NODE_F16
-    P.nodes_h = c->d_nodes_h;
+    P.nodes_h = c->scene.d_nodes_h;
 #endif
-    P.light_dev = c->d_light;
+    P.light_dev = c->scene.d_light;
     // several lights: the ML instances' table (set: mfx_wf_iteration and mfx_wf_resolve launch them)
-    P.lights = wf_multi_light(c) ? c->d_lights.get() : nullptr;
-    P.nlights = wf_multi_light(c) ? (int32_t)c->host.lights.size() : 0;
+    P.lights = wf_multi_light(c) ? c->scene.d_lights.get() : nullptr;
+    P.nlights = wf_multi_light(c) ? (int32_t)c->scene.host.lights.size() : 0;
     // albedo textures: the TX instances' tables (vtex set, by wf_ensure_pool: the launchers run them)
     P.tx = c->tex.tables();
-    P.cam_dev = c->d_cam;
-    P.refs_dev = c->d_refs;
+    P.cam_dev = c->scene.d_cam;
+    P.refs_dev = c->scene.d_refs;
     P.gray_light = wf_gray_light(c);
     P.lit_in_hit = wf_lit_in_hit(c);
-    P.albedo = c->d_albedo;
-    P.nmat = (int32_t)(c->host.albedo.size() / 3);
+    P.albedo = c->scene.d_albedo;
+    P.nmat = (int32_t)(c->scene.host.albedo.size() / 3);
+    const LaunchShapes& L = c->scene.shapes;
+    P.stack_lds_ext = L.stack_lds_ext;
+    P.stack_lds_shd = L.stack_lds_shd;
+    P.ntop_ext = L.ntop_ext;
+    P.ntop_shd = L.ntop_shd;
+    P.nslot_ext = L.nslot_ext;
+    P.nslot_shd = L.nslot_shd;
+    P.shadow_waves = L.shadow_waves;
 }
 
 // ---- camera cuts (mfx_camera_cuts.h): the per-device table and when it is built ----
 // a context whose camera rays run k_camera with cuts on (flat scenes, MFX_CAMERA_PACKETS and MFX_CAMERA_CUTS not 0)
-bool mfxh::cuts_apply(const mfx_ctx* c) { return c->host.inst.empty() && c->wf_cam_grid > 0 && c->cuts.on; }
+bool mfxh::cuts_apply(const mfx_ctx* c) { return c->scene.host.inst.empty() && c->scene.wf_cam_grid > 0 && c->cuts.on; }
 
 // The device's table for its current camera and node image, built on its stream if it is another's
 // (context creation, a camera change, a scene rebuild): every later launch on the stream sees it.
@@ -171,12 +179,12 @@ bool mfxh::cuts_apply(const mfx_ctx* c) { return c->host.inst.empty() && c->wf_c
 // with the trace that crosses the threshold and keeps it.
 int mfxh::cuts_ensure(mfx_ctx* c, int64_t ns) {
     CamCuts& K = c->cuts;
-    const bool same = K.valid && K.image_gen == c->image_gen && std::memcmp(&K.cam, &c->host.camera, sizeof(MfxCamera)) == 0;
+    const bool same = K.valid && K.image_gen == c->image_gen && std::memcmp(&K.cam, &c->scene.host.camera, sizeof(MfxCamera)) == 0;
     if (!same) K.cam_samples = 0;
     K.cam_samples = ns > INT64_MAX - K.cam_samples ? INT64_MAX : K.cam_samples + std::max<int64_t>(ns, 0);
     const bool cull = K.cam_samples >= K.cull_min_samples;
     if (same && (K.culled || !cull)) return MFX_OK;
-    const size_t tiles = (size_t)((c->host.width + 7) / 8) * (size_t)((c->host.height + 7) / 8);
+    const size_t tiles = (size_t)((c->scene.host.width + 7) / 8) * (size_t)((c->scene.host.height + 7) / 8);
     if (K.entries < tiles * K.cap) {
         HIP_TRY(K.table.alloc(tiles * K.cap), _e == hipErrorOutOfMemory ? MFX_E_NOMEM : MFX_E_DEVICE, "camera cuts: ");
         K.entries = tiles * K.cap;
@@ -188,9 +196,9 @@ int mfxh::cuts_ensure(mfx_ctx* c, int64_t ns) {
     }
     K.valid = false;
     HIPCHECK(hipEventRecord(K.e0, c->stream));
-    HIPCHECK(mfx_build_cut_table(c->d_nodes, cull ? (const MfxSlot*)c->d_slots : nullptr, c->d_cam, c->host.width, c->host.height, K.cap, K.table, K.stats, c->stream));
+    HIPCHECK(mfx_build_cut_table(c->scene.d_nodes, cull ? (const MfxSlot*)c->scene.d_slots : nullptr, c->scene.d_cam, c->scene.host.width, c->scene.host.height, K.cap, K.table, K.stats, c->stream));
     HIPCHECK(hipEventRecord(K.e1, c->stream));
-    K.cam = c->host.camera;
+    K.cam = c->scene.host.camera;
     K.image_gen = c->image_gen;
     K.culled = cull;
     K.valid = true;
@@ -225,7 +233,7 @@ int mfxh::wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, TraceMode mode) 
     ResolveSplit* split = std::holds_alternative<ResolveSplit*>(mode) ? std::get<ResolveSplit*>(mode) : nullptr;
     const TileList* list = std::get_if<TileList>(&mode);
     WfPool& wp = c->pool;
-    const int W = c->host.width, H = c->host.height;
+    const int W = c->scene.host.width, H = c->scene.host.height;
     const int brows = band_rows(c);
     if (list && (list->ntiles < 1 || !list->tiles || !list->mom)) return fail(MFX_E_INVALID, "wf_trace: bad tile list");
     // the device's band of the film, or the listed tiles
@@ -268,8 +276,8 @@ int mfxh::wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, TraceMode mode) 
     const bool own_events = fm == nullptr;
     // per-iteration stage events (mfx_trace_timing's split): off with MFX_ITER_EVENTS=0 (A/B of their cost)
     const bool iter_events = own_events && c->iter_events;
-    P.ninst_lds = std::min<int>((int)c->host.inst.size(), WF_INST_LDS);
-    P.spill = c->d_spill;
+    P.ninst_lds = std::min<int>((int)c->scene.host.inst.size(), WF_INST_LDS);
+    P.spill = c->scene.d_spill;
     // slots per chunk fetch: 256 at every frame size. Round 3 used 1024 (512 for frames of at most
     // 2^25 paths); with the shard counters on lines of their own and the closed-shard mask the chunk
     // fetches no longer convoy, so small chunks cut the launches' tails (r04j: C2 fixed cost per
@@ -287,7 +295,7 @@ int mfxh::wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, TraceMode mode) 
     P.tile_n = list ? list->tile_n : nullptr;
     P.list_max = list ? list->list_max : 0;
     const bool stats = (c->flags & MFX_F_COUNT_STATS) != 0;
-    P.cam_grid = c->host.inst.empty() ? c->wf_cam_grid : 0;
+    P.cam_grid = c->scene.host.inst.empty() ? c->scene.wf_cam_grid : 0;
     if (own_events) c->cam_last = P.cam_grid > 0;
     // camera cuts: a table that is already this camera's costs nothing; a trace of fewer than min_samples
     // samples does not pay for a build and walks from the root (the break-even)
@@ -295,7 +303,7 @@ int mfxh::wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, TraceMode mode) 
     P.cut_cap = 0;
     if (P.cam_grid > 0 && cuts_apply(c)) {
         const CamCuts& K = c->cuts;
-        const bool have = K.valid && K.image_gen == c->image_gen && std::memcmp(&K.cam, &c->host.camera, sizeof(MfxCamera)) == 0;
+        const bool have = K.valid && K.image_gen == c->image_gen && std::memcmp(&K.cam, &c->scene.host.camera, sizeof(MfxCamera)) == 0;
         if (have || ns >= K.min_samples) {
             MFX_TRY(cuts_ensure(c, ns));
             P.cuts = K.table;
@@ -346,13 +354,13 @@ int mfxh::wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, TraceMode mode) 
             // the same halving costs 1.5 %, so frames of more than 2^25 paths keep whole chunks)
             P.chunk_shd = (c->wf_shd_half && !P.qcount && total <= ((int64_t)1 << 25)) ? std::max(64, P.chunk / 2) : P.chunk;
             if (!iter_events) {
-                HIPCHECK(mfx_wf_iteration(P, c->wf_ext_grid, c->wf_shd_grid, stats, c->stream, nullptr));
+                HIPCHECK(mfx_wf_iteration(P, c->scene.wf_ext_grid, c->scene.wf_shd_grid, stats, c->stream, nullptr));
                 continue;
             }
             const Event* ev = c->it_ev.data() + 3 * it;
             hipEvent_t mid = ev[1];  // recorded between k_extend and k_shadow
             HIPCHECK(hipEventRecord(ev[0], c->stream));
-            HIPCHECK(mfx_wf_iteration(P, c->wf_ext_grid, c->wf_shd_grid, stats, c->stream, &mid));
+            HIPCHECK(mfx_wf_iteration(P, c->scene.wf_ext_grid, c->scene.wf_shd_grid, stats, c->stream, &mid));
             HIPCHECK(hipEventRecord(ev[2], c->stream));
             if (c->diag_iter) {
                 HIPCHECK(hipStreamSynchronize(c->stream));
@@ -429,20 +437,20 @@ int mfxh::dev_trace_accumulate(mfx_ctx* c, int32_t spp, int64_t sample_base, Res
     P.work_counter = c->d_work;
     P.counters = c->d_counters;
     P.nsamples = ns;
-    P.vscratch = c->d_vscratch;
-    P.waves = c->mega_waves;
+    P.vscratch = c->scene.d_vscratch;
+    P.waves = c->scene.mega_waves;
     // paths per chunk: 256, halved while fewer than 16 chunks per wave remain (a 1-spp frame:
     // 64, one path per lane per fetch; r02g/r02i A/B at 1 spp: 256 -> 64 is +21 %)
     if (c->mega_chunk > 0) {
         P.chunk = c->mega_chunk;
     } else {
-        const int64_t total = (int64_t)((c->host.width + 7) / 8) * band_rows(c) * 64 * ns;
+        const int64_t total = (int64_t)((c->scene.host.width + 7) / 8) * band_rows(c) * 64 * ns;
         int64_t ch = 256;
-        while (ch > 64 && total / ch < 16 * (int64_t)c->grid * 4) ch /= 2;
+        while (ch > 64 && total / ch < 16 * (int64_t)c->scene.grid * 4) ch /= 2;
         P.chunk = (int)ch;
     }
     HIPCHECK(hipEventRecord(c->ev0, c->stream));
-    HIPCHECK(mfx_launch_trace(P, (c->flags & MFX_F_COUNT_STATS) != 0, c->grid, c->stream));
+    HIPCHECK(mfx_launch_trace(P, (c->flags & MFX_F_COUNT_STATS) != 0, c->scene.grid, c->stream));
     HIPCHECK(hipEventRecord(c->ev1, c->stream));
     c->ev_valid = true;
     HIPCHECK(mfx_launch_counters_add(c->d_counters_total, c->d_counters, WF_NCTR * WF_SHARDS, c->stream));
@@ -562,7 +570,7 @@ void mfxh::note_live(mfx_ctx* c, const unsigned long long* h) {
     }
     if (paths <= 0 || it[1] <= 0) return;  // no wavefront trace (megakernel), or no path went on
     int from = -1;
-    for (int d = 0; d + 1 < WF_ITER_CTRS && d < c->host.max_depth; ++d)
+    for (int d = 0; d + 1 < WF_ITER_CTRS && d < c->scene.host.max_depth; ++d)
         if (it[d + 1] / paths < WF_QUEUE_LIVE) {
             from = d;
             break;

@@ -92,6 +92,22 @@ def test_in_place_on_a_repeated_device_list(gpu, oracle):
         assert np.array_equal(m.film_mean(), f.film_mean())
 
 
+def test_rebuild_on_a_repeated_device_list(gpu, oracle):
+    """A rebuild gives every device of a list its new images: both devices of the list trace with them."""
+    a = scene("cornell", W, H)
+    cam = moved(a.camera, **MOVES["cornell"][1])
+    b = with_camera(a, cam)
+    with _ctx(a, devices=[0, 0]) as m, _ctx(b) as f:
+        m.set_camera(cam)
+        assert (m.camera_info()["epoch"], m.camera_info()["rebuilds"]) == (1, 1)
+        assert m.build_info()["digest"] == f.build_info()["digest"]
+        img = m.sample(3)
+        assert np.array_equal(img, oracle.OracleScene(b).sample(3, SEED))
+        assert np.array_equal(img, f.sample(3))
+        assert np.array_equal(m.render_rgba8(1), f.render_rgba8(1))
+        assert np.array_equal(m.film_mean(), f.film_mean())
+
+
 @pytest.mark.parametrize("name", list(MOVES))
 def test_rebuild(gpu, oracle, name):
     a = scene(name, W, H)
