@@ -360,6 +360,65 @@ int mfx_camera_info(mfx_ctx* ctx, double out[16]);
  * a zero direction with derived == 0.                                                           */
 int mfx_set_camera(mfx_ctx* ctx, const mfx_pinhole* cam);
 
+/* ---- the sky (ABI 6, additive; an extension: in the reference a ray that leaves the scene returns black,
+ * TraceRay's `else Color()`, Integrators.fs:137) ---------------------------------------------------------
+ * The environment is a square octahedral map of size x size texels, 1 <= size <= MFX_MAX_ENV_SIZE (at most
+ * 2^24 texels: a texel id fits in 24 bits). A texel is three floats, linear RGB radiance, widened to double
+ * exactly: E[c] = (double)rgb[3*id + c]. size == 1 is a constant sky. No trigonometry: the texel of a
+ * direction is stated in + - * / abs floor and comparisons, so a host statement
+ * (mafrixraytracing_amd/environment.py) and the kernels agree bit for bit, as for mfx_texel_index.
+ *
+ * The texel of a direction. d is the ray's unit direction as the kernels hold it; all FP64, one rounding per
+ * operation, no contraction; +y is the pole (the camera's up):
+ *  1. s = (|dx| + |dy|) + |dz|; px = dx / s; pz = dz / s;
+ *  2. if dy >= 0.0 (which includes -0.0): a = px, b = pz;
+ *  3. otherwise a = (1.0 - |pz|) * sg(px), b = (1.0 - |px|) * sg(pz), with sg(x) = x >= 0.0 ? 1.0 : -1.0;
+ *  4. u = a * 0.5 + 0.5; v = b * 0.5 + 0.5;
+ *  5. xi = (int)floor(u * (double)size) clamped into [0, size-1]; yi likewise from v;
+ *  6. id = yi * size + xi.
+ *
+ * The estimator is the reference's with one change: TraceRay(ray, depth) for depth >= 0 returns E(ray.direction)
+ * on a miss instead of Color(); a hit is handled as ever. The depth -1 query stays untraced and black. So the
+ * rays traced, the iterations and every ray counter are those of the same context without an environment. A
+ * path whose ray missed after nv vertices folds f = E, then f <- (a_v + f) * c_v for v = nv-1 .. 0, over all
+ * nv vertices, the unlit ones included; a camera ray that misses (nv = 0) contributes E itself, so the
+ * background shows; a path that ends by depth alone is as without. Shadow rays ignore the sky, and the sky is
+ * not light-sampled: only the hemisphere-sampled extension ray sees it, no draw is added and the RNG stream is
+ * unchanged. A small bright sun in the map will therefore be noisy. Every surface stays Lambertian, so
+ * mfx_temporal's view independence holds, and mfx_aov's first-hit planes do not depend on the sky (a miss
+ * still adds nothing there).                                                                             */
+typedef struct mfx_environment {
+    const float* rgb; /* size * size texels of 3 floats, row yi after row yi-1 */
+    int32_t size;     /* 1 .. MFX_MAX_ENV_SIZE */
+    int32_t reserved;
+} mfx_environment; /* 16 bytes */
+#define MFX_MAX_ENV_SIZE 4096
+
+/* Makes `env` the sky of every later call, on every device of a device list (the texels are copied to each);
+ * env == NULL removes it, and the context is then the one it was before, kernel for kernel: the same
+ * mfx_launch_info, pool bytes and images. It composes with every creation entry point: it touches no BVH,
+ * slot or digest. With an environment the context runs the ENV instances of k_extend, k_camera and k_resolve,
+ * always the wavefront pipeline (one-sample calls included), and its path pool keeps 4 bytes more per slot:
+ * the miss record. Waits for the context's work first, a render-ahead batch traced in the background included.
+ * What it invalidates: what mfx_set_camera invalidates, except the feature buffers (they do not depend on
+ * the sky): frames held by render-ahead are never served afterwards, and an adaptive result is gone
+ * (mfx_sample_adaptive_resume and MFX_DN_SRC_ADAPTIVE return MFX_E_STATE until mfx_sample_adaptive runs
+ * again). What it leaves alone: the film, the accumulator, next_sample, the ray counters, the feature buffers
+ * and the temporal history. An mfx_set_camera rebuild keeps the environment.
+ * MFX_E_INVALID, decided on the host, the message naming the first offender: a size outside
+ * [1, MFX_MAX_ENV_SIZE]; a NULL rgb (both only with a non-NULL env); a texel that is not finite or is
+ * negative. MFX_E_STATE: a context created with MFX_F_MEGAKERNEL or MFX_F_COUNT_STATS (those kernel
+ * instances are built without an environment).                                                            */
+int mfx_set_environment(mfx_ctx* ctx, const mfx_environment* env);
+/* out[0] = size, out[1] = 1 if the environment instances run, out[2] = bytes of texels on the device,
+ * out[3] = bytes per path slot the environment adds to the pool, out[4] / out[5] = resident blocks per CU of
+ * the k_extend / k_resolve instance in use, out[6] = out[7] = 0. All 0 without an environment.            */
+int mfx_environment_info(mfx_ctx* ctx, double out[8]);
+/* Host-only (no device needed): the texel rule, by the code the kernels compile. id_out[k] = the texel of
+ * direction dirs[3k .. 3k+2] in a size x size map. MFX_E_INVALID: a size outside [1, MFX_MAX_ENV_SIZE], a
+ * NULL array with n > 0, n < 0.                                                                           */
+int mfx_env_texel_index(int32_t size, int64_t n, const double* dirs, uint32_t* id_out);
+
 /* ---- the reference's render API --------------------------------------------------------- */
 
 /* == IPixelIntegrator.Sample(spp) (IIntegrator.fs:35-40, Integrators.fs:161-172):

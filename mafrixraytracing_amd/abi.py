@@ -30,6 +30,7 @@ MFX_MAX_DEVICES = 64
 MFX_MAX_LIGHTS = 64
 MFX_MAX_TEXTURES = 4096
 MFX_MAX_TEXTURE_DIM = 16384
+MFX_MAX_ENV_SIZE = 4096
 MFX_DN_SRC_HOST = 0
 MFX_DN_SRC_ACCUM = 1
 MFX_DN_SRC_ADAPTIVE = 2
@@ -90,6 +91,11 @@ class MfxPrimUv(C.Structure):
     _fields_ = [("texture", C.c_int32), ("reserved", C.c_int32), ("uv", (C.c_double * 2) * 3)]
 
 
+class MfxEnvironment(C.Structure):
+    """mfx_environment: size * size texels of three floats (linear RGB radiance), an octahedral map."""
+    _fields_ = [("rgb", C.POINTER(C.c_float)), ("size", C.c_int32), ("reserved", C.c_int32)]
+
+
 class MfxAdaptive(C.Structure):
     """mfx_adaptive: the schedule and threshold of mfx_sample_adaptive."""
     _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("step_spp", C.c_int32), ("reserved", C.c_int32),
@@ -126,6 +132,7 @@ assert C.sizeof(MfxPrim) == 104
 assert C.sizeof(MfxInstance) == 48
 assert C.sizeof(MfxTexture) == 16
 assert C.sizeof(MfxPrimUv) == 56
+assert C.sizeof(MfxEnvironment) == 16
 assert C.sizeof(MfxAdaptive) == 32
 assert C.sizeof(MfxAdaptiveResume) == 32
 assert C.sizeof(MfxDenoiseCfg) == 56
@@ -269,6 +276,31 @@ def texel_index(sizes, texture: int, uv) -> np.ndarray:
     return out[:len(uv)]
 
 
+def environment_struct(env):
+    """An MfxEnvironment over an (S, S, 3) float32 map (a constant sky may be given as its three values), and
+    the array it points into (keep both alive for the call)."""
+    keep = np.ascontiguousarray(env, dtype=np.float32)
+    if keep.shape == (3,):
+        keep = keep.reshape(1, 1, 3)
+    if keep.ndim != 3 or keep.shape[0] != keep.shape[1] or keep.shape[2] != 3:
+        raise ValueError(f"environment: expected an (S, S, 3) float32 array, got shape {keep.shape}")
+    e = MfxEnvironment()
+    e.rgb = keep.ctypes.data_as(C.POINTER(C.c_float))
+    e.size = keep.shape[0]
+    return e, keep
+
+
+def env_texel_index(dirs, size: int) -> np.ndarray:
+    """Host-only: the texel ids of unit directions dirs (n, 3) in a size x size octahedral map
+    (mfx_env_texel_index; environment.texel_index is the Python statement of the same)."""
+    lib = load_library()
+    d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+    out = np.zeros(max(1, len(d)), dtype=np.uint32)
+    check(lib.mfx_env_texel_index(int(size), len(d), dptr(d), out.ctypes.data_as(C.POINTER(C.c_uint32))),
+          "mfx_env_texel_index")
+    return out[:len(d)]
+
+
 _P = C.POINTER
 _dp = _P(C.c_double)
 _ip = _P(C.c_int32)
@@ -304,6 +336,9 @@ def _bind(lib, strict: bool = True):
         "mfx_pinhole_derive": (C.c_int, [_P(MfxPinhole), _dp]),
         "mfx_camera_info": (C.c_int, [C.c_void_p, _dp]),
         "mfx_set_camera": (C.c_int, [C.c_void_p, _P(MfxPinhole)]),
+        "mfx_set_environment": (C.c_int, [C.c_void_p, _P(MfxEnvironment)]),
+        "mfx_environment_info": (C.c_int, [C.c_void_p, _dp]),
+        "mfx_env_texel_index": (C.c_int, [C.c_int32, C.c_int64, _dp, _P(C.c_uint32)]),
         "mfx_render_rgba8": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint8)]),
         "mfx_accumulate_render_rgba8": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint8)]),
         "mfx_stats": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -346,7 +381,7 @@ def _bind(lib, strict: bool = True):
 
 
 EXPORTED_SYMBOLS = [
-    "mfx_create", "mfx_create_instanced", "mfx_create_lights", "mfx_light_info", "mfx_light_table", "mfx_create_textured", "mfx_texture_info", "mfx_uv_table", "mfx_texel_index", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_sample_adaptive_resume", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_temporal", "mfx_pinhole_derive", "mfx_camera_info", "mfx_set_camera", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
+    "mfx_create", "mfx_create_instanced", "mfx_create_lights", "mfx_light_info", "mfx_light_table", "mfx_create_textured", "mfx_texture_info", "mfx_uv_table", "mfx_texel_index", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_sample_adaptive_resume", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_temporal", "mfx_pinhole_derive", "mfx_camera_info", "mfx_set_camera", "mfx_set_environment", "mfx_environment_info", "mfx_env_texel_index", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
     "mfx_film_mean", "mfx_stats",
     "mfx_trace_accumulate", "mfx_accum_clear", "mfx_accum_reduce", "mfx_accum_device_ptr", "mfx_accum_attach", "mfx_accum_read_mean",
     "mfx_sync", "mfx_stream", "mfx_ray_counts", "mfx_last_trace_ms", "mfx_trace_timing", "mfx_ray_counts_total", "mfx_closest_hit", "mfx_any_hit", "mfx_ref_leaves",

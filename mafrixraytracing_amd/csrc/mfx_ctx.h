@@ -1,6 +1,6 @@
 // mfx_ctx.h — the context behind the extern "C" boundary, shared by its translation units
 // (mfx_api.cpp, mfx_create.cpp, mfx_trace.cpp, mfx_readback.cpp, mfx_ahead.cpp, mfx_adaptive.cpp,
-// mfx_denoise_api.cpp, mfx_query.cpp). Internal: never included from include/.
+// mfx_denoise_api.cpp, mfx_query.cpp, mfx_environment.cpp). Internal: never included from include/.
 // Ownership: a GPU resource is a member (DevBuf, HostBuf, Event, Stream) of the struct of the
 // feature that uses it, and nothing is freed by hand. A feature that allocates at its first call is
 // a nested struct of mfx_ctx whose ready() says whether it has.
@@ -351,6 +351,14 @@ struct Textures {
     MfxTexTables tables() const { return host.on ? MfxTexTables{d_uvrec, d_ptex, d_desc, d_texels} : MfxTexTables{}; }
 };
 
+// The sky (mfx_set_environment; mfx_environment.cpp), per device: the map's texels in HBM. Like the textures it
+// is no part of SceneImages: an mfx_set_camera rebuild leaves it where it is.
+struct Environment {
+    DevBuf<float> d_rgb;             // [size * size][3] linear RGB radiance
+    int32_t size = 0;                // 0: no environment
+    bool on() const { return size > 0; }
+};
+
 // What scene_shapes chooses for k_extend (ext) and k_shadow (shd): wf_trace copies it into a trace's WfParams
 struct LaunchShapes {
     int stack_lds_ext = 0, stack_lds_shd = 0;  // traversal stack entries per lane in LDS; the rest in d_spill
@@ -467,6 +475,7 @@ struct __attribute__((visibility("hidden"))) mfx_ctx {
     mfxh::Readback rb;
     mfxh::Multi multi;
     mfxh::Textures tex;
+    mfxh::Environment sky;
 
     // the RCCL communicators, then the peers, then this device current; the members release themselves
     ~mfx_ctx();
@@ -494,11 +503,15 @@ inline bool wf_multi_light(const mfx_ctx* c) { return c->scene.multi_light(); }
 // and k_aov, the wavefront pipeline for every trace, a texel-id plane in the pool
 inline bool wf_textured(const mfx_ctx* c) { return c->tex.host.on; }
 
+// a sky (mfx_set_environment): the ENV instances of k_extend, k_camera and k_resolve, the wavefront pipeline
+// for every trace, a miss-record word per slot in the pool
+inline bool wf_env(const mfx_ctx* c) { return c->sky.on(); }
+
 // bytes of one path slot of the wavefront pool (ray queues included)
 inline size_t pool_slot_bytes(const mfx_ctx* c) {
     const int nv = c->scene.host.max_depth + 1;  // vertices per path
     return WF_DOUBLES_PER_SLOT(nv) * 8 + WF_WORDS_PER_SLOT(nv) * 4 + (wf_multi_light(c) ? WF_LIGHT_BYTES_PER_SLOT(nv) : 0) +
-           (wf_textured(c) ? WF_TEXEL_BYTES_PER_SLOT(nv) : 0);
+           (wf_textured(c) ? WF_TEXEL_BYTES_PER_SLOT(nv) : 0) + (wf_env(c) ? WF_ENV_BYTES_PER_SLOT : 0);
 }
 
 // the scene images' device pointers of a kernel parameter struct (WfParams, TraceParams, AovParams, QueryParams)

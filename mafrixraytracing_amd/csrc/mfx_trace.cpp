@@ -62,6 +62,17 @@ static int wf_ensure_pool(mfx_ctx* c, int32_t pool, bool queues) {
     A.vmat = (WfMat*)take(P * sizeof(WfMat) * nv);
     A.vlt = wf_multi_light(c) ? (uint8_t*)take(P * WF_LIGHT_BYTES_PER_SLOT(nv)) : nullptr;  // (in pool_slot_bytes)
     A.vtex = wf_textured(c) ? (uint32_t*)take(P * WF_TEXEL_BYTES_PER_SLOT(nv)) : nullptr;  // (in pool_slot_bytes)
+    // a sky: the slots' miss records, all "none" from here on (k_resolve puts the value back where it reads a miss)
+    A.env_rec = wf_env(c) ? (uint32_t*)take(P * WF_ENV_BYTES_PER_SLOT) : nullptr;  // (in pool_slot_bytes)
+    if (A.env_rec) {
+        const hipError_t ef = hipMemsetAsync(A.env_rec, 0xff, P * WF_ENV_BYTES_PER_SLOT, c->stream);
+        if (ef != hipSuccess) {
+            wp.mem.reset();
+            wp.bytes = 0;
+            A.env_rec = nullptr;
+            return fail(MFX_E_DEVICE, std::string("wavefront pool: ") + hipGetErrorString(ef));
+        }
+    }
     A.vstride = (int64_t)P;
     A.rn = (uint32_t*)take(P * 4);
     A.depth = (int32_t*)take(P * 4);
@@ -151,6 +162,9 @@ static void fill_scene_params(mfx_ctx* c, WfParams& P) {
     P.nlights = wf_multi_light(c) ? (int32_t)c->scene.host.lights.size() : 0;
     // albedo textures: the TX instances' tables (vtex set, by wf_ensure_pool: the launchers run them)
     P.tx = c->tex.tables();
+    // a sky: the ENV instances' map (env_rec set, by wf_ensure_pool: the launchers run them)
+    P.env_rgb = wf_env(c) ? c->sky.d_rgb.get() : nullptr;
+    P.env_size = c->sky.size;
     P.cam_dev = c->scene.d_cam;
     P.refs_dev = c->scene.d_refs;
     P.gray_light = wf_gray_light(c);
@@ -416,8 +430,8 @@ int mfxh::dev_trace_accumulate(mfx_ctx* c, int32_t spp, int64_t sample_base, Res
     // is exact, and its per-path arithmetic is the wavefront's, so the bits are the same; it does
     // not pay the wavefront's per-bounce launches over a 2 M-path frame (r02e: 1.7 vs 7.9 ms at 1080p).
     // (several lights: always the wavefront, as under MFX_F_WAVEFRONT; creation refused MFX_F_MEGAKERNEL)
-    // (albedo textures: likewise)
-    c->mega_last = !wf_multi_light(c) && !wf_textured(c) && ((c->flags & MFX_F_MEGAKERNEL) != 0 || (ns == 1 && (c->flags & MFX_F_WAVEFRONT) == 0));
+    // (albedo textures, a sky: likewise; mfx_set_environment refuses an MFX_F_MEGAKERNEL context)
+    c->mega_last = !wf_multi_light(c) && !wf_textured(c) && !wf_env(c) && ((c->flags & MFX_F_MEGAKERNEL) != 0 || (ns == 1 && (c->flags & MFX_F_WAVEFRONT) == 0));
     if (ns == 0) {  // this partition has no sample in the call: zero rays in zero device time
         HIPCHECK(hipEventRecord(c->ev0, c->stream));
         HIPCHECK(hipEventRecord(c->ev1, c->stream));

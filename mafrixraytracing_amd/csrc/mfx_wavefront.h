@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "mfx_camera_cuts.h"
+#include "mfx_environment.h"
 #include "mfx_layout.h"
 #include "mfx_texture.h"
 
@@ -212,6 +213,14 @@ struct WfParams {
     // on an untextured primitive) and stores it in vtex, where k_resolve finds the texel its albedo takes.
     MfxTexTables tx;
     uint32_t* vtex;          // [vertex][stride] the vertex's texel id (beside vmat; allocated in textured contexts only)
+    // The sky (mfx_set_environment; otherwise null, null, 0, and none of the instances without reads them). It
+    // runs the ENV instances of k_extend, k_camera and k_resolve: the kernel that finds a miss stores texel id |
+    // nv << 24 in the path slot's word of env_rec (mfx_environment.h; nv = the iteration, the vertices before the
+    // miss), and k_resolve starts that path's fold with the texel's radiance and puts MFX_ENV_NONE back, so the
+    // plane is filled once, when the pool is allocated.
+    const float* env_rgb;    // [size * size][3] linear RGB radiance
+    uint32_t* env_rec;       // [pool slot] the miss record (in the pool; allocated with an environment only)
+    int32_t env_size;
 };
 #define WF_MAX_LIGHTS 64  // MFX_MAX_LIGHTS: a light index is 6 bits of k_shadow's pending flag word
 
@@ -254,6 +263,8 @@ hipError_t mfx_wf_tile_check(const TileCheckParams& C, hipStream_t st);
 #define WF_LIGHT_BYTES_PER_SLOT(nvert) (nvert)
 // albedo textures: four bytes per vertex more, the vertices' texel ids (WfParams::vtex)
 #define WF_TEXEL_BYTES_PER_SLOT(nvert) (4 * (nvert))
+// the sky: one word per slot, the miss record (WfParams::env_rec)
+#define WF_ENV_BYTES_PER_SLOT 4
 
 #ifndef WF_STACK_LDS
 #define WF_STACK_LDS 16  // traversal stack entries per lane kept in LDS (deeper ones spill to HBM/L2)
@@ -279,11 +290,13 @@ struct WfLdsShape {
     int nslot;      // slots' test prefixes
     bool ml;        // k_shadow's several-light instance (WfParams::lights set; the same LDS footprint)
     bool tx;        // k_shadow's textured instance (WfParams::vtex set; its table pointers take 32 B of LDS more)
+    bool env;       // k_extend's ENV instance (WfParams::env_rec set; the same LDS footprint)
 };
 // resident blocks per CU of the kernel instance that holds shape s
 hipError_t mfx_wf_kernel_occupancy(const WfLdsShape& s, int* blocks_per_cu);
 // resident blocks per CU of k_resolve's accumulator instance (ml: the several-light one, tx: the textured one)
-hipError_t mfx_wf_resolve_occupancy(bool ml, int* blocks_per_cu, bool tx = false);
+// (env: the ENV one)
+hipError_t mfx_wf_resolve_occupancy(bool ml, int* blocks_per_cu, bool tx = false, bool env = false);
 // resident blocks per CU of k_camera (camera-ray packets; cuts: its CUTS instance)
 hipError_t mfx_cam_occupancy(int stack_size, int* blocks_per_cu, bool cuts = false);
 // a ray queue's arrays (MFX_RAY_QUEUE): entries in the pool's shard ranges, counts per shard

@@ -560,7 +560,11 @@ __device__ __forceinline__ VertexSample sample_vertex(const MfxLight& LT1, bool 
 // NF: the node format (node_step): the instances a flat scene's default path launches (the bounce and
 // queue ones, wf_nf) are built for one format each, so their node loop holds one step and none of the
 // other's registers; the rest (STATS, START, LIST, the other scene kinds) take either (MFX_NF_ANY)
-template <bool STATS, bool SPILL, int SK, bool Q, bool START = false, int LIST = WF_LIST_NONE, int NF = MFX_NF_ANY>
+// ENV: the instances for a sky (mfx_set_environment): a miss stores the texel of the ray's direction and the
+// iteration (the vertices before the miss; wave-uniform) in the path slot's word of P.env_rec, through qslot
+// on a queue. A template parameter for ML's reason: the instances without hold none of it.
+template <bool STATS, bool SPILL, int SK, bool Q, bool START = false, int LIST = WF_LIST_NONE, int NF = MFX_NF_ANY,
+          bool ENV = false>
 __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
     constexpr bool INST = SK == WF_SK_INST, SLDS = SK == WF_SK_SLDS;
     extern __shared__ int lds_all[];
@@ -653,6 +657,9 @@ __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
         } else {  // a later miss finishes the path: its lit mask goes into the state word
             const int lm = fresh || Q ? 0 : (lit_in_entry ? (se >> 28) & 7 : (P.depth[s] >> WF_LIT_SHIFT) & 0xffff);
             P.state[s] = WF_MISS | (lm << WF_SHADE_SHIFT) | fl;
+            if constexpr (ENV)  // the path ends in the sky: k_resolve starts its fold there
+                P.env_rec[Q ? P.qslot[s] : s] =
+                    mfx_env_texel(T.d.x, T.d.y, T.d.z, P.env_size) | ((uint32_t)P.iter << MFX_ENV_NV_SHIFT);
         }
         active = false;
     };
@@ -757,7 +764,10 @@ __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
 // per-tile counts (WF_LIST_TILE_N) so is its count; a window past the tile's share has no active lane
 // CUTS: the packets start from their tile's cut (WfParams::cuts) instead of the root; the instance without
 // holds none of it
-template <bool STATS, int LIST = WF_LIST_NONE, bool CUTS = false>
+// ENV: the instances for a sky: a camera ray's miss stores the texel of its direction in the slot's word of
+// P.env_rec (no vertex before it). A tile whose cut is empty still makes no ray and walks nothing, but its lanes
+// derive their key, draws and direction for the texel, unless the map is one texel (id 0 whatever the direction).
+template <bool STATS, int LIST = WF_LIST_NONE, bool CUTS = false, bool ENV = false>
 __global__ void __launch_bounds__(256, MFX_CAM_WAVES) k_camera(WfParams P) {
     extern __shared__ int lds_all[];
     const int lane = lane_id();
@@ -824,7 +834,8 @@ __global__ void __launch_bounds__(256, MFX_CAM_WAVES) k_camera(WfParams P) {
         const bool seen = !(CUTS && MFX_CUT_EMPTY_SKIP) || row->code != MFX_CUT_END;
         if (act && !seen) c_primary++;
         DV o = dv(0, 0, 0), d = dv(0, 0, 1);
-        if (act && seen) {  // PixelIntegrator.Sample (Integrators.fs:167-169) + GetRay (Camera.fs:134-139)
+        const bool aim = seen || (ENV && P.env_size > 1);  // (without ENV: seen)
+        if (act && aim) {  // PixelIntegrator.Sample (Integrators.fs:167-169) + GetRay (Camera.fs:134-139)
             const int64_t pixel = (int64_t)x * P.height + y;  // Color[w,h] x-major
             const int64_t gsample = path_gsample<LIST>(P, smp);
             const uint64_t key = path_key(P.seed, (uint64_t)pixel, (uint64_t)gsample);
@@ -835,7 +846,7 @@ __global__ void __launch_bounds__(256, MFX_CAM_WAVES) k_camera(WfParams P) {
             const DV target = vadd(vadd(ld3(CAM.topleft), vmul(ld3(CAM.right), u)), vmul(ld3(CAM.down), v));
             o = ld3(CAM.position);
             d = vnormalize(vsub(target, o));
-            c_primary++;
+            if (!ENV || seen) c_primary++;
         }
         Best B;
 #if MFX_DIAG_STAMPS == 3
@@ -853,6 +864,7 @@ __global__ void __launch_bounds__(256, MFX_CAM_WAVES) k_camera(WfParams P) {
                 P.state[j] = ((B.info & MFX_INFO_SHADE_MASK) << WF_SHADE_SHIFT) | WF_HIT | WF_FRESH;
             } else {
                 P.state[j] = WF_MISS | WF_FRESH;
+                if constexpr (ENV) P.env_rec[j] = mfx_env_texel(d.x, d.y, d.z, P.env_size);
             }
         }
         CAM_MARK(t_out);
@@ -1332,11 +1344,13 @@ __device__ __forceinline__ uint32_t load_texel(const WfParams& P, int64_t at) {
     const uint32_t id = P.vtex[at];
     return id == MFX_TEXEL_NONE ? MFX_TEXEL_NONE : P.tx.texels[id];
 }
-template <bool ML, bool TX>
-__device__ __forceinline__ void load_path(const WfParams& P, int64_t j, int mask, PathRec& R) {
+// ENV: the records up to vertex etop (a path that ended in the sky folds every vertex before its miss, the
+// unlit ones above its deepest lit one too; etop < 0: no vertex); without, up to the deepest lit vertex
+template <bool ML, bool TX, bool ENV = false>
+__device__ __forceinline__ void load_path(const WfParams& P, int64_t j, int mask, PathRec& R, int etop = -1) {
     R.mask = mask;
-    if (mask == 0) return;
-    const int top = 31 - __builtin_clz(mask);
+    if (ENV ? etop < 0 : mask == 0) return;
+    const int top = ENV ? etop : 31 - __builtin_clz(mask);
 #pragma unroll
     for (int v = 0; v < WF_RES_VERTS; ++v) {
         R.ei[v] = 0.0; R.cs[v] = 0.0; R.so[v] = 0.0; R.mat[v] = 0;
@@ -1401,10 +1415,10 @@ __device__ __forceinline__ void fold_vertex(const WfParams& P, bool lit, double 
     fy = (ay + fy) * cy;
     fz = (az + fz) * cz;
 }
-template <bool ML, bool TX>
+template <bool ML, bool TX, bool ENV = false>
 __device__ __forceinline__ void fold_path(const WfParams& P, int64_t j, const PathRec& R, const double* alb_lds,
-                                          double& fx, double& fy, double& fz, const double* lt_lds) {
-    const int top = 31 - __builtin_clz(R.mask);
+                                          double& fx, double& fy, double& fz, const double* lt_lds, int etop = -1) {
+    const int top = ENV ? etop : 31 - __builtin_clz(R.mask);  // (ENV: f comes in as the sky's radiance, or black)
     // vertices deeper than the batched records (max_depth >= WF_RES_VERTS), read here
     for (int v = top; v >= WF_RES_VERTS; --v) {
         const bool lit = (R.mask >> v) & 1;
@@ -1454,7 +1468,12 @@ __device__ __forceinline__ void fold_path(const WfParams& P, int64_t j, const Pa
 // indexed by the light a lit vertex recorded (P.vlt); the one-light instances carry none of it
 // TX: the instances for albedo textures: every vertex's texel, gathered through the id k_shadow<TX> stored
 // (P.vtex), scales its albedo; the untextured instances carry none of it
-template <int MODE, bool ML = false, bool TX = false>
+// ENV: the instances for a sky: every path of the generation reads its slot's miss record (P.env_rec). A set
+// record means the path ended in a miss after nv vertices: its fold starts with the texel's radiance, widened
+// exactly, and covers vertices nv - 1 .. 0 (none for a camera ray's miss: the texel itself, the background),
+// and the record goes back to MFX_ENV_NONE. Such a path adds to its pixel whatever its lit mask; a path
+// that ended by depth alone is as without.
+template <int MODE, bool ML = false, bool TX = false, bool ENV = false>
 __global__ void __launch_bounds__(256) k_resolve(WfParams P) {
     constexpr bool FRAMES = MODE == WF_RES_FRAMES, MOM = MODE == WF_RES_MOMENTS;
     __shared__ double alb[3 * WF_RES_MAT_LDS];
@@ -1523,14 +1542,38 @@ __global__ void __launch_bounds__(256) k_resolve(WfParams P) {
             mask[u] = ((sw[u] & WF_STATE_MASK) == WF_DONE || (sw[u] & WF_STATE_MASK) == WF_MISS)
                           ? ((unsigned)sw[u] >> WF_SHADE_SHIFT) & 0xffff : 0;
         }
+        [[maybe_unused]] uint32_t ew[U];  // ENV: the paths' miss records
+        [[maybe_unused]] int etop[U];     // and their deepest vertex to fold (-1: none)
+        if constexpr (ENV) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                ew[u] = in[u] ? P.env_rec[jv[u]] : MFX_ENV_NONE;
+                etop[u] = ew[u] != MFX_ENV_NONE ? (int)(ew[u] >> MFX_ENV_NV_SHIFT) - 1
+                                                : (mask[u] ? 31 - __builtin_clz(mask[u]) : -1);
+            }
+        }
         PathRec R[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) load_path<ML, TX>(P, jv[u], mask[u], R[u]);
+        for (int u = 0; u < U; ++u) {
+            if constexpr (ENV) load_path<ML, TX, true>(P, jv[u], mask[u], R[u], etop[u]);
+            else load_path<ML, TX>(P, jv[u], mask[u], R[u]);
+        }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (!in[u]) continue;
             double fx = 0.0, fy = 0.0, fz = 0.0;
-            if (R[u].mask) fold_path<ML, TX>(P, jv[u], R[u], alb, fx, fy, fz, lt_lds);
+            if constexpr (ENV) {
+                if (ew[u] != MFX_ENV_NONE) {
+                    const float* e = P.env_rgb + 3 * (size_t)(ew[u] & MFX_ENV_ID_MASK);
+                    fx = (double)e[0];
+                    fy = (double)e[1];
+                    fz = (double)e[2];
+                    P.env_rec[jv[u]] = MFX_ENV_NONE;
+                }
+                if (etop[u] >= 0) fold_path<ML, TX, true>(P, jv[u], R[u], alb, fx, fy, fz, lt_lds, etop[u]);
+            } else if (R[u].mask) {
+                fold_path<ML, TX>(P, jv[u], R[u], alb, fx, fy, fz, lt_lds);
+            }
             if (FRAMES) {
                 ax = ax + (0.0 + fx) / 1.0;
                 ay = ay + (0.0 + fy) / 1.0;
@@ -1543,7 +1586,7 @@ __global__ void __launch_bounds__(256) k_resolve(WfParams P) {
                     o[2] = post_byte(az / cnt);
                     o[3] = 255;
                 }
-            } else if (R[u].mask) {  // a path with no lit vertex adds nothing
+            } else if (R[u].mask || (ENV && ew[u] != MFX_ENV_NONE)) {  // a path with no lit vertex adds nothing (ENV: unless it ended in the sky)
                 ax += fx;
                 ay += fy;
                 az += fz;
@@ -1652,6 +1695,11 @@ static constexpr bool shadow_built(const WfKey& k) {
 static constexpr bool camera_built(const WfKey& k) {
     return !k.ml && !k.tx && !k.spill && k.sk == WF_SK_FLAT && !k.queue && k.start && k.nf == MFX_NF_ANY && k.waves == 4;
 }
+// (a sky, ENV: k_extend and k_camera record a miss; every instance without the traversal counters has its ENV
+// twin, and contexts created with MFX_F_COUNT_STATS refuse mfx_set_environment. Not a key field: the twin is
+// chosen beside the key, as k_camera's CUTS twin is. k_shadow has none: shadow rays ignore the sky.)
+static constexpr bool extend_env_built(const WfKey& k) { return extend_built(k) && !k.stats; }
+static constexpr bool camera_env_built(const WfKey& k) { return camera_built(k) && !k.stats; }
 static constexpr int built_count(bool (*built)(const WfKey&)) {
     int n = 0;
     for (int i = 0; i < WF_KEYS; ++i) n += built(key_at(i));
@@ -1663,8 +1711,11 @@ static_assert(built_count(extend_built) == (MFX_NODE_F16 ? 64 : 60) &&
               "(k_shadow: 152 / 144 one-light instances, plus the several-light ones, ML: every spill, scene kind, "
               "queue and list of the 4-wave build without counters, 36, and the FP16 format of the 4 flat unlisted ones; "
               "the textured ones, TX, are as many again in each ML state)");
+static_assert(built_count(extend_env_built) == (MFX_NODE_F16 ? 34 : 30) && built_count(camera_env_built) == 3,
+              "the sky's instances, ENV: the twin of every k_extend instance without counters, 34 / 30, and of every "
+              "k_camera instance without counters in both CUTS states, 2 * 3; k_resolve's twelve have a twin each");
 
-enum { WF_K_EXTEND, WF_K_SHADOW, WF_K_CAMERA, WF_K_CAMERA_CUTS };
+enum { WF_K_EXTEND, WF_K_SHADOW, WF_K_CAMERA, WF_K_CAMERA_CUTS, WF_K_EXTEND_ENV, WF_K_CAMERA_ENV, WF_K_CAMERA_CUTS_ENV };
 template <int KERNEL, int I>
 static const void* instance_at() {
     constexpr WfKey k = key_at(I);
@@ -1676,6 +1727,12 @@ static const void* instance_at() {
         return (const void*)k_camera<k.stats, k.list>;
     else if constexpr (KERNEL == WF_K_CAMERA_CUTS && camera_built(k))  // every k_camera instance has its CUTS twin
         return (const void*)k_camera<k.stats, k.list, true>;
+    else if constexpr (KERNEL == WF_K_EXTEND_ENV && extend_env_built(k))
+        return (const void*)k_extend<k.stats, k.spill, k.sk, k.queue, k.start, k.list, k.nf, true>;
+    else if constexpr (KERNEL == WF_K_CAMERA_ENV && camera_env_built(k))
+        return (const void*)k_camera<k.stats, k.list, false, true>;
+    else if constexpr (KERNEL == WF_K_CAMERA_CUTS_ENV && camera_env_built(k))
+        return (const void*)k_camera<k.stats, k.list, true, true>;
     else
         return nullptr;
 }
@@ -1684,11 +1741,17 @@ static const void* instance(const WfKey& k, std::index_sequence<I...>) {
     static const void* const table[WF_KEYS] = {instance_at<KERNEL, (int)I>()...};
     return table[key_index(k)];
 }
-// a key's kernel (null: not built)
-static const void* extend_kernel(const WfKey& k) { return instance<WF_K_EXTEND>(k, std::make_index_sequence<WF_KEYS>{}); }
+// a key's kernel (null: not built); env: its ENV twin
+static const void* extend_kernel(const WfKey& k, bool env = false) {
+    return env ? instance<WF_K_EXTEND_ENV>(k, std::make_index_sequence<WF_KEYS>{})
+               : instance<WF_K_EXTEND>(k, std::make_index_sequence<WF_KEYS>{});
+}
 static const void* shadow_kernel(const WfKey& k) { return instance<WF_K_SHADOW>(k, std::make_index_sequence<WF_KEYS>{}); }
 // (cuts: the twin that starts from the cut table, WfParams::cuts set; not a key field, k_camera alone has it)
-static const void* camera_kernel(const WfKey& k, bool cuts) {
+static const void* camera_kernel(const WfKey& k, bool cuts, bool env = false) {
+    if (env)
+        return cuts ? instance<WF_K_CAMERA_CUTS_ENV>(k, std::make_index_sequence<WF_KEYS>{})
+                    : instance<WF_K_CAMERA_ENV>(k, std::make_index_sequence<WF_KEYS>{});
     return cuts ? instance<WF_K_CAMERA_CUTS>(k, std::make_index_sequence<WF_KEYS>{})
                 : instance<WF_K_CAMERA>(k, std::make_index_sequence<WF_KEYS>{});
 }
@@ -1710,7 +1773,7 @@ hipError_t mfx_wf_kernel_occupancy(const WfLdsShape& s, int* blocks_per_cu) {
     if (!s.shadow && !wf_nf_fixed(k)) k.start = true;
     const size_t lds = wf_lds_bytes(s);
     const hipError_t e =
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, s.shadow ? shadow_kernel(k) : extend_kernel(k), 256, lds);
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, s.shadow ? shadow_kernel(k) : extend_kernel(k, s.env), 256, lds);
     // (the API counts finer LDS granules than the hardware allocates: measured, k_shadow at 53,952 B per
     // block runs 2 blocks per CU where it says 3, a 10 % loss)
     *blocks_per_cu = std::min(*blocks_per_cu, mfx_lds_blocks(lds));
@@ -1737,18 +1800,23 @@ static WfLdsShape lds_shape(const WfParams& P, bool shadow) {
     const int stack_lds = shadow ? P.stack_lds_shd : P.stack_lds_ext;
     return {shadow, stack_lds < P.stack_size, wf_fp16(P), stack_lds, shadow ? P.ntop_shd : P.ntop_ext,
             P.inst ? P.ninst_lds : 0, shadow ? P.nslot_shd : P.nslot_ext, shadow && P.lights != nullptr,
-            shadow && P.vtex != nullptr};
+            shadow && P.vtex != nullptr, !shadow && P.env_rec != nullptr};
 }
 
 static hipError_t launch_iteration(const WfParams& P, int ext_grid, int shd_grid, bool stats, hipStream_t st,
                                    hipEvent_t* ev) {
     const int list = list_kind(P.ntiles, P.tile_n);
+    const bool env = P.env_rec != nullptr;  // a sky: the ENV twins of k_camera and k_extend
     if (!P.inst && P.start && P.cam_grid > 0) {  // camera rays as packets
-        launch(camera_kernel(camera_key(stats, list), P.cuts != nullptr), P.cam_grid, cam_lds_bytes(P.stack_size), st, P);
+        const void* cam = camera_kernel(camera_key(stats, list), P.cuts != nullptr, env);
+        if (!cam) return hipErrorInvalidValue;  // (a sky with counters: refused by mfx_set_environment)
+        launch(cam, P.cam_grid, cam_lds_bytes(P.stack_size), st, P);
     } else {
         const WfLdsShape s = lds_shape(P, false);
         const bool queue = P.qcount != nullptr, start = !queue && P.start;
-        launch(extend_kernel(shape_key(s, stats, queue, start, start ? list : WF_LIST_NONE, 4)), ext_grid, wf_lds_bytes(s), st, P);
+        const void* ext = extend_kernel(shape_key(s, stats, queue, start, start ? list : WF_LIST_NONE, 4), env);
+        if (!ext) return hipErrorInvalidValue;
+        launch(ext, ext_grid, wf_lds_bytes(s), st, P);
     }
     if (ev) {  // between the two kernels (per-stage timing); null: not recorded
         const hipError_t e = hipEventRecord(ev[0], st);
@@ -1768,6 +1836,8 @@ hipError_t mfx_wf_iteration(const WfParams& P, int ext_grid, int shd_grid, bool 
     if (P.lights && (!P.vlt || P.nlights < 2 || P.nlights > WF_MAX_LIGHTS || P.gray_light || stats)) return hipErrorInvalidValue;
     // albedo textures: the id plane and the tables go together (k_shadow<TX> reads the tables and writes vtex)
     if (P.vtex && (!P.tx.uvrec || !P.tx.ptex || !P.tx.desc || !P.tx.texels || stats)) return hipErrorInvalidValue;
+    // a sky: the record plane and the map go together (k_extend<ENV> / k_camera<ENV> write env_rec)
+    if (P.env_rec && (!P.env_rgb || P.env_size < 1 || P.env_size > MFX_ENV_SIZE_MAX || stats)) return hipErrorInvalidValue;
     // the chunk heads and, beside them (WF_CTL_Q0 / WF_CTL_Q1), the next queue's shard counts
     unsigned long long* z = P.ctl;
     size_t nz = WF_NCTL;
@@ -1782,11 +1852,15 @@ hipError_t mfx_wf_iteration(const WfParams& P, int ext_grid, int shd_grid, bool 
     return hipGetLastError();
 }
 
-// k_resolve's instance of a mode: several lights (ML) and albedo textures (TX) each have one
+// k_resolve's instance of a mode: several lights (ML), albedo textures (TX) and a sky (ENV) each have one
+template <int MODE, bool ENV>
+static const void* resolve_kernel_env(bool ml, bool tx) {
+    return ml ? (tx ? (const void*)k_resolve<MODE, true, true, ENV> : (const void*)k_resolve<MODE, true, false, ENV>)
+              : (tx ? (const void*)k_resolve<MODE, false, true, ENV> : (const void*)k_resolve<MODE, false, false, ENV>);
+}
 template <int MODE>
-static const void* resolve_kernel(bool ml, bool tx) {
-    return ml ? (tx ? (const void*)k_resolve<MODE, true, true> : (const void*)k_resolve<MODE, true, false>)
-              : (tx ? (const void*)k_resolve<MODE, false, true> : (const void*)k_resolve<MODE, false, false>);
+static const void* resolve_kernel(bool ml, bool tx, bool env) {
+    return env ? resolve_kernel_env<MODE, true>(ml, tx) : resolve_kernel_env<MODE, false>(ml, tx);
 }
 static hipError_t launch_resolve(const void* kernel, int64_t threads, hipStream_t st, const WfParams& P) {
     void* args[] = {const_cast<WfParams*>(&P)};
@@ -1799,17 +1873,19 @@ hipError_t mfx_wf_resolve(const WfParams& P, hipStream_t st) {
     const bool tx = P.vtex != nullptr;    // albedo textures: the TX instance
     if (ml && (!P.vlt || P.nlights < 2 || P.nlights > WF_MAX_LIGHTS || P.gray_light)) return hipErrorInvalidValue;
     if (tx && !P.tx.texels) return hipErrorInvalidValue;
+    const bool env = P.env_rec != nullptr;  // a sky: the ENV instance
+    if (env && (!P.env_rgb || P.env_size < 1 || P.env_size > MFX_ENV_SIZE_MAX)) return hipErrorInvalidValue;
     if (P.mom || P.ntiles > 0) {  // the adaptive sampler's passes: the moments instance (a listed trace runs no other)
         if (!P.mom || P.film || P.res_ntx > 0) return hipErrorInvalidValue;
         const int64_t n = P.ntiles > 0 ? (int64_t)P.ntiles * 64 : (int64_t)((P.width + 7) >> 3) * P.band_rows * 64;
-        return launch_resolve(resolve_kernel<WF_RES_MOMENTS>(ml, tx), n, st, P);
+        return launch_resolve(resolve_kernel<WF_RES_MOMENTS>(ml, tx, env), n, st, P);
     }
     const int64_t per_sample = (int64_t)(P.res_ntx > 0 ? P.res_ntx : (P.width + 7) >> 3) * P.band_rows * 64;
-    return launch_resolve(P.film ? resolve_kernel<WF_RES_FRAMES>(ml, tx) : resolve_kernel<WF_RES_ACCUM>(ml, tx), per_sample, st, P);
+    return launch_resolve(P.film ? resolve_kernel<WF_RES_FRAMES>(ml, tx, env) : resolve_kernel<WF_RES_ACCUM>(ml, tx, env), per_sample, st, P);
 }
 
-hipError_t mfx_wf_resolve_occupancy(bool ml, int* blocks_per_cu, bool tx) {
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, resolve_kernel<WF_RES_ACCUM>(ml, tx), 256, 0);
+hipError_t mfx_wf_resolve_occupancy(bool ml, int* blocks_per_cu, bool tx, bool env) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, resolve_kernel<WF_RES_ACCUM>(ml, tx, env), 256, 0);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -13,7 +13,7 @@ import numpy as np
 from .abi import (INSTANCING_KEYS, LAUNCH_INFO_KEYS, MFX_DN_SRC_ACCUM, MFX_DN_SRC_ADAPTIVE, MFX_DN_SRC_HOST,
                   MFX_DN_SRC_TEMPORAL, MFX_F_NONE, MFX_F_TWO_LEVEL, MfxAdaptive, MfxAdaptiveResume, MfxDenoiseCfg,
                   MfxDenoiseVarCfg, MfxInstance, MfxOptions, MfxPrimUv, MfxTemporalCfg, PRIM_UV_DTYPE, SceneArrays, check, dptr,
-                  iptr, load_library, pinhole_struct, quad_lights, texture_structs)
+                  iptr, load_library, pinhole_struct, quad_lights, texture_structs, environment_struct)
 from .denoise import DenoiseConfig, DenoiseVarConfig
 from .temporal import TemporalConfig
 
@@ -27,7 +27,7 @@ class NativeContext:
     def __init__(self, arrays: SceneArrays, seed: int = DEFAULT_SEED, device: int = 0, flags: int = MFX_F_NONE,
                  part_index: int = 0, part_count: int = 1, devices: list[int] | None = None,
                  instancing: bool = True, render_ahead: int = 0, lights: list | None = None,
-                 textures: list | None = None, prim_uv: np.ndarray | None = None):
+                 textures: list | None = None, prim_uv: np.ndarray | None = None, environment=None):
         """devices: drive this list of HIP devices from one context (mfx_options.devices; the
         library's own RCCL reduce sums them into devices[0]); None: the single `device`.
         instancing: a scene with instancing data is created through mfx_create_instanced (two-level
@@ -42,7 +42,9 @@ class NativeContext:
         (abi.PRIM_UV_DTYPE, one per primitive the context is created from: the templates of an instanced
         scene, the world list otherwise) create the context through mfx_create_textured, with `lights` or
         arrays.light. Pass arrays.textures and arrays.prim_uv for a scene loaded with textures=True. None:
-        an untextured context, whatever arrays holds."""
+        an untextured context, whatever arrays holds.
+        environment: an (S, S, 3) float32 octahedral map of linear RGB radiance (environment.py makes them), set
+        with set_environment right after creation: rays that leave the scene return its texel. None: black."""
         self.lib = load_library()
         self.arrays = arrays
         self.w, self.h = arrays.width, arrays.height
@@ -84,6 +86,12 @@ class NativeContext:
         else:
             check(self.lib.mfx_create(C.byref(self._desc), C.byref(opt), C.byref(h)), "mfx_create")
         self._h = h
+        if environment is not None:
+            try:
+                self.set_environment(environment)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_h", None):
@@ -223,6 +231,26 @@ class NativeContext:
         temporal and sample_adaptive_resume."""
         p = pinhole_struct(camera)
         check(self.lib.mfx_set_camera(self._h, C.byref(p)), "mfx_set_camera")
+
+    def set_environment(self, environment):
+        """mfx_set_environment: make the (S, S, 3) float32 octahedral map `environment` (linear RGB radiance; a
+        (3,) constant works too) the sky of every later call, or with None remove it. The texels are copied.
+        The film, the accumulator, next_sample and the feature buffers are left as they are; sample_adaptive()
+        must run again before sample_adaptive_resume and the adaptive source of denoise_var."""
+        if environment is None:
+            check(self.lib.mfx_set_environment(self._h, None), "mfx_set_environment")
+            return
+        e, keep = environment_struct(environment)
+        check(self.lib.mfx_set_environment(self._h, C.byref(e)), "mfx_set_environment")
+        del keep
+
+    def environment_info(self) -> np.ndarray:
+        """mfx_environment_info: [0] size, [1] 1 if the environment kernel instances run, [2] bytes of texels,
+        [3] bytes per path slot the environment adds to the pool, [4] / [5] resident blocks per CU of the
+        k_extend / k_resolve instance in use; [6], [7] 0. All 0 without an environment."""
+        out = np.zeros(8)
+        check(self.lib.mfx_environment_info(self._h, dptr(out)), "mfx_environment_info")
+        return out
 
     def camera_info(self) -> dict:
         """mfx_camera_info: the current derived camera (position, topleft, right, down; `derived` the twelve
