@@ -384,7 +384,8 @@ int mfx_set_camera(mfx_ctx* ctx, const mfx_pinhole* cam);
  * nv vertices, the unlit ones included; a camera ray that misses (nv = 0) contributes E itself, so the
  * background shows; a path that ends by depth alone is as without. Shadow rays ignore the sky, and the sky is
  * not light-sampled: only the hemisphere-sampled extension ray sees it, no draw is added and the RNG stream is
- * unchanged. A small bright sun in the map will therefore be noisy. Every surface stays Lambertian, so
+ * unchanged. A small bright sun in the map will therefore be noisy (mfx_set_environment_sampled below samples
+ * the map as a light instead). Every surface stays Lambertian, so
  * mfx_temporal's view independence holds, and mfx_aov's first-hit planes do not depend on the sky (a miss
  * still adds nothing there).                                                                             */
 typedef struct mfx_environment {
@@ -418,6 +419,88 @@ int mfx_environment_info(mfx_ctx* ctx, double out[8]);
  * direction dirs[3k .. 3k+2] in a size x size map. MFX_E_INVALID: a size outside [1, MFX_MAX_ENV_SIZE], a
  * NULL array with n > 0, n < 0.                                                                           */
 int mfx_env_texel_index(int32_t size, int64_t n, const double* dirs, uint32_t* id_out);
+
+/* ---- the sky as a light (ABI 6, additive; an extension like the sky itself) -------------------------------
+ * mfx_set_environment_sampled is mfx_set_environment, and the sky becomes the (N+1)-th light of the pick of
+ * mfx_create_lights: it is sampled at every path vertex in proportion to its radiance, so a small bright sun
+ * in the map is found by one vertex in N + 1 instead of one in 1e5. N >= 1 is the number of area lights, at
+ * most MFX_MAX_SKY_LIGHTS: the sky takes light index N.
+ *
+ * Everything is FP64 with one rounding per operation in the order written and no contraction.
+ * dot(a,b) = (a0*b0 + a1*b1) + a2*b2, sg(x) = x >= 0.0 ? 1.0 : -1.0, INVPI = 1. / 3.141592653589793.
+ *
+ * The table, built on the host when the sky is set; n = size*size:
+ *  - the weight of texel t is w_t = ((r + g) + b) * (1.0 / (len2_c * len_c)), r, g, b the texel widened
+ *    exactly, len2_c and len_c from the direction rule below at the texel's centre (ju = jv = 0.5): the
+ *    sampling density per solid angle is proportional to the texel's radiance. If every w_t is 0 (a black map)
+ *    every w_t is 1.0;
+ *  - an alias table over the w_t (Vose's method; the construction is the library's, deterministic for a given
+ *    map): per texel a float q[k] in [0, 1] and a uint32 alias[k];
+ *  - per texel the probability those two arrays imply, an exact statement of the arrays:
+ *    prob[t] = (q_t + sum over k with alias[k] == t, k != t, of (1 - q_k)) / n, q widened to double exactly,
+ *    the sum taken in increasing k from (double)q_t;
+ *  - a texel with w_t = 0 has q = 0 and is no entry's alias, so it is never returned.
+ *
+ * At a path vertex the steps are mfx_create_lights' steps 1-6 with N + 1 in place of N everywhere:
+ *  - the pick draw is taken always (N + 1 >= 2): n = (int)floor(r * (double)(N + 1));
+ *  - for n < N the vertex is an area-light vertex exactly as there, with pdf_n = (1.0 / area_n) / (double)(N + 1);
+ *  - for n == N, the sky:
+ *    1. four more draws, in this order: r1, r2, ju, jv;
+ *    2. k = (int)floor(r1 * (double)n_texels) clamped into [0, n_texels - 1]; t = r2 < (double)q[k] ? k : alias[k];
+ *       xi = t % size, yi = t / size;
+ *    3. the direction of (t, ju, jv): u = ((double)xi + ju) / (double)size, a = u * 2.0 - 1.0; b likewise from
+ *       yi, jv; py = (1.0 - |a|) - |b|; if (|a| + |b|) <= 1.0 then px = a, pz = b, otherwise
+ *       px = (1.0 - |b|) * sg(a), pz = (1.0 - |a|) * sg(b); len2 = (px*px + py*py) + pz*pz, len = sqrt(len2),
+ *       unit = (px/len, py/len, pz/len). This is the inverse of the texel rule above. The radiance used is
+ *       texel t's, by id, not a second lookup of unit;
+ *    4. cs = dot(unit, nm); the vertex is lightable iff cs > 0.0: the sky lights the side the normal points
+ *       to, the side the extension ray sees it from;
+ *    5. pdf_v = (((prob[t] * (double)(size*size)) * 0.25) * (len2 * len)) / (double)(N + 1) (a texel covers
+ *       4/size^2 of the (a, b) square, and d omega = da db / len^3);
+ *    6. the shadow query is the any-hit of Ray(hp, unit) on [1e-6, 99999999.], the extension ray's far bound;
+ *    7. the vertex is lit iff it is lightable and not occluded; its direct term is
+ *       a_v[c] = ((cs * E_t[c]) * INVPI) / pdf_v. (The INVPI is there because the fold multiplies the direct
+ *       term by col = 2 a ei, whose mean is the albedo; the reference's area-light term carries no 1/pi, a
+ *       radiance map needs it.)
+ *  - the fold f <- (a_v + f) * c_v, the hemisphere sample and the ray counters are as ever: one shadow ray per
+ *    vertex, and the primary, extension and shadow counts are those of the same context under a black sampled
+ *    sky. (Against a context with no sky they are equal where they do not depend on the draws: the pick draw and
+ *    the sky vertex's fifth draw move the later hemisphere samples to other draws, so in an open scene a path may
+ *    leave at another vertex.)
+ *
+ * The miss term under sampling: a camera ray that misses (nv = 0) still returns E, so the background shows; a
+ * later miss returns black, since the sky now reaches surfaces through the pick alone and would be counted
+ * twice. Consequence: a sampled sky lights every vertex 0 .. max_depth, as the area lights do, where an
+ * unsampled sky lights 0 .. max_depth - 1 (the last vertex sends no extension ray). With all light intensities
+ * 0, the sampled sky at depth D and the unsampled sky at depth D + 1 have the same expectation.
+ *
+ * The context runs the SKY instances of k_shadow and k_resolve (twins of the several-light ones, so one area
+ * light beside a sampled sky runs several-light instances and mfx_light_info reports them), the ENV instances
+ * of k_camera / k_extend for the camera rays and the plain ones for the bounces. The pool keeps 4 bytes more
+ * per path vertex (a sky vertex's texel id), and with one area light the byte per vertex of the light index.
+ * Out of scope: multiple importance sampling with the hemisphere sample, a power-proportional pick.        */
+#define MFX_MAX_SKY_LIGHTS 63   /* area lights at most beside a sampled sky: the sky takes light index N */
+
+/* mfx_set_environment, and the sky becomes a light that is sampled at every path vertex (the rule above).
+ * env == NULL removes the sky, as there. mfx_set_environment(ctx, env) on such a context makes the sky an
+ * unsampled one again. Refusals: mfx_set_environment's; MFX_E_STATE also for a context with 64 lights (the
+ * message names the count). A refused call changes nothing. It invalidates and keeps what mfx_set_environment
+ * does; a switch between none, unsampled and sampled releases the path pool (its layout changes), and the
+ * lights' pdf_n is recomputed with N + 1 when sampling goes on and with N when it goes off. An mfx_set_camera
+ * rebuild keeps the sampling. */
+int mfx_set_environment_sampled(mfx_ctx* ctx, const mfx_environment* env);
+/* out[0] = 1 if the sky is sampled, out[1] = N + 1, out[2] = bytes of the sampling table on the device
+ * (16 per texel), out[3] = bytes per path slot it adds to the pool (4 per vertex, 5 with one area light),
+ * out[4] / out[5] = resident blocks per CU of the k_shadow / k_resolve instance in use, out[6] = out[7] = 0.
+ * All 0 otherwise. */
+int mfx_sky_sampling_info(mfx_ctx* ctx, double out[8]);
+/* Host-only: the table creation builds from a map, by the code creation runs. q[n], alias[n], prob[n],
+ * n = size * size. The refusals of mfx_set_environment for the map. */
+int mfx_env_sample_table(const mfx_environment* env, float* q, uint32_t* alias, double* prob);
+/* Host-only: the direction rule, by the code the kernels compile. For texel[k] and jitter[2k], jitter[2k+1]:
+ * out[4k .. 4k+2] = the unit direction, out[4k+3] = len2 * len (the Jacobian factor of the pdf).
+ * MFX_E_INVALID: a size outside [1, MFX_MAX_ENV_SIZE], a texel outside the map, a NULL array with n > 0, n < 0. */
+int mfx_env_sample_direction(int32_t size, int64_t n, const uint32_t* texel, const double* jitter, double* out);
 
 /* ---- the reference's render API --------------------------------------------------------- */
 

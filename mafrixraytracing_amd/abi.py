@@ -31,6 +31,7 @@ MFX_MAX_LIGHTS = 64
 MFX_MAX_TEXTURES = 4096
 MFX_MAX_TEXTURE_DIM = 16384
 MFX_MAX_ENV_SIZE = 4096
+MFX_MAX_SKY_LIGHTS = 63
 MFX_DN_SRC_HOST = 0
 MFX_DN_SRC_ACCUM = 1
 MFX_DN_SRC_ADAPTIVE = 2
@@ -301,6 +302,36 @@ def env_texel_index(dirs, size: int) -> np.ndarray:
     return out[:len(d)]
 
 
+def env_sample_table(env):
+    """Host-only: the sampling table mfx_set_environment_sampled builds from the map env ((S, S, 3) float32):
+    (q float32 (n,), alias uint32 (n,), prob float64 (n,)), n = S * S (mfx_env_sample_table)."""
+    lib = load_library()
+    e, keep = environment_struct(env)
+    n = int(e.size) * int(e.size)
+    q = np.zeros(n, dtype=np.float32)
+    alias = np.zeros(n, dtype=np.uint32)
+    prob = np.zeros(n, dtype=np.float64)
+    check(lib.mfx_env_sample_table(C.byref(e), q.ctypes.data_as(C.POINTER(C.c_float)),
+                                   alias.ctypes.data_as(C.POINTER(C.c_uint32)), dptr(prob)), "mfx_env_sample_table")
+    del keep
+    return q, alias, prob
+
+
+def env_sample_direction(size: int, texel, jitter) -> np.ndarray:
+    """Host-only: the direction rule of a sampled sky by the code the kernels compile: for texel (n,) and jitter
+    (n, 2) = (ju, jv), (n, 4) = the unit direction and len2 * len (mfx_env_sample_direction;
+    environment.sample_direction is the Python statement of the same)."""
+    lib = load_library()
+    t = np.ascontiguousarray(texel, dtype=np.uint32).reshape(-1)
+    j = np.ascontiguousarray(jitter, dtype=np.float64).reshape(-1, 2)
+    if len(j) != len(t):
+        raise ValueError("env_sample_direction: one (ju, jv) per texel")
+    out = np.zeros((max(1, len(t)), 4), dtype=np.float64)
+    check(lib.mfx_env_sample_direction(int(size), len(t), t.ctypes.data_as(C.POINTER(C.c_uint32)), dptr(j), dptr(out)),
+          "mfx_env_sample_direction")
+    return out[:len(t)]
+
+
 _P = C.POINTER
 _dp = _P(C.c_double)
 _ip = _P(C.c_int32)
@@ -339,6 +370,10 @@ def _bind(lib, strict: bool = True):
         "mfx_set_environment": (C.c_int, [C.c_void_p, _P(MfxEnvironment)]),
         "mfx_environment_info": (C.c_int, [C.c_void_p, _dp]),
         "mfx_env_texel_index": (C.c_int, [C.c_int32, C.c_int64, _dp, _P(C.c_uint32)]),
+        "mfx_set_environment_sampled": (C.c_int, [C.c_void_p, _P(MfxEnvironment)]),
+        "mfx_sky_sampling_info": (C.c_int, [C.c_void_p, _dp]),
+        "mfx_env_sample_table": (C.c_int, [_P(MfxEnvironment), _P(C.c_float), _P(C.c_uint32), _dp]),
+        "mfx_env_sample_direction": (C.c_int, [C.c_int32, C.c_int64, _P(C.c_uint32), _dp, _dp]),
         "mfx_render_rgba8": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint8)]),
         "mfx_accumulate_render_rgba8": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint8)]),
         "mfx_stats": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -381,7 +416,7 @@ def _bind(lib, strict: bool = True):
 
 
 EXPORTED_SYMBOLS = [
-    "mfx_create", "mfx_create_instanced", "mfx_create_lights", "mfx_light_info", "mfx_light_table", "mfx_create_textured", "mfx_texture_info", "mfx_uv_table", "mfx_texel_index", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_sample_adaptive_resume", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_temporal", "mfx_pinhole_derive", "mfx_camera_info", "mfx_set_camera", "mfx_set_environment", "mfx_environment_info", "mfx_env_texel_index", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
+    "mfx_create", "mfx_create_instanced", "mfx_create_lights", "mfx_light_info", "mfx_light_table", "mfx_create_textured", "mfx_texture_info", "mfx_uv_table", "mfx_texel_index", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_sample_adaptive_resume", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_temporal", "mfx_pinhole_derive", "mfx_camera_info", "mfx_set_camera", "mfx_set_environment", "mfx_environment_info", "mfx_env_texel_index", "mfx_set_environment_sampled", "mfx_sky_sampling_info", "mfx_env_sample_table", "mfx_env_sample_direction", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
     "mfx_film_mean", "mfx_stats",
     "mfx_trace_accumulate", "mfx_accum_clear", "mfx_accum_reduce", "mfx_accum_device_ptr", "mfx_accum_attach", "mfx_accum_read_mean",
     "mfx_sync", "mfx_stream", "mfx_ray_counts", "mfx_last_trace_ms", "mfx_trace_timing", "mfx_ray_counts_total", "mfx_closest_hit", "mfx_any_hit", "mfx_ref_leaves",

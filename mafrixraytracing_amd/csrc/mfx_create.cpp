@@ -112,7 +112,7 @@ static int texture_upload(mfx_ctx* c) {
 
 WfLdsShape mfxh::wf_lds_shape(const SceneImages& im, bool textured, bool shd, int nlds, int ntop, int nslot) {
     const WfLdsShape s{shd, nlds < im.stack_size, im.d_nodes_h != nullptr, nlds, ntop, (int)im.host.inst.size(), nslot,
-                       shd && im.multi_light(), shd && textured};
+                       shd && im.multi_light(), shd && textured, false, shd && im.sky_light};
     return s;
 }
 
@@ -274,6 +274,17 @@ static int ctx_setup(mfx_ctx* c) {
     CK(hipMemset(c->d_film, 0, 3 * plane));
     CK(hipMemset(c->d_counters, 0, kCounterBytes));
     return scene_shapes(c->scene, c->device, env, wf_textured(c), c->cuts.on);
+}
+
+// mfx_set_environment(_sampled) made the sky a light of c's images or took it away (set_sky_light): the light
+// and the light table in HBM with their new pdf_n, and the launch shapes of the k_shadow instance that runs now.
+// On c's device, which is current; the context's work has finished.
+int mfxh::scene_relight(mfx_ctx* c) {
+    SceneImages& s = c->scene;
+    CK(upload(s.d_light, std::vector<MfxLight>{s.host.light}));
+    if (s.multi_light()) CK(upload(s.d_lights, s.host.lights));
+    else s.d_lights.reset();
+    return scene_shapes(s, c->device, c->env, wf_textured(c), c->cuts.on);
 }
 #undef CK
 
@@ -505,6 +516,7 @@ static int rebuild_for_camera(mfx_ctx* c, const mfx_pinhole* cam) {
     for (size_t g = 0; g < ds.size() && rc == MFX_OK; ++g) {
         const mfx_ctx* dv = ds[g];
         fresh[g].host = h;
+        set_sky_light(fresh[g], dv->scene.sky_light);  // (a sampled sky stays a light of the new images)
         rc = hipSetDevice(dv->device) == hipSuccess ? MFX_OK : fail(MFX_E_DEVICE, "mfx_set_camera: hipSetDevice failed");
         if (rc == MFX_OK) rc = scene_upload(fresh[g], dv->env);
         if (rc == MFX_OK) rc = scene_shapes(fresh[g], dv->device, dv->env, wf_textured(dv), dv->cuts.on);

@@ -356,6 +356,9 @@ struct Textures {
 struct Environment {
     DevBuf<float> d_rgb;             // [size * size][3] linear RGB radiance
     int32_t size = 0;                // 0: no environment
+    // the sky as a light (mfx_set_environment_sampled): the sampling table, one entry per texel (null: unsampled)
+    DevBuf<MfxSkyEntry> d_tab;
+    bool sampled = false;
     bool on() const { return size > 0; }
 };
 
@@ -395,10 +398,26 @@ struct SceneImages {
     DevBuf<int32_t> d_spill;     // deep traversal-stack entries [spill_deep][spill_lanes]
     int spill_deep = 0, spill_lanes = 0;
     DevBuf<double> d_vscratch;   // megakernel: per-lane vertex records [max_depth + 1][6][grid * 256]
-    // several lights (mfx_create_lights, N >= 2): the ML instances of k_shadow and k_resolve, the wavefront
-    // pipeline for every trace, a light-index plane in the pool
-    bool multi_light() const { return host.lights.size() >= 2; }
+    // the sky is a light of this context (mfx_set_environment_sampled): the pick is over N + 1, so the lights'
+    // pdf_n in `host` is (1 / area) / (N + 1) and one area light runs the several-light instances too. Set and
+    // cleared by set_sky_light, which mfx_set_camera's rebuild applies to the images it builds.
+    bool sky_light = false;
+    // several lights (mfx_create_lights, N >= 2; a sampled sky beside N >= 1): the ML instances of k_shadow and
+    // k_resolve, the wavefront pipeline for every trace, a light-index plane in the pool
+    bool multi_light() const { return host.lights.size() >= 2 || sky_light; }
 };
+
+// Makes the sky a light of the images `s` or takes it away again, on the host: pdf_n = (1 / area_n) / (N + on),
+// make_light's two divisions (mfx_scene.cpp). The caller uploads the lights and asks for the launch shapes again.
+inline void set_sky_light(SceneImages& s, bool on) {
+    s.sky_light = on;
+    const double np = (double)(s.host.lights.size() + (on ? 1 : 0));
+    for (MfxLight& L : s.host.lights) {
+        const double inv = 1. / L.area;
+        L.pdf = inv / np;
+    }
+    if (!s.host.lights.empty()) s.host.light.pdf = s.host.lights[0].pdf;
+}
 
 // Multi-device (primary context only)
 struct Multi {
@@ -506,12 +525,16 @@ inline bool wf_textured(const mfx_ctx* c) { return c->tex.host.on; }
 // a sky (mfx_set_environment): the ENV instances of k_extend, k_camera and k_resolve, the wavefront pipeline
 // for every trace, a miss-record word per slot in the pool
 inline bool wf_env(const mfx_ctx* c) { return c->sky.on(); }
+// a sampled sky (mfx_set_environment_sampled): the SKY instances of k_shadow and k_resolve, which are several-light
+// instances (wf_multi_light holds), the sampling table, a texel-id plane per vertex in the pool
+inline bool wf_sky_sampled(const mfx_ctx* c) { return c->sky.on() && c->sky.sampled; }
 
 // bytes of one path slot of the wavefront pool (ray queues included)
 inline size_t pool_slot_bytes(const mfx_ctx* c) {
     const int nv = c->scene.host.max_depth + 1;  // vertices per path
     return WF_DOUBLES_PER_SLOT(nv) * 8 + WF_WORDS_PER_SLOT(nv) * 4 + (wf_multi_light(c) ? WF_LIGHT_BYTES_PER_SLOT(nv) : 0) +
-           (wf_textured(c) ? WF_TEXEL_BYTES_PER_SLOT(nv) : 0) + (wf_env(c) ? WF_ENV_BYTES_PER_SLOT : 0);
+           (wf_textured(c) ? WF_TEXEL_BYTES_PER_SLOT(nv) : 0) + (wf_env(c) ? WF_ENV_BYTES_PER_SLOT : 0) +
+           (wf_sky_sampled(c) ? WF_SKY_BYTES_PER_SLOT(nv) : 0);
 }
 
 // the scene images' device pointers of a kernel parameter struct (WfParams, TraceParams, AovParams, QueryParams)
@@ -540,6 +563,8 @@ inline bool wf_lit_in_hit(const mfx_ctx* c) {
 }
 
 // mfx_create.cpp
+// after set_sky_light on c's images: the lights in HBM again and the launch shapes of the instances that run now
+int scene_relight(mfx_ctx* c);
 // the LDS shape of k_extend or (shd) k_shadow over the scene images `s` of a context (textured: wf_textured) with
 // nlds stack entries per lane in LDS (the rest spilled), and ntop top nodes and nslot slots beside them
 WfLdsShape wf_lds_shape(const SceneImages& s, bool textured, bool shd, int nlds, int ntop = 0, int nslot = 0);

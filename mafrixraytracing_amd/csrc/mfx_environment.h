@@ -46,4 +46,47 @@ MFX_ENV_HD uint32_t mfx_env_texel(double dx, double dy, double dz, int size) {
     return (uint32_t)(yi * size + xi);
 }
 
+// ---- the sky as a light (mfx_set_environment_sampled): the sampling table and the direction rule -----------
+// One entry per texel, 16 B: the alias pair of entry k (q, alias) and the probability prob of texel k that the
+// whole table implies. A sky vertex reads entry k for its pick and entry t for its pdf.
+struct MfxSkyEntry {
+    float q;         // in [0, 1]: draw r2 < q returns k, otherwise alias
+    uint32_t alias;
+    double prob;     // (q_t + sum over k != t with alias[k] == t of (1 - q_k)) / n, in increasing k
+};
+static_assert(sizeof(MfxSkyEntry) == 16, "MfxSkyEntry: 16 B a texel");
+
+// the extension ray's far bound (Integrators.fs:108): the sky's shadow query ends there too
+#define MFX_ENV_FAR 99999999.
+
+// The direction of (texel t, jitter ju, jv) in a size x size map, the inverse of mfx_env_texel: out = the unit
+// direction, len2 and len of the unnormalised point (the pdf's Jacobian factor is len2 * len).
+MFX_ENV_HD void mfx_env_sample_dir(uint32_t t, double ju, double jv, int size, double out[3], double& len2, double& len) {
+    const int xi = (int)(t % (uint32_t)size), yi = (int)(t / (uint32_t)size);
+    const double u = ((double)xi + ju) / (double)size, a = u * 2.0 - 1.0;
+    const double v = ((double)yi + jv) / (double)size, b = v * 2.0 - 1.0;
+    const double py = (1.0 - fabs(a)) - fabs(b);
+    double px = a, pz = b;
+    if (!((fabs(a) + fabs(b)) <= 1.0)) {
+        px = (1.0 - fabs(b)) * mfx_env_sg(a);
+        pz = (1.0 - fabs(a)) * mfx_env_sg(b);
+    }
+    len2 = (px * px + py * py) + pz * pz;
+    len = sqrt(len2);
+    out[0] = px / len;
+    out[1] = py / len;
+    out[2] = pz / len;
+}
+
+// the entry index of draw r1 among n entries: floor(r1 * n) clamped into [0, n - 1]
+MFX_ENV_HD uint32_t mfx_env_sample_entry(double r1, uint32_t n) {
+    const double f = floor(r1 * (double)n);
+    return !(f >= 0.0) ? 0u : (f >= (double)n ? n - 1u : (uint32_t)f);
+}
+
+// pdf_v of a sky vertex: (((prob * n) * 0.25) * (len2 * len)) / (N + 1)
+MFX_ENV_HD double mfx_env_sample_pdf(double prob, int size, double len2, double len, int nlights) {
+    return (((prob * (double)(size * size)) * 0.25) * (len2 * len)) / (double)(nlights + 1);
+}
+
 #endif

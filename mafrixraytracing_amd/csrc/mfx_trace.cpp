@@ -62,6 +62,7 @@ static int wf_ensure_pool(mfx_ctx* c, int32_t pool, bool queues) {
     A.vmat = (WfMat*)take(P * sizeof(WfMat) * nv);
     A.vlt = wf_multi_light(c) ? (uint8_t*)take(P * WF_LIGHT_BYTES_PER_SLOT(nv)) : nullptr;  // (in pool_slot_bytes)
     A.vtex = wf_textured(c) ? (uint32_t*)take(P * WF_TEXEL_BYTES_PER_SLOT(nv)) : nullptr;  // (in pool_slot_bytes)
+    A.vsky = wf_sky_sampled(c) ? (uint32_t*)take(P * WF_SKY_BYTES_PER_SLOT(nv)) : nullptr;  // (in pool_slot_bytes)
     // a sky: the slots' miss records, all "none" from here on (k_resolve puts the value back where it reads a miss)
     A.env_rec = wf_env(c) ? (uint32_t*)take(P * WF_ENV_BYTES_PER_SLOT) : nullptr;  // (in pool_slot_bytes)
     if (A.env_rec) {
@@ -165,6 +166,8 @@ static void fill_scene_params(mfx_ctx* c, WfParams& P) {
     // a sky: the ENV instances' map (env_rec set, by wf_ensure_pool: the launchers run them)
     P.env_rgb = wf_env(c) ? c->sky.d_rgb.get() : nullptr;
     P.env_size = c->sky.size;
+    // a sampled sky: the SKY instances' table (vsky set, by wf_ensure_pool; the lights above are the N area lights)
+    P.sky_tab = wf_sky_sampled(c) ? c->sky.d_tab.get() : nullptr;
     P.cam_dev = c->scene.d_cam;
     P.refs_dev = c->scene.d_refs;
     P.gray_light = wf_gray_light(c);

@@ -221,6 +221,14 @@ struct WfParams {
     const float* env_rgb;    // [size * size][3] linear RGB radiance
     uint32_t* env_rec;       // [pool slot] the miss record (in the pool; allocated with an environment only)
     int32_t env_size;
+    // The sky as a light (mfx_set_environment_sampled; otherwise null, null, and none of the instances without
+    // reads them). With env_rgb and env_rec set as above it runs the SKY instances of k_shadow and k_resolve, which
+    // are ML instances: lights and vlt are set with nlights = N >= 1 area lights, the pick is over N + 1, and the
+    // vertex whose pick is N draws a texel from sky_tab, stores its id in vsky and its cs and pdf_v where cs and
+    // solid go. k_extend's and k_camera's ENV twins run the generation's first iteration alone (the camera rays),
+    // the plain instances the bounces, so env_rec holds camera-ray misses only.
+    const MfxSkyEntry* sky_tab;  // [size * size] the sampling table
+    uint32_t* vsky;              // [vertex][stride] a sky vertex's texel id (beside vtex; allocated with a sampled sky only)
 };
 #define WF_MAX_LIGHTS 64  // MFX_MAX_LIGHTS: a light index is 6 bits of k_shadow's pending flag word
 
@@ -265,6 +273,8 @@ hipError_t mfx_wf_tile_check(const TileCheckParams& C, hipStream_t st);
 #define WF_TEXEL_BYTES_PER_SLOT(nvert) (4 * (nvert))
 // the sky: one word per slot, the miss record (WfParams::env_rec)
 #define WF_ENV_BYTES_PER_SLOT 4
+// the sky as a light: four bytes per vertex more, the sky vertices' texel ids (WfParams::vsky)
+#define WF_SKY_BYTES_PER_SLOT(nvert) (4 * (nvert))
 
 #ifndef WF_STACK_LDS
 #define WF_STACK_LDS 16  // traversal stack entries per lane kept in LDS (deeper ones spill to HBM/L2)
@@ -291,12 +301,13 @@ struct WfLdsShape {
     bool ml;        // k_shadow's several-light instance (WfParams::lights set; the same LDS footprint)
     bool tx;        // k_shadow's textured instance (WfParams::vtex set; its table pointers take 32 B of LDS more)
     bool env;       // k_extend's ENV instance (WfParams::env_rec set; the same LDS footprint)
+    bool sky;       // k_shadow's SKY twin of the ml instance (WfParams::sky_tab set; the same LDS footprint)
 };
 // resident blocks per CU of the kernel instance that holds shape s
 hipError_t mfx_wf_kernel_occupancy(const WfLdsShape& s, int* blocks_per_cu);
 // resident blocks per CU of k_resolve's accumulator instance (ml: the several-light one, tx: the textured one)
-// (env: the ENV one)
-hipError_t mfx_wf_resolve_occupancy(bool ml, int* blocks_per_cu, bool tx = false, bool env = false);
+// (env: the ENV one; sky: the SKY twin of the ml, env one)
+hipError_t mfx_wf_resolve_occupancy(bool ml, int* blocks_per_cu, bool tx = false, bool env = false, bool sky = false);
 // resident blocks per CU of k_camera (camera-ray packets; cuts: its CUTS instance)
 hipError_t mfx_cam_occupancy(int stack_size, int* blocks_per_cu, bool cuts = false);
 // a ray queue's arrays (MFX_RAY_QUEUE): entries in the pool's shard ranges, counts per shard

@@ -487,6 +487,7 @@ struct VertexSample {
     double ei, dist, cs, solid;
     bool lightable;
     int light;  // ML: the picked light
+    uint32_t texel;  // SKY: the sky vertex's texel (light == nlights)
 };
 // k_shadow's several-light instances keep these in the LDS block the one light's copy takes otherwise
 struct MlPtrs {
@@ -495,15 +496,28 @@ struct MlPtrs {
     int32_t nlights;
 };
 static_assert(sizeof(MlPtrs) <= sizeof(MfxLight), "MlPtrs lies in the light's LDS block: k_shadow's footprint stays");
+// the SKY instances' table and plane, in the same block after MlPtrs
+struct SkyPtrs {
+    MlPtrs ml;
+    const MfxSkyEntry* tab;
+    uint32_t* vsky;
+    int32_t size;
+};
+static_assert(sizeof(SkyPtrs) <= sizeof(MfxLight), "SkyPtrs lies in the light's LDS block: k_shadow's footprint stays");
 // LT1: the light (k_shadow's LDS copy).
 // ML: several lights (mfx_create_lights). After the hemisphere sample one more draw r picks light
 // n = floor(r * N) of the table `lights` (no clamp: r <= 1 - 2^-53, and (1 - 2^-53) * N rounds below N for
 // N <= 64); the lane reads that light's fields from global memory (lanes of a wave pick different
 // lights; the table is 208 B a light and stays in L1 / L2), and LT is not read.
-template <bool ML = false>
+// SKY (an ML instance; mfx_set_environment_sampled): the pick is over N + 1, always drawn. A lane whose pick is N
+// takes four more draws r1, r2, ju, jv, reads entry k = floor(r1 * n) of the sampling table for its texel t and
+// entry t for prob, and gets the direction of (t, ju, jv) (mfx_environment.h): unit, cs = unit . n, pdf_v in
+// `solid`, lightable iff cs > 0, dist = the extension ray's far bound. It reads no light.
+template <bool ML = false, bool SKY = false>
 __device__ __forceinline__ VertexSample sample_vertex(const MfxLight& LT1, bool own, DV hp, DV nm, uint64_t key,
                                                       uint32_t& rn, int* scratch, const MfxLight* lights = nullptr,
-                                                      int nlights = 1) {
+                                                      int nlights = 1, const MfxSkyEntry* sky_tab = nullptr,
+                                                      int sky_size = 0) {
     VertexSample V{};
 #if defined(MFX_DIAG_ONE_TRIAL)  // timing experiment only: the first trial, mirrored into the hemisphere
     DV p = dv(rng_next(key, rn) * 2.0 - 1.0, rng_next(key, rn) * 2.0 - 1.0, rng_next(key, rn) * 2.0 - 1.0);
@@ -516,7 +530,28 @@ __device__ __forceinline__ VertexSample sample_vertex(const MfxLight& LT1, bool 
     V.ei = vdot(nm, V.wi);
     if constexpr (ML) {  // the pick (RandomDirectLightIntegrator, Integrators.fs:62)
         const double r = rng_next(key, rn);
-        V.light = (int)floor(r * (double)nlights);
+        V.light = (int)floor(r * (double)(SKY ? nlights + 1 : nlights));
+    }
+    if constexpr (SKY) {
+        if (V.light >= nlights) {  // the sky
+            const double r1 = rng_next(key, rn);
+            const double r2 = rng_next(key, rn);
+            const double ju = rng_next(key, rn);
+            const double jv = rng_next(key, rn);
+            const uint32_t k = mfx_env_sample_entry(r1, (uint32_t)(sky_size * sky_size));
+            const MfxSkyEntry ek = sky_tab[k];
+            const uint32_t t = r2 < (double)ek.q ? k : ek.alias;
+            double u3[3], len2, len;
+            mfx_env_sample_dir(t, ju, jv, sky_size, u3, len2, len);
+            V.light = nlights;
+            V.texel = t;
+            V.unit = dv(u3[0], u3[1], u3[2]);
+            V.dist = MFX_ENV_FAR;
+            V.cs = vdot(V.unit, nm);
+            V.solid = mfx_env_sample_pdf(sky_tab[t].prob, sky_size, len2, len, nlights);
+            V.lightable = V.cs > 0.0;
+            return V;
+        }
     }
     const MfxLight& LT = ML ? lights[V.light] : LT1;
     const double sel = rng_next(key, rn);
@@ -966,8 +1001,13 @@ struct ShdPtrs {
 // hit point (mfx_texture.h) and stores it in P.vtex beside the vertex's material, all before the sampler
 // runs, so the record is dead by then; an untextured primitive stores MFX_TEXEL_NONE. The table pointers
 // lie in 32 B of LDS after the scene references (TxShd). A template parameter for ML's reason.
+// SKY: the twins of the ML instances for a sampled sky (mfx_set_environment_sampled): the pick is over N + 1 and
+// the lane whose pick is N samples the map (sample_vertex), stores the texel's id in P.vsky at shading time,
+// sends its shadow ray to the extension ray's far bound, and records cs and pdf_v where cs and solid go and N
+// as the light index. The table, the plane and the map's size lie in the light's LDS block after MlPtrs
+// (SkyPtrs), so the LDS footprint is the ML instance's.
 template <bool STATS, bool SPILL, int WAVES, int SK, bool Q, int LIST = WF_LIST_NONE, int NF = MFX_NF_ANY, bool ML = false,
-          bool TX = false>
+          bool TX = false, bool SKY = false>
 __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
     constexpr bool INST = SK == WF_SK_INST, SLDS = SK == WF_SK_SLDS;
     extern __shared__ int lds_all[];
@@ -985,7 +1025,11 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
     // the light, after the four waves' shade lists (8-B aligned): copied before load_top_nodes' barrier
     MfxLight* light_lds = (MfxLight*)((int*)(red + 16) + 4 * 2 * WF_SHD_LIST);
     if constexpr (ML) {
-        if (threadIdx.x == 3) *(MlPtrs*)light_lds = MlPtrs{P.lights, P.vlt, P.nlights};
+        if constexpr (SKY) {
+            if (threadIdx.x == 3) *(SkyPtrs*)light_lds = SkyPtrs{MlPtrs{P.lights, P.vlt, P.nlights}, P.sky_tab, P.vsky, P.env_size};
+        } else {
+            if (threadIdx.x == 3) *(MlPtrs*)light_lds = MlPtrs{P.lights, P.vlt, P.nlights};
+        }
     } else {
         if (threadIdx.x < sizeof(MfxLight) / 8)
             ((double*)light_lds)[threadIdx.x] = ((const double*)P.light_dev)[threadIdx.x];
@@ -1028,6 +1072,7 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
     if (SLDS) load_slots_lds(slot_lds, P.slots, nslot);
     const MfxLight& LT = *light_lds;
     [[maybe_unused]] const MlPtrs& M = *(const MlPtrs*)light_lds;  // ML: the same block holds these instead
+    [[maybe_unused]] const SkyPtrs& K = *(const SkyPtrs*)light_lds;  // SKY: and these after them
     // the pool's and the queues' array pointers, read from LDS where they are used (the shading batch,
     // the records) instead of held in scalar registers through the traversal loop
     const ShdPtrs& C = *(const ShdPtrs*)(light_lds + 1);
@@ -1164,7 +1209,8 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
                     }
                 }
                 wave_lds_sync();  // every owner has read its shl entries: shl[0, 64) is the sampler's scratch
-                const VertexSample V = sample_vertex<ML>(LT, own, hp, nm, key, rn, shl, ML ? M.lights : nullptr, ML ? M.nlights : 1);
+                const VertexSample V = sample_vertex<ML, SKY>(LT, own, hp, nm, key, rn, shl, ML ? M.lights : nullptr, ML ? M.nlights : 1,
+                                                              SKY ? K.tab : nullptr, SKY ? K.size : 0);
                 if (own) {
                     const DV wi = V.wi, unit = V.unit;
                     const double dist = V.dist, cs = V.cs, solid = V.solid;
@@ -1187,7 +1233,13 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
                     pd.slot[lane] = (Q && cn && C.ncount) ? qi : j;
                     pd.flag[lane] = (cn ? 1 : 0) | (lightable ? 2 : 0) | (v << 2) | (dw & ~0xff) | (ML ? V.light << 24 : 0);
                     pd.v[0 * 64 + lane] = unit.x; pd.v[1 * 64 + lane] = unit.y; pd.v[2 * 64 + lane] = unit.z;
-                    pd.v[3 * 64 + lane] = dist - 1e-6;
+                    if constexpr (SKY) {  // a sky vertex: its texel, and the query runs to the far bound itself
+                        const bool sv = V.light == M.nlights;
+                        if (sv) K.vsky[(int64_t)v * P.vstride + jr] = V.texel;
+                        pd.v[3 * 64 + lane] = sv ? MFX_ENV_FAR : dist - 1e-6;
+                    } else {
+                        pd.v[3 * 64 + lane] = dist - 1e-6;
+                    }
                     // a gray light: the direct term itself, (cs * (solid * I)) / pdf_li (Integrators.fs:52,
                     // Light.fs:52-53), the expression k_resolve evaluates per channel otherwise
                     // (ML: never gray; k_resolve has every light's intensity and pdf)
@@ -1338,6 +1390,7 @@ struct PathRec {
     int mat[WF_RES_VERTS];
     int lt[WF_RES_VERTS];  // ML: a lit vertex's light (P.vlt); the one-light instances never touch it
     uint32_t tx[WF_RES_VERTS];  // TX: the vertex's texel (MFX_TEXEL_NONE: untextured); the untextured instances never touch it
+    uint32_t sky[WF_RES_VERTS];  // SKY: a lit vertex's sky texel id (P.vsky; read only where lt is N); the others never touch it
 };
 // TX: the vertex's texel, gathered through its id (P.vtex); MFX_TEXEL_NONE stands for an untextured vertex
 __device__ __forceinline__ uint32_t load_texel(const WfParams& P, int64_t at) {
@@ -1346,7 +1399,7 @@ __device__ __forceinline__ uint32_t load_texel(const WfParams& P, int64_t at) {
 }
 // ENV: the records up to vertex etop (a path that ended in the sky folds every vertex before its miss, the
 // unlit ones above its deepest lit one too; etop < 0: no vertex); without, up to the deepest lit vertex
-template <bool ML, bool TX, bool ENV = false>
+template <bool ML, bool TX, bool ENV = false, bool SKY = false>
 __device__ __forceinline__ void load_path(const WfParams& P, int64_t j, int mask, PathRec& R, int etop = -1) {
     R.mask = mask;
     if (ENV ? etop < 0 : mask == 0) return;
@@ -1356,6 +1409,7 @@ __device__ __forceinline__ void load_path(const WfParams& P, int64_t j, int mask
         R.ei[v] = 0.0; R.cs[v] = 0.0; R.so[v] = 0.0; R.mat[v] = 0;
         if constexpr (ML) R.lt[v] = 0;
         if constexpr (TX) R.tx[v] = MFX_TEXEL_NONE;
+        if constexpr (SKY) R.sky[v] = 0;
         if (v <= top) {
             R.ei[v] = P.vei[v * P.vstride + j];
             R.mat[v] = P.vmat[v * P.vstride + j];
@@ -1365,6 +1419,8 @@ __device__ __forceinline__ void load_path(const WfParams& P, int64_t j, int mask
                 R.cs[v] = vl[0];  // (a gray light: a_v itself)
                 if (ML || !P.gray_light) R.so[v] = vl[P.vstride];
                 if constexpr (ML) R.lt[v] = P.vlt[v * P.vstride + j] & (WF_MAX_LIGHTS - 1);  // (the mask keeps the LDS read in bounds)
+                // (the id k_shadow stored if this is a sky vertex; masked: the map read stays in bounds whatever the word)
+                if constexpr (SKY) R.sky[v] = P.vsky[v * P.vstride + j] & MFX_ENV_ID_MASK;
             }
         }
     }
@@ -1379,10 +1435,12 @@ __device__ __forceinline__ void load_path(const WfParams& P, int64_t j, int mask
 // TX (albedo textures): the albedo is the material's times the vertex's texel, a[c] = al[c] * (byte_c / 255.0)
 // (mfx_texture.h); a texel whose three bytes are 255, MFX_TEXEL_NONE among them, leaves it as it is, which
 // is what the product gives (byte / 255.0 is exactly 1.0).
-template <bool ML, bool TX>
+// SKY (a sampled sky): a lit vertex whose light is N, the sky, takes the radiance of texel `sky` of the map and
+// pdf_v from `so`: a_v = ((cs * E[c]) * INVPI) / pdf_v.
+template <bool ML, bool TX, bool SKY = false>
 __device__ __forceinline__ void fold_vertex(const WfParams& P, bool lit, double ei, int mat, double cs, double so,
                                             const double* alb_lds, double& fx, double& fy, double& fz,
-                                            const double* lt_lds, int lt, uint32_t texel) {
+                                            const double* lt_lds, int lt, uint32_t texel, uint32_t sky = 0) {
     [[maybe_unused]] const MfxLight& LT = P.light;
     const double* al = mat < WF_RES_MAT_LDS ? alb_lds + 3 * mat : P.albedo + 3 * mat;
     double a0 = al[0], a1 = al[1], a2 = al[2];
@@ -1398,7 +1456,13 @@ __device__ __forceinline__ void fold_vertex(const WfParams& P, bool lit, double 
     const double cz = TWOPI * (ei * (INVPI * a2));
     double ax = 0.0, ay = 0.0, az = 0.0;
     if constexpr (ML) {
-        if (lit) {
+        if (SKY && lit && lt == P.nlights) {
+            const uint32_t n = (uint32_t)P.env_size * (uint32_t)P.env_size;
+            const float* e = P.env_rgb + 3 * (size_t)(sky < n ? sky : 0);
+            ax = ((cs * (double)e[0]) * INVPI) / so;
+            ay = ((cs * (double)e[1]) * INVPI) / so;
+            az = ((cs * (double)e[2]) * INVPI) / so;
+        } else if (lit) {
             const double* L = lt_lds + 4 * lt;
             ax = (cs * (so * L[0])) / L[3];
             ay = (cs * (so * L[1])) / L[3];
@@ -1415,7 +1479,7 @@ __device__ __forceinline__ void fold_vertex(const WfParams& P, bool lit, double 
     fy = (ay + fy) * cy;
     fz = (az + fz) * cz;
 }
-template <bool ML, bool TX, bool ENV = false>
+template <bool ML, bool TX, bool ENV = false, bool SKY = false>
 __device__ __forceinline__ void fold_path(const WfParams& P, int64_t j, const PathRec& R, const double* alb_lds,
                                           double& fx, double& fy, double& fz, const double* lt_lds, int etop = -1) {
     const int top = ENV ? etop : 31 - __builtin_clz(R.mask);  // (ENV: f comes in as the sky's radiance, or black)
@@ -1425,16 +1489,17 @@ __device__ __forceinline__ void fold_path(const WfParams& P, int64_t j, const Pa
         const double* vl = P.vls + (int64_t)(2 * v) * P.vstride + j;
         uint32_t texel = MFX_TEXEL_NONE;
         if constexpr (TX) texel = load_texel(P, v * P.vstride + j);
-        fold_vertex<ML, TX>(P, lit, P.vei[v * P.vstride + j], P.vmat[v * P.vstride + j], lit ? vl[0] : 0.0,
-                            lit ? vl[P.vstride] : 0.0, alb_lds, fx, fy, fz, lt_lds,
-                            (ML && lit) ? P.vlt[v * P.vstride + j] & (WF_MAX_LIGHTS - 1) : 0, texel);
+        fold_vertex<ML, TX, SKY>(P, lit, P.vei[v * P.vstride + j], P.vmat[v * P.vstride + j], lit ? vl[0] : 0.0,
+                                 lit ? vl[P.vstride] : 0.0, alb_lds, fx, fy, fz, lt_lds,
+                                 (ML && lit) ? P.vlt[v * P.vstride + j] & (WF_MAX_LIGHTS - 1) : 0, texel,
+                                 (SKY && lit) ? P.vsky[v * P.vstride + j] & MFX_ENV_ID_MASK : 0);
     }
     // the batched ones, indices known at compile time (the records stay in registers)
 #pragma unroll
     for (int v = WF_RES_VERTS - 1; v >= 0; --v)
         if (v <= top)
-            fold_vertex<ML, TX>(P, (R.mask >> v) & 1, R.ei[v], R.mat[v], R.cs[v], R.so[v], alb_lds, fx, fy, fz, lt_lds,
-                                ML ? R.lt[v] : 0, TX ? R.tx[v] : MFX_TEXEL_NONE);
+            fold_vertex<ML, TX, SKY>(P, (R.mask >> v) & 1, R.ei[v], R.mat[v], R.cs[v], R.so[v], alb_lds, fx, fy, fz, lt_lds,
+                                     ML ? R.lt[v] : 0, TX ? R.tx[v] : MFX_TEXEL_NONE, SKY ? R.sky[v] : 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1473,7 +1538,11 @@ __device__ __forceinline__ void fold_path(const WfParams& P, int64_t j, const Pa
 // exactly, and covers vertices nv - 1 .. 0 (none for a camera ray's miss: the texel itself, the background),
 // and the record goes back to MFX_ENV_NONE. Such a path adds to its pixel whatever its lit mask; a path
 // that ended by depth alone is as without.
-template <int MODE, bool ML = false, bool TX = false, bool ENV = false>
+// SKY: the twins of the ML, ENV instances for a sampled sky: a lit vertex whose light index is N takes the
+// radiance of the texel k_shadow<SKY> stored (P.vsky) and its pdf_v (fold_vertex). The miss records are as under
+// ENV; the launcher runs the ENV twins of k_extend and k_camera for the camera rays alone, so every record is a
+// camera ray's (nv = 0), and one with nv >= 1 is not honoured: cleared, the path as without.
+template <int MODE, bool ML = false, bool TX = false, bool ENV = false, bool SKY = false>
 __global__ void __launch_bounds__(256) k_resolve(WfParams P) {
     constexpr bool FRAMES = MODE == WF_RES_FRAMES, MOM = MODE == WF_RES_MOMENTS;
     __shared__ double alb[3 * WF_RES_MAT_LDS];
@@ -1548,6 +1617,12 @@ __global__ void __launch_bounds__(256) k_resolve(WfParams P) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 ew[u] = in[u] ? P.env_rec[jv[u]] : MFX_ENV_NONE;
+                if constexpr (SKY) {
+                    if (ew[u] != MFX_ENV_NONE && (ew[u] >> MFX_ENV_NV_SHIFT) != 0) {
+                        P.env_rec[jv[u]] = MFX_ENV_NONE;
+                        ew[u] = MFX_ENV_NONE;
+                    }
+                }
                 etop[u] = ew[u] != MFX_ENV_NONE ? (int)(ew[u] >> MFX_ENV_NV_SHIFT) - 1
                                                 : (mask[u] ? 31 - __builtin_clz(mask[u]) : -1);
             }
@@ -1555,7 +1630,7 @@ __global__ void __launch_bounds__(256) k_resolve(WfParams P) {
         PathRec R[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            if constexpr (ENV) load_path<ML, TX, true>(P, jv[u], mask[u], R[u], etop[u]);
+            if constexpr (ENV) load_path<ML, TX, true, SKY>(P, jv[u], mask[u], R[u], etop[u]);
             else load_path<ML, TX>(P, jv[u], mask[u], R[u]);
         }
 #pragma unroll
@@ -1570,7 +1645,7 @@ __global__ void __launch_bounds__(256) k_resolve(WfParams P) {
                     fz = (double)e[2];
                     P.env_rec[jv[u]] = MFX_ENV_NONE;
                 }
-                if (etop[u] >= 0) fold_path<ML, TX, true>(P, jv[u], R[u], alb, fx, fy, fz, lt_lds, etop[u]);
+                if (etop[u] >= 0) fold_path<ML, TX, true, SKY>(P, jv[u], R[u], alb, fx, fy, fz, lt_lds, etop[u]);
             } else if (R[u].mask) {
                 fold_path<ML, TX>(P, jv[u], R[u], alb, fx, fy, fz, lt_lds);
             }
@@ -1700,6 +1775,9 @@ static constexpr bool camera_built(const WfKey& k) {
 // chosen beside the key, as k_camera's CUTS twin is. k_shadow has none: shadow rays ignore the sky.)
 static constexpr bool extend_env_built(const WfKey& k) { return extend_built(k) && !k.stats; }
 static constexpr bool camera_env_built(const WfKey& k) { return camera_built(k) && !k.stats; }
+// (a sampled sky, SKY: k_shadow's twin of every several-light instance, textured or not; beside the key as ENV is.
+// k_extend and k_camera have none: their ENV twins run the camera rays, their plain instances the bounces.)
+static constexpr bool shadow_sky_built(const WfKey& k) { return shadow_built(k) && k.ml; }
 static constexpr int built_count(bool (*built)(const WfKey&)) {
     int n = 0;
     for (int i = 0; i < WF_KEYS; ++i) n += built(key_at(i));
@@ -1714,8 +1792,11 @@ static_assert(built_count(extend_built) == (MFX_NODE_F16 ? 64 : 60) &&
 static_assert(built_count(extend_env_built) == (MFX_NODE_F16 ? 34 : 30) && built_count(camera_env_built) == 3,
               "the sky's instances, ENV: the twin of every k_extend instance without counters, 34 / 30, and of every "
               "k_camera instance without counters in both CUTS states, 2 * 3; k_resolve's twelve have a twin each");
+static_assert(built_count(shadow_sky_built) == (MFX_NODE_F16 ? 2 * 40 : 2 * 36),
+              "the sampled sky's instances, SKY: the twin of every several-light k_shadow instance, untextured and "
+              "textured, 2 * 40 / 2 * 36; k_resolve's six ML, ENV instances have a twin each");
 
-enum { WF_K_EXTEND, WF_K_SHADOW, WF_K_CAMERA, WF_K_CAMERA_CUTS, WF_K_EXTEND_ENV, WF_K_CAMERA_ENV, WF_K_CAMERA_CUTS_ENV };
+enum { WF_K_EXTEND, WF_K_SHADOW, WF_K_CAMERA, WF_K_CAMERA_CUTS, WF_K_EXTEND_ENV, WF_K_CAMERA_ENV, WF_K_CAMERA_CUTS_ENV, WF_K_SHADOW_SKY };
 template <int KERNEL, int I>
 static const void* instance_at() {
     constexpr WfKey k = key_at(I);
@@ -1733,6 +1814,8 @@ static const void* instance_at() {
         return (const void*)k_camera<k.stats, k.list, false, true>;
     else if constexpr (KERNEL == WF_K_CAMERA_CUTS_ENV && camera_env_built(k))
         return (const void*)k_camera<k.stats, k.list, true, true>;
+    else if constexpr (KERNEL == WF_K_SHADOW_SKY && shadow_sky_built(k))
+        return (const void*)k_shadow<k.stats, k.spill, k.waves, k.sk, k.queue, k.list, k.nf, k.ml, k.tx, true>;
     else
         return nullptr;
 }
@@ -1746,7 +1829,11 @@ static const void* extend_kernel(const WfKey& k, bool env = false) {
     return env ? instance<WF_K_EXTEND_ENV>(k, std::make_index_sequence<WF_KEYS>{})
                : instance<WF_K_EXTEND>(k, std::make_index_sequence<WF_KEYS>{});
 }
-static const void* shadow_kernel(const WfKey& k) { return instance<WF_K_SHADOW>(k, std::make_index_sequence<WF_KEYS>{}); }
+// (sky: the SKY twin of a several-light key)
+static const void* shadow_kernel(const WfKey& k, bool sky = false) {
+    return sky ? instance<WF_K_SHADOW_SKY>(k, std::make_index_sequence<WF_KEYS>{})
+               : instance<WF_K_SHADOW>(k, std::make_index_sequence<WF_KEYS>{});
+}
 // (cuts: the twin that starts from the cut table, WfParams::cuts set; not a key field, k_camera alone has it)
 static const void* camera_kernel(const WfKey& k, bool cuts, bool env = false) {
     if (env)
@@ -1773,7 +1860,7 @@ hipError_t mfx_wf_kernel_occupancy(const WfLdsShape& s, int* blocks_per_cu) {
     if (!s.shadow && !wf_nf_fixed(k)) k.start = true;
     const size_t lds = wf_lds_bytes(s);
     const hipError_t e =
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, s.shadow ? shadow_kernel(k) : extend_kernel(k, s.env), 256, lds);
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, s.shadow ? shadow_kernel(k, s.sky) : extend_kernel(k, s.env), 256, lds);
     // (the API counts finer LDS granules than the hardware allocates: measured, k_shadow at 53,952 B per
     // block runs 2 blocks per CU where it says 3, a 10 % loss)
     *blocks_per_cu = std::min(*blocks_per_cu, mfx_lds_blocks(lds));
@@ -1800,21 +1887,23 @@ static WfLdsShape lds_shape(const WfParams& P, bool shadow) {
     const int stack_lds = shadow ? P.stack_lds_shd : P.stack_lds_ext;
     return {shadow, stack_lds < P.stack_size, wf_fp16(P), stack_lds, shadow ? P.ntop_shd : P.ntop_ext,
             P.inst ? P.ninst_lds : 0, shadow ? P.nslot_shd : P.nslot_ext, shadow && P.lights != nullptr,
-            shadow && P.vtex != nullptr, !shadow && P.env_rec != nullptr};
+            shadow && P.vtex != nullptr, !shadow && P.env_rec != nullptr, shadow && P.sky_tab != nullptr};
 }
 
 static hipError_t launch_iteration(const WfParams& P, int ext_grid, int shd_grid, bool stats, hipStream_t st,
                                    hipEvent_t* ev) {
     const int list = list_kind(P.ntiles, P.tile_n);
-    const bool env = P.env_rec != nullptr;  // a sky: the ENV twins of k_camera and k_extend
+    // a sky: the ENV twins of k_camera and k_extend; a sampled one: for the camera rays alone (the iteration that
+    // starts the generation's paths holds nothing else), the plain instances for the bounces
+    const bool env = P.env_rec != nullptr && (P.sky_tab == nullptr || P.start);
     if (!P.inst && P.start && P.cam_grid > 0) {  // camera rays as packets
         const void* cam = camera_kernel(camera_key(stats, list), P.cuts != nullptr, env);
         if (!cam) return hipErrorInvalidValue;  // (a sky with counters: refused by mfx_set_environment)
         launch(cam, P.cam_grid, cam_lds_bytes(P.stack_size), st, P);
     } else {
-        const WfLdsShape s = lds_shape(P, false);
-        const bool queue = P.qcount != nullptr, start = !queue && P.start;
-        const void* ext = extend_kernel(shape_key(s, stats, queue, start, start ? list : WF_LIST_NONE, 4), env);
+        WfLdsShape s = lds_shape(P, false);
+        s.env = env;
+        const bool queue = P.qcount != nullptr, start = !queue && P.start;        const void* ext = extend_kernel(shape_key(s, stats, queue, start, start ? list : WF_LIST_NONE, 4), env);
         if (!ext) return hipErrorInvalidValue;
         launch(ext, ext_grid, wf_lds_bytes(s), st, P);
     }
@@ -1824,7 +1913,7 @@ static hipError_t launch_iteration(const WfParams& P, int ext_grid, int shd_grid
     }
     const WfLdsShape s = lds_shape(P, true);
     const bool queue = P.qslot || P.ncount;
-    const void* shd = shadow_kernel(shape_key(s, stats, queue, false, list, shadow_build(P.shadow_waves)));
+    const void* shd = shadow_kernel(shape_key(s, stats, queue, false, list, shadow_build(P.shadow_waves)), s.sky);
     if (!shd) return hipErrorInvalidValue;  // (several lights or textures with counters or the 3-wave build: refused at creation)
     launch(shd, shd_grid, wf_lds_bytes(s), st, P);
     return hipSuccess;
@@ -1833,7 +1922,11 @@ static hipError_t launch_iteration(const WfParams& P, int ext_grid, int shd_grid
 hipError_t mfx_wf_iteration(const WfParams& P, int ext_grid, int shd_grid, bool stats, hipStream_t st,
                             hipEvent_t* ev) {
     // several lights: the table, its count and the index plane go together (k_shadow<ML> writes vlt)
-    if (P.lights && (!P.vlt || P.nlights < 2 || P.nlights > WF_MAX_LIGHTS || P.gray_light || stats)) return hipErrorInvalidValue;
+    // (a sampled sky is the light after them: one area light will do, 63 at most)
+    if (P.lights && (!P.vlt || P.nlights < (P.sky_tab ? 1 : 2) || P.nlights > WF_MAX_LIGHTS - (P.sky_tab ? 1 : 0) || P.gray_light || stats))
+        return hipErrorInvalidValue;
+    // a sampled sky: the table and the id plane go together, with the sky's map and the lights' table
+    if ((P.sky_tab != nullptr) != (P.vsky != nullptr) || (P.sky_tab && (!P.env_rec || !P.lights))) return hipErrorInvalidValue;
     // albedo textures: the id plane and the tables go together (k_shadow<TX> reads the tables and writes vtex)
     if (P.vtex && (!P.tx.uvrec || !P.tx.ptex || !P.tx.desc || !P.tx.texels || stats)) return hipErrorInvalidValue;
     // a sky: the record plane and the map go together (k_extend<ENV> / k_camera<ENV> write env_rec)
@@ -1859,7 +1952,10 @@ static const void* resolve_kernel_env(bool ml, bool tx) {
               : (tx ? (const void*)k_resolve<MODE, false, true, ENV> : (const void*)k_resolve<MODE, false, false, ENV>);
 }
 template <int MODE>
-static const void* resolve_kernel(bool ml, bool tx, bool env) {
+static const void* resolve_kernel(bool ml, bool tx, bool env, bool sky = false) {
+    if (sky)  // the SKY twin of the ML, ENV instance
+        return ml && env ? (tx ? (const void*)k_resolve<MODE, true, true, true, true> : (const void*)k_resolve<MODE, true, false, true, true>)
+                         : nullptr;
     return env ? resolve_kernel_env<MODE, true>(ml, tx) : resolve_kernel_env<MODE, false>(ml, tx);
 }
 static hipError_t launch_resolve(const void* kernel, int64_t threads, hipStream_t st, const WfParams& P) {
@@ -1871,21 +1967,25 @@ static hipError_t launch_resolve(const void* kernel, int64_t threads, hipStream_
 hipError_t mfx_wf_resolve(const WfParams& P, hipStream_t st) {
     const bool ml = P.lights != nullptr;  // several lights: the ML instance of each mode
     const bool tx = P.vtex != nullptr;    // albedo textures: the TX instance
-    if (ml && (!P.vlt || P.nlights < 2 || P.nlights > WF_MAX_LIGHTS || P.gray_light)) return hipErrorInvalidValue;
+    const bool sky = P.sky_tab != nullptr;  // a sampled sky: the SKY instance
+    if (ml && (!P.vlt || P.nlights < (sky ? 1 : 2) || P.nlights > WF_MAX_LIGHTS - (sky ? 1 : 0) || P.gray_light)) return hipErrorInvalidValue;
     if (tx && !P.tx.texels) return hipErrorInvalidValue;
+    if (sky && (!ml || !P.vsky || !P.env_rec)) return hipErrorInvalidValue;
     const bool env = P.env_rec != nullptr;  // a sky: the ENV instance
     if (env && (!P.env_rgb || P.env_size < 1 || P.env_size > MFX_ENV_SIZE_MAX)) return hipErrorInvalidValue;
     if (P.mom || P.ntiles > 0) {  // the adaptive sampler's passes: the moments instance (a listed trace runs no other)
         if (!P.mom || P.film || P.res_ntx > 0) return hipErrorInvalidValue;
         const int64_t n = P.ntiles > 0 ? (int64_t)P.ntiles * 64 : (int64_t)((P.width + 7) >> 3) * P.band_rows * 64;
-        return launch_resolve(resolve_kernel<WF_RES_MOMENTS>(ml, tx, env), n, st, P);
+        return launch_resolve(resolve_kernel<WF_RES_MOMENTS>(ml, tx, env, sky), n, st, P);
     }
     const int64_t per_sample = (int64_t)(P.res_ntx > 0 ? P.res_ntx : (P.width + 7) >> 3) * P.band_rows * 64;
-    return launch_resolve(P.film ? resolve_kernel<WF_RES_FRAMES>(ml, tx, env) : resolve_kernel<WF_RES_ACCUM>(ml, tx, env), per_sample, st, P);
+    return launch_resolve(P.film ? resolve_kernel<WF_RES_FRAMES>(ml, tx, env, sky) : resolve_kernel<WF_RES_ACCUM>(ml, tx, env, sky), per_sample, st, P);
 }
 
-hipError_t mfx_wf_resolve_occupancy(bool ml, int* blocks_per_cu, bool tx, bool env) {
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, resolve_kernel<WF_RES_ACCUM>(ml, tx, env), 256, 0);
+hipError_t mfx_wf_resolve_occupancy(bool ml, int* blocks_per_cu, bool tx, bool env, bool sky) {
+    const void* k = resolve_kernel<WF_RES_ACCUM>(ml, tx, env, sky);
+    if (!k) return hipErrorInvalidValue;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k, 256, 0);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""The sky (mfx_set_environment): a square octahedral map of linear RGB radiance that rays leaving the scene
+"""The sky (mfx_set_environment, mfx_set_environment_sampled): a square octahedral map of linear RGB radiance that rays leaving the scene
 return instead of black. The rule is the contract in include/mafrix_rt.h; `texel_index` states it in Python
 floats (IEEE doubles, one rounding per operation, in the order written), so it agrees bit for bit with
 csrc/mfx_environment.h, which the host and the gfx950 kernels compile. +y is the pole.
@@ -82,3 +82,50 @@ def from_latlong(image, size: int) -> np.ndarray:
     row = np.clip(np.floor(theta / math.pi * H).astype(np.int64), 0, H - 1)
     col = np.clip(np.floor((phi / (2.0 * math.pi) + 0.5) * W).astype(np.int64), 0, W - 1)
     return np.ascontiguousarray(img[row, col, :3], dtype=np.float32)
+
+
+# ---- the sky as a light (mfx_set_environment_sampled): the header's rule in Python floats -------------------
+INVPI = 1. / 3.141592653589793
+
+
+def sample_table(m):
+    """The sampling table the library builds from the map m: (q float32 (n,), alias uint32 (n,), prob float64
+    (n,)). The construction is the library's (mfx_env_sample_table); the rule takes the three arrays as data."""
+    from .abi import env_sample_table
+    return env_sample_table(m)
+
+
+def sample_entry(r1: float, n: int) -> int:
+    """Step 2's entry: floor(r1 * n) clamped into [0, n - 1]."""
+    return _coord(r1, n)
+
+
+def sample_direction(size: int, texel: int, ju: float, jv: float):
+    """Step 3: the direction of (texel, ju, jv) in a size x size map: ((ux, uy, uz), len2, len)."""
+    xi, yi = int(texel) % size, int(texel) // size
+    u = (float(xi) + ju) / float(size)
+    a = u * 2.0 - 1.0
+    v = (float(yi) + jv) / float(size)
+    b = v * 2.0 - 1.0
+    py = (1.0 - abs(a)) - abs(b)
+    if (abs(a) + abs(b)) <= 1.0:
+        px, pz = a, b
+    else:
+        px = (1.0 - abs(b)) * _sg(a)
+        pz = (1.0 - abs(a)) * _sg(b)
+    len2 = (px * px + py * py) + pz * pz
+    ln = math.sqrt(len2)
+    return (px / ln, py / ln, pz / ln), len2, ln
+
+
+def sample_pdf(prob_t: float, size: int, len2: float, ln: float, nlights: int) -> float:
+    """Step 5: pdf_v of a sky vertex of a context with nlights area lights."""
+    return (((prob_t * float(size * size)) * 0.25) * (len2 * ln)) / float(nlights + 1)
+
+
+def sun_map(size: int, sun_texel: int, sun, rest) -> np.ndarray:
+    """A size x size map of radiance `rest` (a value or three) with the one texel `sun_texel` at `sun`."""
+    m = np.empty((size, size, 3), dtype=np.float32)
+    m[:] = np.asarray(rest, dtype=np.float32)
+    m.reshape(-1, 3)[int(sun_texel)] = np.asarray(sun, dtype=np.float32)
+    return m

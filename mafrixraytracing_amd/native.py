@@ -27,7 +27,8 @@ class NativeContext:
     def __init__(self, arrays: SceneArrays, seed: int = DEFAULT_SEED, device: int = 0, flags: int = MFX_F_NONE,
                  part_index: int = 0, part_count: int = 1, devices: list[int] | None = None,
                  instancing: bool = True, render_ahead: int = 0, lights: list | None = None,
-                 textures: list | None = None, prim_uv: np.ndarray | None = None, environment=None):
+                 textures: list | None = None, prim_uv: np.ndarray | None = None, environment=None,
+                 sample_sky: bool = False):
         """devices: drive this list of HIP devices from one context (mfx_options.devices; the
         library's own RCCL reduce sums them into devices[0]); None: the single `device`.
         instancing: a scene with instancing data is created through mfx_create_instanced (two-level
@@ -44,7 +45,8 @@ class NativeContext:
         arrays.light. Pass arrays.textures and arrays.prim_uv for a scene loaded with textures=True. None:
         an untextured context, whatever arrays holds.
         environment: an (S, S, 3) float32 octahedral map of linear RGB radiance (environment.py makes them), set
-        with set_environment right after creation: rays that leave the scene return its texel. None: black."""
+        with set_environment right after creation: rays that leave the scene return its texel. None: black.
+        sample_sky: set it with mfx_set_environment_sampled instead: the sky is a light, sampled at every vertex."""
         self.lib = load_library()
         self.arrays = arrays
         self.w, self.h = arrays.width, arrays.height
@@ -88,7 +90,7 @@ class NativeContext:
         self._h = h
         if environment is not None:
             try:
-                self.set_environment(environment)
+                self.set_environment(environment, sampled=sample_sky)
             except Exception:
                 self.close()
                 raise
@@ -232,17 +234,29 @@ class NativeContext:
         p = pinhole_struct(camera)
         check(self.lib.mfx_set_camera(self._h, C.byref(p)), "mfx_set_camera")
 
-    def set_environment(self, environment):
+    def set_environment(self, environment, sampled: bool = False):
         """mfx_set_environment: make the (S, S, 3) float32 octahedral map `environment` (linear RGB radiance; a
         (3,) constant works too) the sky of every later call, or with None remove it. The texels are copied.
         The film, the accumulator, next_sample and the feature buffers are left as they are; sample_adaptive()
-        must run again before sample_adaptive_resume and the adaptive source of denoise_var."""
+        must run again before sample_adaptive_resume and the adaptive source of denoise_var.
+        sampled: mfx_set_environment_sampled: the sky becomes the (N+1)-th light of the pick and is sampled at
+        every path vertex in proportion to its radiance (at most 63 area lights beside it)."""
+        name = "mfx_set_environment_sampled" if sampled else "mfx_set_environment"
+        fn = getattr(self.lib, name)
         if environment is None:
-            check(self.lib.mfx_set_environment(self._h, None), "mfx_set_environment")
+            check(fn(self._h, None), name)
             return
         e, keep = environment_struct(environment)
-        check(self.lib.mfx_set_environment(self._h, C.byref(e)), "mfx_set_environment")
+        check(fn(self._h, C.byref(e)), name)
         del keep
+
+    def sky_sampling_info(self) -> np.ndarray:
+        """mfx_sky_sampling_info: [0] 1 if the sky is sampled, [1] N + 1, [2] bytes of the sampling table, [3] bytes
+        per path slot the sampling adds to the pool, [4] / [5] resident blocks per CU of the k_shadow / k_resolve
+        instance in use; [6], [7] 0. All 0 otherwise."""
+        out = np.zeros(8)
+        check(self.lib.mfx_sky_sampling_info(self._h, dptr(out)), "mfx_sky_sampling_info")
+        return out
 
     def environment_info(self) -> np.ndarray:
         """mfx_environment_info: [0] size, [1] 1 if the environment kernel instances run, [2] bytes of texels,
