@@ -502,6 +502,81 @@ int mfx_env_sample_table(const mfx_environment* env, float* q, uint32_t* alias, 
  * MFX_E_INVALID: a size outside [1, MFX_MAX_ENV_SIZE], a texel outside the map, a NULL array with n > 0, n < 0. */
 int mfx_env_sample_direction(int32_t size, int64_t n, const uint32_t* texel, const double* jitter, double* out);
 
+/* ---- the thin lens (ABI 6, additive; an extension: the reference's camera is PinholeCamera alone) ---------
+ * While a lens is set, every camera ray starts from a point of a disk around the camera position and passes
+ * through the point where the pinhole ray of the same (u, v) meets the focus plane: what lies in that plane is
+ * sharp, the rest is blurred by the disk. aperture is the lens radius in world units, focus the distance of the
+ * plane of sharp focus along the forward axis.
+ *
+ * Everything is FP64 with one rounding per operation in the order written and no contraction.
+ * dot(a,b) = (a0*b0 + a1*b1) + a2*b2.
+ *
+ * The lens record, on the host, when the lens is set or the camera changes. P0, TL, R, D are the derived
+ * camera's position, topleft, right and down (mfx_pinhole_derive):
+ *  1. lr = sqrt(dot(R,R)); ld = sqrt(dot(D,D));
+ *  2. U[c] = (R[c] / lr) * aperture; V[c] = (D[c] / ld) * aperture;
+ *  3. n = cross(R, D): n0 = R1*D2 - R2*D1, n1 = R2*D0 - R0*D2, n2 = R0*D1 - R1*D0;
+ *  4. ln = sqrt(dot(n,n)); f[c] = n[c] / ln, the forward axis (the constructor's direction, normalised);
+ *  5. dplane = dot(TL - P0, f) (0.5 for a constructed camera, up to rounding);
+ *  6. s = focus / dplane;
+ *  7. the record is U[3], V[3], s: seven doubles.
+ *
+ * A camera ray. Pixel, sample, key and u, v are as ever (the path's first two draws):
+ *  1. target = (TL + R*u) + D*v, the pinhole's expression; pin = target - P0;
+ *  2. the lens point comes from a stream of its own, so the path's stream does not move: draw m is
+ *     rng_unit(mix64(key + m * 0x9e3779b97f4a7c15)), as rng_next with counter m, and the lens uses counters
+ *     2^31 + 1, 2^31 + 2, ... of the path's own key. The path's counter goes on at 2 (a path's own counter
+ *     stays far below 2^31);
+ *  3. per trial: r1, r2 are the next two lens draws; a = r1*2.0 - 1.0; b = r2*2.0 - 1.0; the trial is accepted
+ *     iff (a*a + b*b) < 1.0 (rejection, as the reference's GetRandomInUnitSphere: no trigonometry);
+ *  4. o = (P0 + U*a) + V*b;
+ *  5. fp = P0 + pin*s;
+ *  6. d = normalize(fp - o), the camera ray's own normalisation (x / l, l = sqrt(x*x + y*y + z*z), 0 for l == 0);
+ *  7. Ray(o, d) is traced on [1e-6, 99999999.], as a camera ray is.
+ * Everything after the first hit is unchanged; under a sky a camera ray's miss records the texel of d.
+ * mfx_aov traces these rays too: its planes are the film's own rays', and plane [3] is t along the lens ray.  */
+typedef struct mfx_lens {
+    double aperture; /* the lens radius, world units; finite, >= 0; exactly 0: no lens */
+    double focus;    /* the distance of the focus plane along the forward axis; finite, > 0 */
+} mfx_lens; /* 16 bytes */
+
+/* Makes `lens` the lens of every later call, on every device of a device list; NULL, or an aperture of exactly
+ * 0, removes it, and the context is then the pinhole one again, kernel for kernel: the same mfx_launch_info,
+ * pool bytes, digest and images. It composes with every creation entry point and every sampling call. With a
+ * lens the context runs the LENS twin of the k_extend instance that starts a generation's paths (flat scenes
+ * too: no camera packets and no camera cuts, which rest on one shared origin) and of k_aov, and always the
+ * wavefront pipeline (one-sample calls included); k_shadow, k_resolve, the bounces and the pool are as without.
+ * Waits for the context's work first, as mfx_set_camera does.
+ * The widening: the traversal boxes' eps is sized by the magnitudes of ray origins, and lens origins lie off P0
+ * by up to |U| + |V| per axis. The eps needed is the largest over the eight corners of that box; if the images'
+ * eps covers it only the lens changes, otherwise the images are built again by creation's code for that corner
+ * (a failed rebuild leaves the old state in place). Images built for a lens are built again for the camera alone
+ * when the lens is removed. mfx_set_camera under a lens keeps aperture and focus, derives the record again and
+ * applies the same rule.
+ * What it invalidates: what mfx_set_camera invalidates (held render-ahead frames, the adaptive result, the
+ * feature buffers). What it leaves alone: the film, the accumulator, next_sample, the ray counters, the sky,
+ * the lights and the textures. mfx_temporal returns MFX_E_STATE under a lens (its reprojection is the
+ * pinhole's) and leaves the history as it is; mfx_denoise and mfx_denoise_var run unchanged on the lens features.
+ * MFX_E_INVALID, decided on the host before a device is touched, the message naming the field: an aperture
+ * that is not finite or negative; a focus that is not finite or not > 0; a camera for which lr, ld, ln or
+ * dplane is zero or not finite, or dplane <= 0; a non-finite s. MFX_E_STATE: a context created with
+ * MFX_F_MEGAKERNEL or MFX_F_COUNT_STATS. A refused call changes nothing.                                  */
+int mfx_set_lens(mfx_ctx* ctx, const mfx_lens* lens);
+/* out[0] = 1 with a lens, out[1] = aperture, out[2] = focus, out[3..5] = U, out[6..8] = V, out[9] = s,
+ * out[10] = the eps the lens camera needs, out[11] = the image rebuilds mfx_set_lens caused, out[12] / out[13] =
+ * resident blocks per CU of the k_extend instance that starts the paths / of the k_aov instance in use, the
+ * rest 0. All 0 without a lens.                                                                          */
+int mfx_lens_info(mfx_ctx* ctx, double out[16]);
+/* Host-only (no device needed), by the code the kernels compile: the record of `cam` under `lens`,
+ * out = U[3], V[3], s. The MFX_E_INVALID refusals of mfx_set_lens (an aperture of 0 is accepted: U = V = 0). */
+int mfx_lens_derive(const mfx_pinhole* cam, const mfx_lens* lens, double out[7]);
+/* Host-only: the camera rays of n paths, path i being sample sample[i] of pixel (px[i], py[i]) of a
+ * width x height film under `seed`: out[8i .. 8i+7] = o, d, a, b and trials[i] = the rejection trials it took.
+ * MFX_E_INVALID: mfx_lens_derive's refusals, a film size below 1, a pixel outside the film, a negative sample,
+ * n < 0, a NULL array with n > 0.                                                                        */
+int mfx_lens_rays(const mfx_pinhole* cam, const mfx_lens* lens, uint64_t seed, int32_t width, int32_t height, int64_t n,
+                  const int32_t* px, const int32_t* py, const int64_t* sample, double* out, int32_t* trials);
+
 /* ---- the reference's render API --------------------------------------------------------- */
 
 /* == IPixelIntegrator.Sample(spp) (IIntegrator.fs:35-40, Integrators.fs:161-172):

@@ -97,6 +97,11 @@ class MfxEnvironment(C.Structure):
     _fields_ = [("rgb", C.POINTER(C.c_float)), ("size", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MfxLens(C.Structure):
+    """mfx_lens: the lens radius (world units; 0: no lens) and the distance of the focus plane along the forward axis."""
+    _fields_ = [("aperture", C.c_double), ("focus", C.c_double)]
+
+
 class MfxAdaptive(C.Structure):
     """mfx_adaptive: the schedule and threshold of mfx_sample_adaptive."""
     _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("step_spp", C.c_int32), ("reserved", C.c_int32),
@@ -332,6 +337,41 @@ def env_sample_direction(size: int, texel, jitter) -> np.ndarray:
     return out[:len(t)]
 
 
+def lens_struct(lens) -> "MfxLens":
+    """An MfxLens from (aperture, focus); an MfxLens passes through."""
+    if isinstance(lens, MfxLens):
+        return lens
+    aperture, focus = lens
+    return MfxLens(aperture=float(aperture), focus=float(focus))
+
+
+def lens_derive(camera, lens) -> np.ndarray:
+    """Host-only: the lens record of `camera` (pinhole_struct's shapes) under lens = (aperture, focus), by the code
+    the kernels compile (mfx_lens_derive): U[3], V[3], s (lens.derive is the Python statement of the same)."""
+    lib = load_library()
+    p, ln = pinhole_struct(camera), lens_struct(lens)
+    out = np.zeros(7)
+    check(lib.mfx_lens_derive(C.byref(p), C.byref(ln), dptr(out)), "mfx_lens_derive")
+    return out
+
+
+def lens_rays(camera, lens, seed: int, width: int, height: int, px, py, sample):
+    """Host-only: the lens camera rays of paths (px[i], py[i], sample[i]) of a width x height film under `seed`, by
+    the code the kernels compile (mfx_lens_rays): ((n, 8) float64 = o, d, a, b, (n,) int32 = the trials each took)."""
+    lib = load_library()
+    p, ln = pinhole_struct(camera), lens_struct(lens)
+    x = np.ascontiguousarray(px, dtype=np.int32).reshape(-1)
+    y = np.ascontiguousarray(py, dtype=np.int32).reshape(-1)
+    s = np.ascontiguousarray(sample, dtype=np.int64).reshape(-1)
+    if not (len(x) == len(y) == len(s)):
+        raise ValueError("lens_rays: one px, py and sample per path")
+    out = np.zeros((max(1, len(x)), 8))
+    trials = np.zeros(max(1, len(x)), dtype=np.int32)
+    check(lib.mfx_lens_rays(C.byref(p), C.byref(ln), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), int(width), int(height), len(x),
+                            iptr(x), iptr(y), s.ctypes.data_as(C.POINTER(C.c_int64)), dptr(out), iptr(trials)), "mfx_lens_rays")
+    return out[:len(x)], trials[:len(x)]
+
+
 _P = C.POINTER
 _dp = _P(C.c_double)
 _ip = _P(C.c_int32)
@@ -374,6 +414,11 @@ def _bind(lib, strict: bool = True):
         "mfx_sky_sampling_info": (C.c_int, [C.c_void_p, _dp]),
         "mfx_env_sample_table": (C.c_int, [_P(MfxEnvironment), _P(C.c_float), _P(C.c_uint32), _dp]),
         "mfx_env_sample_direction": (C.c_int, [C.c_int32, C.c_int64, _P(C.c_uint32), _dp, _dp]),
+        "mfx_set_lens": (C.c_int, [C.c_void_p, _P(MfxLens)]),
+        "mfx_lens_info": (C.c_int, [C.c_void_p, _dp]),
+        "mfx_lens_derive": (C.c_int, [_P(MfxPinhole), _P(MfxLens), _dp]),
+        "mfx_lens_rays": (C.c_int, [_P(MfxPinhole), _P(MfxLens), C.c_uint64, C.c_int32, C.c_int32, C.c_int64, _ip, _ip,
+                                    _P(C.c_int64), _dp, _ip]),
         "mfx_render_rgba8": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint8)]),
         "mfx_accumulate_render_rgba8": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint8)]),
         "mfx_stats": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -416,7 +461,7 @@ def _bind(lib, strict: bool = True):
 
 
 EXPORTED_SYMBOLS = [
-    "mfx_create", "mfx_create_instanced", "mfx_create_lights", "mfx_light_info", "mfx_light_table", "mfx_create_textured", "mfx_texture_info", "mfx_uv_table", "mfx_texel_index", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_sample_adaptive_resume", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_temporal", "mfx_pinhole_derive", "mfx_camera_info", "mfx_set_camera", "mfx_set_environment", "mfx_environment_info", "mfx_env_texel_index", "mfx_set_environment_sampled", "mfx_sky_sampling_info", "mfx_env_sample_table", "mfx_env_sample_direction", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
+    "mfx_create", "mfx_create_instanced", "mfx_create_lights", "mfx_light_info", "mfx_light_table", "mfx_create_textured", "mfx_texture_info", "mfx_uv_table", "mfx_texel_index", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_sample_adaptive_resume", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_temporal", "mfx_pinhole_derive", "mfx_camera_info", "mfx_set_camera", "mfx_set_environment", "mfx_environment_info", "mfx_env_texel_index", "mfx_set_environment_sampled", "mfx_sky_sampling_info", "mfx_env_sample_table", "mfx_env_sample_direction", "mfx_set_lens", "mfx_lens_info", "mfx_lens_derive", "mfx_lens_rays", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
     "mfx_film_mean", "mfx_stats",
     "mfx_trace_accumulate", "mfx_accum_clear", "mfx_accum_reduce", "mfx_accum_device_ptr", "mfx_accum_attach", "mfx_accum_read_mean",
     "mfx_sync", "mfx_stream", "mfx_ray_counts", "mfx_last_trace_ms", "mfx_trace_timing", "mfx_ray_counts_total", "mfx_closest_hit", "mfx_any_hit", "mfx_ref_leaves",

@@ -87,7 +87,7 @@ static int scene_upload(SceneImages& s, const CreateEnv& env) {
     CK(upload(s.d_albedo, s.host.albedo));
     CK(upload(s.d_light, std::vector<MfxLight>{s.host.light}));
     if (s.multi_light()) CK(upload(s.d_lights, s.host.lights));  // (once per device of a list: every device runs this)
-    CK(upload(s.d_cam, std::vector<MfxCamera>{s.host.camera}));
+    CK(upload(s.d_cam, std::vector<MfxCamera>{s.host.camera, MfxCamera{}}));  // ([1]: room for a lens record, mfx_set_lens)
     CK(upload(s.d_refs, std::vector<const void*>{s.d_slot_ref.get(), s.d_ref_blob.get()}));
     if (!s.host.inst.empty()) CK(upload(s.d_inst, s.host.inst));
     return MFX_OK;
@@ -502,14 +502,29 @@ static int create_impl(const CreateArgs& a) {
     return MFX_OK;
 }
 
-// ---- mfx_set_camera -------------------------------------------------------------------------------
+// ---- mfx_set_camera, mfx_set_lens ------------------------------------------------------------------
 // Prepare the kept scene again for `cam` by creation's own steps: the host scene once, then for every device
 // of the context a fresh SceneImages (scene_upload, scene_shapes). They are moved in only when every device
 // has its own, so a failure leaves every context as it was: what was built so far goes with `fresh`.
-static int rebuild_for_camera(mfx_ctx* c, const mfx_pinhole* cam) {
+// at (null: the camera's own position): the point the widening is sized for, a corner of the lens box; the images
+// are then those of a camera at `at`, and carry `cam` as their camera.
+static int rebuild_for_camera(mfx_ctx* c, const char* who, const mfx_pinhole* cam, const double* at) {
     HIPCHECK(hipSetDevice(c->device));
     MfxHostScene h;
-    MFX_TRY(build_host_scene("mfx_set_camera", source_of(c->kept), *cam, c->scene.host.lights, h));
+    if (at) {
+        MfxCamera m;
+        mfx_derive_camera(*cam, m);
+        mfx_pinhole sized = *cam;
+        sized.derived = 1;
+        std::copy(at, at + 3, sized.position);
+        std::copy(m.topleft, m.topleft + 3, sized.topleft);
+        std::copy(m.right, m.right + 3, sized.right);
+        std::copy(m.down, m.down + 3, sized.down);
+        MFX_TRY(build_host_scene(who, source_of(c->kept), sized, c->scene.host.lights, h));
+        h.camera = m;
+    } else {
+        MFX_TRY(build_host_scene(who, source_of(c->kept), *cam, c->scene.host.lights, h));
+    }
     const std::vector<mfx_ctx*> ds = devs_of(c);
     std::vector<SceneImages> fresh(ds.size());  // (the shapes start from a fresh context's defaults)
     int rc = MFX_OK;
@@ -517,7 +532,7 @@ static int rebuild_for_camera(mfx_ctx* c, const mfx_pinhole* cam) {
         const mfx_ctx* dv = ds[g];
         fresh[g].host = h;
         set_sky_light(fresh[g], dv->scene.sky_light);  // (a sampled sky stays a light of the new images)
-        rc = hipSetDevice(dv->device) == hipSuccess ? MFX_OK : fail(MFX_E_DEVICE, "mfx_set_camera: hipSetDevice failed");
+        rc = hipSetDevice(dv->device) == hipSuccess ? MFX_OK : fail(MFX_E_DEVICE, std::string(who) + ": hipSetDevice failed");
         if (rc == MFX_OK) rc = scene_upload(fresh[g], dv->env);
         if (rc == MFX_OK) rc = scene_shapes(fresh[g], dv->device, dv->env, wf_textured(dv), dv->cuts.on);
     }
@@ -533,6 +548,95 @@ static int rebuild_for_camera(mfx_ctx* c, const mfx_pinhole* cam) {
     }
     HIPCHECK(hipSetDevice(c->device));
     c->kept.desc.camera = *cam;
+    return MFX_OK;
+}
+
+// The widening camera m needs over `host`: its position's, or under a lens the largest over the corners of the
+// lens box, P0 +- (|U| + |V|) per axis (every lens origin lies inside). at: the point that asks for it.
+static void camera_lens_eps(const MfxHostScene& host, const MfxCamera& m, const MfxLensRec* L, float* eps, float* eps_t, double at[3]) {
+    std::copy(m.position, m.position + 3, at);
+    mfx_camera_eps(host, m.position, eps, eps_t);
+    if (!L) return;
+    for (int k = 0; k < 8; ++k) {
+        double p[3];
+        for (int a = 0; a < 3; ++a) {
+            const double r = std::fabs(L->U[a]) + std::fabs(L->V[a]);
+            p[a] = (k >> a) & 1 ? m.position[a] + r : m.position[a] - r;
+        }
+        float e = 0.f, et = 0.f;
+        mfx_camera_eps(host, p, &e, &et);
+        if (e > *eps || (e == *eps && et > *eps_t)) {
+            *eps = e, *eps_t = et;
+            std::copy(p, p + 3, at);
+        }
+    }
+}
+
+static const char* lens_refusal(int code) {
+    switch (code) {
+    case MFX_LENS_BAD_APERTURE: return "aperture must be finite and >= 0";
+    case MFX_LENS_BAD_FOCUS: return "focus must be finite and > 0";
+    case MFX_LENS_BAD_RIGHT: return "the camera's right has no finite non-zero length (lr)";
+    case MFX_LENS_BAD_DOWN: return "the camera's down has no finite non-zero length (ld)";
+    case MFX_LENS_BAD_FORWARD: return "the camera's right and down span no plane (ln)";
+    case MFX_LENS_BAD_DPLANE: return "dplane must be finite and > 0 (the film plane lies ahead of the camera)";
+    default: return "s = focus / dplane is not finite";
+    }
+}
+
+int mfxh::lens_record(const char* who, const mfx_pinhole* cam, const mfx_lens* lens, MfxLensRec& rec) {
+    MfxCamera m;
+    mfx_derive_camera(*cam, m);
+    const int bad = mfx_lens_record(m.position, lens->aperture, lens->focus, rec, nullptr);
+    return bad ? fail(MFX_E_INVALID, std::string(who) + ": " + lens_refusal(bad)) : MFX_OK;
+}
+
+int mfxh::apply_camera_lens(mfx_ctx* c, const char* who, const mfx_pinhole* cam, const mfx_lens* lens) {
+    MfxCamera m;
+    mfx_derive_camera(*cam, m);
+    Lens nl = c->lens;  // the lens state after the call
+    nl.on = lens != nullptr;
+    nl.aperture = lens ? lens->aperture : 0.0;
+    nl.focus = lens ? lens->focus : 0.0;
+    nl.rec = MfxLensRec{};
+    if (lens) MFX_TRY(lens_record(who, cam, lens, nl.rec));  // on the host, before a device is touched
+    const bool by_lens = std::strcmp(who, "mfx_set_lens") == 0;
+    // held render-ahead frames are the old camera's: the film comes back to d_film under the old camera, and
+    // the frames' epoch ends; then everything the context has enqueued, a background batch included, finishes
+    MFX_TRY(ahead_break(c));
+    MFX_TRY(mfx_sync(c));
+    const MfxHostScene& host = c->scene.host;
+    float eps = 0.f, eps_t = 0.f;
+    double at[3];
+    camera_lens_eps(host, m, lens ? &nl.rec : nullptr, &eps, &eps_t, at);
+    // images built for a lens box go with the lens: the pinhole context again, digest included
+    const bool narrow = !lens && c->lens.widened;
+    if (!narrow && eps <= host.eps && eps_t <= host.eps_templates) {
+        // in place: the boxes stay conservative for every ray this camera can start
+        for (mfx_ctx* d : devs_of(c)) {
+            HIPCHECK(hipSetDevice(d->device));
+            HIPCHECK(hipMemcpy(d->scene.d_cam, &m, sizeof(m), hipMemcpyHostToDevice));
+            d->scene.host.camera = m;
+        }
+        HIPCHECK(hipSetDevice(c->device));
+        c->kept.desc.camera = *cam;
+    } else {
+        MFX_TRY(rebuild_for_camera(c, who, cam, lens ? at : nullptr));
+        (by_lens ? nl.rebuilds : c->cam_rebuilds) += 1;
+        nl.widened = lens != nullptr;
+    }
+    if (lens)  // the record behind the camera, where the LENS instances read it (new images have room for it too)
+        for (mfx_ctx* d : devs_of(c)) {
+            HIPCHECK(hipSetDevice(d->device));
+            HIPCHECK(hipMemcpy(d->scene.d_cam.get() + 1, &nl.rec, sizeof(nl.rec), hipMemcpyHostToDevice));
+        }
+    HIPCHECK(hipSetDevice(c->device));
+    nl.eps = lens ? eps : 0.f;
+    if (!lens) nl.rebuilds = 0;  // (mfx_lens_info: all 0 without a lens)
+    for (mfx_ctx* d : devs_of(c)) d->lens = nl;
+    c->cam_epoch += 1;           // the feature buffers are the old camera's
+    c->adp.accum_valid = false;  // a resume must not mix cameras
+    c->ahead.dfilm_buf = -1;
     return MFX_OK;
 }
 
@@ -554,31 +658,23 @@ int mfx_set_camera(mfx_ctx* c, const mfx_pinhole* cam) {
     for (const double* v : {m.position, m.topleft, m.right, m.down})
         for (int a = 0; a < 3; ++a)
             if (!std::isfinite(v[a])) return fail(MFX_E_INVALID, "mfx_set_camera: the derived camera is not finite");
-    const MfxHostScene& host = c->scene.host;
-    if (std::memcmp(&m, &host.camera, sizeof(m)) == 0) return MFX_OK;  // the current camera: nothing to do
-    // held render-ahead frames are the old camera's: the film comes back to d_film under the old camera, and
-    // the frames' epoch ends; then everything the context has enqueued, a background batch included, finishes
-    MFX_TRY(ahead_break(c));
-    MFX_TRY(mfx_sync(c));
-    float eps = 0.f, eps_t = 0.f;
-    mfx_camera_eps(host, m.position, &eps, &eps_t);
-    if (eps <= host.eps && eps_t <= host.eps_templates) {
-        // in place: the boxes stay conservative for every ray this camera can start
-        for (mfx_ctx* d : devs_of(c)) {
-            HIPCHECK(hipSetDevice(d->device));
-            HIPCHECK(hipMemcpy(d->scene.d_cam, &m, sizeof(m), hipMemcpyHostToDevice));
-            d->scene.host.camera = m;
-        }
-        HIPCHECK(hipSetDevice(c->device));
-        c->kept.desc.camera = *cam;
-    } else {
-        MFX_TRY(rebuild_for_camera(c, cam));
-        c->cam_rebuilds += 1;
-    }
-    c->cam_epoch += 1;
-    c->adp.accum_valid = false;  // a resume must not mix cameras
-    c->ahead.dfilm_buf = -1;
-    return MFX_OK;
+    if (std::memcmp(&m, &c->scene.host.camera, sizeof(m)) == 0) return MFX_OK;  // the current camera: nothing to do
+    // under a lens the call keeps aperture and focus, derives the record again and sizes the widening for the lens box
+    const mfx_lens cur{c->lens.aperture, c->lens.focus};
+    return apply_camera_lens(c, "mfx_set_camera", cam, c->lens.on ? &cur : nullptr);
+}
+
+int mfx_set_lens(mfx_ctx* c, const mfx_lens* lens) {
+    if (!c) return fail(MFX_E_INVALID, "mfx_set_lens: null context");
+    if (lens && lens->aperture == 0.0) lens = nullptr;  // an aperture of exactly 0 is the pinhole
+    if (lens && (c->flags & (MFX_F_MEGAKERNEL | MFX_F_COUNT_STATS)))
+        return fail(MFX_E_STATE, "mfx_set_lens: a context created with MFX_F_MEGAKERNEL or MFX_F_COUNT_STATS has no lens instances");
+    if (!lens && !c->lens.on) return MFX_OK;  // no lens, none wanted
+    if (lens && c->lens.on && std::memcmp(&lens->aperture, &c->lens.aperture, sizeof(double)) == 0 &&
+        std::memcmp(&lens->focus, &c->lens.focus, sizeof(double)) == 0)
+        return MFX_OK;  // the current lens
+    const mfx_pinhole cam = c->kept.desc.camera;
+    return apply_camera_lens(c, "mfx_set_lens", &cam, lens);
 }
 
 int mfx_create(const mfx_scene_desc* scene, const mfx_options* opt, mfx_ctx** out) {

@@ -362,6 +362,19 @@ struct Environment {
     bool on() const { return size > 0; }
 };
 
+// The thin lens (mfx_set_lens; mfx_lens.cpp), per device: the record the LENS instances read. Like the sky it is no
+// part of SceneImages; its only tie to them is the widening (the images' eps covers the lens box's corners).
+struct Lens {
+    bool on = false;
+    double aperture = 0.0, focus = 0.0;
+    MfxLensRec rec{};
+    float eps = 0.f;         // the widening the lens camera needs (the largest over the lens box's corners)
+    int64_t rebuilds = 0;    // image rebuilds mfx_set_lens caused (primary)
+    // the images were built for a lens box (by mfx_set_lens, or by mfx_set_camera under a lens): removing the lens
+    // builds them again for the camera alone, so the context is the pinhole one again, digest included (primary)
+    bool widened = false;
+};
+
 // What scene_shapes chooses for k_extend (ext) and k_shadow (shd): wf_trace copies it into a trace's WfParams
 struct LaunchShapes {
     int stack_lds_ext = 0, stack_lds_shd = 0;  // traversal stack entries per lane in LDS; the rest in d_spill
@@ -495,6 +508,7 @@ struct __attribute__((visibility("hidden"))) mfx_ctx {
     mfxh::Multi multi;
     mfxh::Textures tex;
     mfxh::Environment sky;
+    mfxh::Lens lens;
 
     // the RCCL communicators, then the peers, then this device current; the members release themselves
     ~mfx_ctx();
@@ -528,6 +542,10 @@ inline bool wf_env(const mfx_ctx* c) { return c->sky.on(); }
 // a sampled sky (mfx_set_environment_sampled): the SKY instances of k_shadow and k_resolve, which are several-light
 // instances (wf_multi_light holds), the sampling table, a texel-id plane per vertex in the pool
 inline bool wf_sky_sampled(const mfx_ctx* c) { return c->sky.on() && c->sky.sampled; }
+
+// a thin lens (mfx_set_lens): the LENS twin of the k_extend instance that starts the paths (no k_camera, no camera
+// cuts) and of k_aov, the wavefront pipeline for every trace
+inline bool wf_lens(const mfx_ctx* c) { return c->lens.on; }
 
 // bytes of one path slot of the wavefront pool (ray queues included)
 inline size_t pool_slot_bytes(const mfx_ctx* c) {
@@ -563,6 +581,12 @@ inline bool wf_lit_in_hit(const mfx_ctx* c) {
 }
 
 // mfx_create.cpp
+// The camera `cam` and the lens (null: none) become the context's, on every device: in place when the images' widening
+// covers what they need, by building the images again otherwise (a failure leaves everything as it was). who: the
+// calling entry point, for messages. Waits for the context's work and invalidates what mfx_set_camera invalidates.
+int apply_camera_lens(mfx_ctx* c, const char* who, const mfx_pinhole* cam, const mfx_lens* lens);
+// the lens record of `cam` under `lens`, or MFX_E_INVALID with who + ": " + the field that is refused
+int lens_record(const char* who, const mfx_pinhole* cam, const mfx_lens* lens, MfxLensRec& rec);
 // after set_sky_light on c's images: the lights in HBM again and the launch shapes of the instances that run now
 int scene_relight(mfx_ctx* c);
 // the LDS shape of k_extend or (shd) k_shadow over the scene images `s` of a context (textured: wf_textured) with

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "mfx_layout.h"
+#include "mfx_lens.h"
 #include "mfx_texture.h"
 
 #define MFX_AOV_PLANES 8  // normal xyz, hit t, albedo rgb, hit fraction
@@ -30,6 +31,8 @@ struct AovParams {
     double* feat;             // [MFX_AOV_PLANES][w*h], x-major pixels
     double* out;              // null, or [w*h][MFX_AOV_PLANES] (the caller's layout)
     MfxTexTables tx;          // albedo textures (all null without: the untextured instances run)
+    MfxLensRec lens;          // a thin lens (mfx_set_lens; lens_on runs the LENS instances: the film's own lens rays)
+    int32_t lens_on;
 };
 
 // k_atrous: one iteration of the edge-avoiding a-trous filter (the rule: include/mafrix_rt.h)
@@ -88,6 +91,8 @@ struct TemporalParams {
 };
 
 hipError_t mfx_launch_aov(const AovParams& P, hipStream_t st);
+// resident blocks per CU of k_aov's instance (two-level, textured, lens) with stack_size stack entries per lane in LDS
+hipError_t mfx_aov_occupancy(bool inst, bool tx, bool lens, int stack_size, int* blocks_per_cu);
 hipError_t mfx_launch_temporal(const TemporalParams& P, hipStream_t st);
 hipError_t mfx_launch_atrous(const AtrousParams& P, hipStream_t st);
 hipError_t mfx_launch_atrous_var(const AtrousVarParams& P, hipStream_t st);

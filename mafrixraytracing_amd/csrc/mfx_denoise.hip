@@ -16,6 +16,7 @@
 
 #include "mfx_layout.h"
 #include "mfx_denoise.h"
+#include "mfx_lens.h"
 #include "mfx_trace_common.h"
 
 // ----------------------------------------------------------------------------------------------
@@ -26,7 +27,9 @@
 // ----------------------------------------------------------------------------------------------
 // TX: the instances for albedo textures (mfx_create_textured): the albedo planes take the material's albedo
 // times the texel of the hit point, by the rule and the functions the path vertices use (mfx_texture.h).
-template <bool INST, bool TX = false>
+// LENS: the instances for a thin lens (mfx_set_lens): the ray is the film's own lens ray (mfx_lens.h), so plane [3]
+// is t along it.
+template <bool INST, bool TX = false, bool LENS = false>
 __global__ void __launch_bounds__(256) k_aov(AovParams P) {
     extern __shared__ int lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -46,9 +49,17 @@ __global__ void __launch_bounds__(256) k_aov(AovParams P) {
         uint32_t rn = 0;
         const double u = ((double)x + rng_next(key, rn)) / (double)P.width;
         const double v = ((double)y + rng_next(key, rn)) / (double)P.height;
-        const DV target = vadd(vadd(ld3(CAM.topleft), vmul(ld3(CAM.right), u)), vmul(ld3(CAM.down), v));
-        const DV o = ld3(CAM.position);
-        const DV d = vnormalize(vsub(target, o));
+        DV o, d;
+        if constexpr (LENS) {
+            double lo[3], ldir[3], la, lb;
+            mfx_lens_ray(CAM.position, P.lens, key, u, v, lo, ldir, la, lb);
+            o = dv(lo[0], lo[1], lo[2]);
+            d = dv(ldir[0], ldir[1], ldir[2]);
+        } else {
+            const DV target = vadd(vadd(ld3(CAM.topleft), vmul(ld3(CAM.right), u)), vmul(ld3(CAM.down), v));
+            o = ld3(CAM.position);
+            d = vnormalize(vsub(target, o));
+        }
         Best B;
         Stats st{0, 0, 0};
         if (!traverse<false, false, INST>(S, o, d, 1e-6, 99999999., stack, B, st)) continue;  // a miss adds nothing
@@ -411,18 +422,29 @@ __global__ void k_dn_post(const double* __restrict__ src, int w, int h, double* 
 // ----------------------------------------------------------------------------------------------
 static inline unsigned dn_grid(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
-hipError_t mfx_launch_aov(const AovParams& P, hipStream_t st) {
-    const size_t lds = (size_t)4 * P.stack_size * 64 * sizeof(int);  // mfx_launch_query's: a column per lane
-    const dim3 g(dn_grid((int64_t)P.width * P.height, 256));
-    if (P.tx.texels) {  // albedo textures: the TX instances
-        if (!P.tx.uvrec || !P.tx.ptex || !P.tx.desc) return hipErrorInvalidValue;
-        if (P.inst) hipLaunchKernelGGL((k_aov<true, true>), g, dim3(256), lds, st, P);
-        else hipLaunchKernelGGL((k_aov<false, true>), g, dim3(256), lds, st, P);
-        return hipGetLastError();
+// k_aov's instance: two-level (inst), albedo textures (tx), a thin lens (lens)
+static const void* aov_kernel(bool inst, bool tx, bool lens) {
+    if (lens) {
+        if (tx) return inst ? (const void*)k_aov<true, true, true> : (const void*)k_aov<false, true, true>;
+        return inst ? (const void*)k_aov<true, false, true> : (const void*)k_aov<false, false, true>;
     }
-    if (P.inst) hipLaunchKernelGGL(k_aov<true>, g, dim3(256), lds, st, P);
-    else hipLaunchKernelGGL(k_aov<false>, g, dim3(256), lds, st, P);
-    return hipGetLastError();
+    if (tx) return inst ? (const void*)k_aov<true, true> : (const void*)k_aov<false, true>;
+    return inst ? (const void*)k_aov<true> : (const void*)k_aov<false>;
+}
+static size_t aov_lds_bytes(int stack_size) { return (size_t)4 * stack_size * 64 * sizeof(int); }  // mfx_launch_query's: a column per lane
+
+hipError_t mfx_launch_aov(const AovParams& P, hipStream_t st) {
+    const dim3 g(dn_grid((int64_t)P.width * P.height, 256));
+    // albedo textures: the TX instances
+    if (P.tx.texels && (!P.tx.uvrec || !P.tx.ptex || !P.tx.desc)) return hipErrorInvalidValue;
+    void* args[] = {const_cast<AovParams*>(&P)};
+    const hipError_t e = hipLaunchKernel(aov_kernel(P.inst != nullptr, P.tx.texels != nullptr, P.lens_on != 0), g, dim3(256), args,
+                                         aov_lds_bytes(P.stack_size), st);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t mfx_aov_occupancy(bool inst, bool tx, bool lens, int stack_size, int* blocks_per_cu) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, aov_kernel(inst, tx, lens), 256, aov_lds_bytes(stack_size));
 }
 
 hipError_t mfx_launch_temporal(const TemporalParams& P, hipStream_t st) {

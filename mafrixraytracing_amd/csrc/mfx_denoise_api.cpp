@@ -69,6 +69,8 @@ extern "C" int mfx_aov(mfx_ctx* c, int32_t spp, int64_t sample_base, double* out
     P.feat = dn.feat;
     P.out = out ? dn.feat_out.get() : nullptr;
     P.tx = c->tex.tables();  // albedo textures: k_aov's TX instances (all null without)
+    P.lens = c->lens.rec;    // a thin lens: k_aov's LENS instances trace the film's own lens rays
+    P.lens_on = wf_lens(c) ? 1 : 0;
     HIPCHECK(hipEventRecord(dn.ev0, c->stream));
     HIPCHECK(mfx_launch_aov(P, c->stream));
     HIPCHECK(hipEventRecord(dn.ev1, c->stream));
@@ -242,6 +244,8 @@ extern "C" int mfx_temporal(mfx_ctx* c, const mfx_temporal_cfg* a, const double*
         for (int64_t q = 0; q < c->npix; ++q)
             if (!std::isfinite(count_in[q])) return fail(MFX_E_INVALID, "mfx_temporal: count_in must be finite");
     MFX_TRY(whole_film_single_device(c, "mfx_temporal"));
+    // (its reprojection sends a world point through the pinhole; the history stays as it is)
+    if (wf_lens(c)) return fail(MFX_E_STATE, "mfx_temporal: the context has a lens (mfx_set_lens): the reprojection is the pinhole's");
     Denoise& dn = c->dn;
     Temporal& tp = c->tp;
     if (!dn.ready()) return fail(MFX_E_STATE, "mfx_temporal: no feature buffers (call mfx_aov on this context first)");

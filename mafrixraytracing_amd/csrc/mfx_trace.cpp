@@ -312,7 +312,8 @@ int mfxh::wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, TraceMode mode) 
     P.tile_n = list ? list->tile_n : nullptr;
     P.list_max = list ? list->list_max : 0;
     const bool stats = (c->flags & MFX_F_COUNT_STATS) != 0;
-    P.cam_grid = c->scene.host.inst.empty() ? c->scene.wf_cam_grid : 0;
+    // (a lens: no packets and no cut table, which rest on one shared origin; k_extend's LENS twin starts the paths)
+    P.cam_grid = c->scene.host.inst.empty() && !wf_lens(c) ? c->scene.wf_cam_grid : 0;
     if (own_events) c->cam_last = P.cam_grid > 0;
     // camera cuts: a table that is already this camera's costs nothing; a trace of fewer than min_samples
     // samples does not pay for a build and walks from the root (the break-even)
@@ -371,13 +372,13 @@ int mfxh::wf_trace(mfx_ctx* c, int64_t ns, int64_t sample_base, TraceMode mode) 
             // the same halving costs 1.5 %, so frames of more than 2^25 paths keep whole chunks)
             P.chunk_shd = (c->wf_shd_half && !P.qcount && total <= ((int64_t)1 << 25)) ? std::max(64, P.chunk / 2) : P.chunk;
             if (!iter_events) {
-                HIPCHECK(mfx_wf_iteration(P, c->scene.wf_ext_grid, c->scene.wf_shd_grid, stats, c->stream, nullptr));
+                HIPCHECK(mfx_wf_iteration(P, c->scene.wf_ext_grid, c->scene.wf_shd_grid, stats, c->stream, nullptr, wf_lens(c)));
                 continue;
             }
             const Event* ev = c->it_ev.data() + 3 * it;
             hipEvent_t mid = ev[1];  // recorded between k_extend and k_shadow
             HIPCHECK(hipEventRecord(ev[0], c->stream));
-            HIPCHECK(mfx_wf_iteration(P, c->scene.wf_ext_grid, c->scene.wf_shd_grid, stats, c->stream, &mid));
+            HIPCHECK(mfx_wf_iteration(P, c->scene.wf_ext_grid, c->scene.wf_shd_grid, stats, c->stream, &mid, wf_lens(c)));
             HIPCHECK(hipEventRecord(ev[2], c->stream));
             if (c->diag_iter) {
                 HIPCHECK(hipStreamSynchronize(c->stream));
@@ -433,8 +434,8 @@ int mfxh::dev_trace_accumulate(mfx_ctx* c, int32_t spp, int64_t sample_base, Res
     // is exact, and its per-path arithmetic is the wavefront's, so the bits are the same; it does
     // not pay the wavefront's per-bounce launches over a 2 M-path frame (r02e: 1.7 vs 7.9 ms at 1080p).
     // (several lights: always the wavefront, as under MFX_F_WAVEFRONT; creation refused MFX_F_MEGAKERNEL)
-    // (albedo textures, a sky: likewise; mfx_set_environment refuses an MFX_F_MEGAKERNEL context)
-    c->mega_last = !wf_multi_light(c) && !wf_textured(c) && !wf_env(c) && ((c->flags & MFX_F_MEGAKERNEL) != 0 || (ns == 1 && (c->flags & MFX_F_WAVEFRONT) == 0));
+    // (albedo textures, a sky, a lens: likewise; mfx_set_environment and mfx_set_lens refuse an MFX_F_MEGAKERNEL context)
+    c->mega_last = !wf_multi_light(c) && !wf_textured(c) && !wf_env(c) && !wf_lens(c) && ((c->flags & MFX_F_MEGAKERNEL) != 0 || (ns == 1 && (c->flags & MFX_F_WAVEFRONT) == 0));
     if (ns == 0) {  // this partition has no sample in the call: zero rays in zero device time
         HIPCHECK(hipEventRecord(c->ev0, c->stream));
         HIPCHECK(hipEventRecord(c->ev1, c->stream));

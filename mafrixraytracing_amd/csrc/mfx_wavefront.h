@@ -31,6 +31,7 @@
 #include "mfx_camera_cuts.h"
 #include "mfx_environment.h"
 #include "mfx_layout.h"
+#include "mfx_lens.h"
 #include "mfx_texture.h"
 
 #define WF_FREE 0
@@ -229,7 +230,11 @@ struct WfParams {
     // the plain instances the bounces, so env_rec holds camera-ray misses only.
     const MfxSkyEntry* sky_tab;  // [size * size] the sampling table
     uint32_t* vsky;              // [vertex][stride] a sky vertex's texel id (beside vtex; allocated with a sampled sky only)
+    // (A thin lens, mfx_set_lens, adds no field: its record lies behind the camera in device memory, cam_dev[1], where
+    // k_extend's LENS instances read it (wf_lens_rec), and the launcher is told of it beside P. Kernel arguments of
+    // more than 1024 B cost every launch of every instance time, and these are 1000.)
 };
+static_assert(sizeof(MfxLensRec) <= sizeof(MfxCamera), "the lens record lies in the camera buffer's second element");
 #define WF_MAX_LIGHTS 64  // MFX_MAX_LIGHTS: a light index is 6 bits of k_shadow's pending flag word
 
 // The adaptive sampler's tile check (k_tile_check: one wave per active tile) and the compaction of the
@@ -302,6 +307,7 @@ struct WfLdsShape {
     bool tx;        // k_shadow's textured instance (WfParams::vtex set; its table pointers take 32 B of LDS more)
     bool env;       // k_extend's ENV instance (WfParams::env_rec set; the same LDS footprint)
     bool sky;       // k_shadow's SKY twin of the ml instance (WfParams::sky_tab set; the same LDS footprint)
+    bool lens;      // k_extend's LENS twin of the instance that starts the paths (mfx_set_lens; the same LDS footprint)
 };
 // resident blocks per CU of the kernel instance that holds shape s
 hipError_t mfx_wf_kernel_occupancy(const WfLdsShape& s, int* blocks_per_cu);
@@ -318,8 +324,9 @@ struct WfQueue {
     unsigned long long* count;  // [WF_SHARDS * WF_HS]
 };
 // one iteration (extend, shadow); ev[0] is recorded between the two kernels (ev may be null)
+// lens: the context has a thin lens, its record in cam_dev[1]: the LENS twin of k_extend starts the paths
 hipError_t mfx_wf_iteration(const WfParams& P, int ext_grid, int shd_grid, bool stats, hipStream_t st,
-                            hipEvent_t* ev);
+                            hipEvent_t* ev, bool lens = false);
 // after a generation's last iteration: add its finished paths' radiance to their pixels
 hipError_t mfx_wf_resolve(const WfParams& P, hipStream_t st);
 

@@ -598,9 +598,13 @@ __device__ __forceinline__ VertexSample sample_vertex(const MfxLight& LT1, bool 
 // ENV: the instances for a sky (mfx_set_environment): a miss stores the texel of the ray's direction and the
 // iteration (the vertices before the miss; wave-uniform) in the path slot's word of P.env_rec, through qslot
 // on a queue. A template parameter for ML's reason: the instances without hold none of it.
+// LENS: the START instances for a thin lens (mfx_set_lens): the camera ray starts on the lens disk and passes
+// through the pinhole ray's point of the focus plane (mfx_lens.h); a flat scene's camera rays take these instead of
+// k_camera, whose packets rest on one shared origin. Nothing after the ray's start differs.
 template <bool STATS, bool SPILL, int SK, bool Q, bool START = false, int LIST = WF_LIST_NONE, int NF = MFX_NF_ANY,
-          bool ENV = false>
+          bool ENV = false, bool LENS = false>
 __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
+    static_assert(!LENS || START, "a lens bends camera rays only");
     constexpr bool INST = SK == WF_SK_INST, SLDS = SK == WF_SK_SLDS;
     extern __shared__ int lds_all[];
 #if MFX_NODE_F16
@@ -666,9 +670,17 @@ __global__ void __launch_bounds__(256, MFX_TRAV_WAVES) k_extend(WfParams P) {
             const double u = ((double)x + rng_next(key, rn)) / (double)P.width;
             const double v = ((double)y + rng_next(key, rn)) / (double)P.height;
             const MfxCamera& CAM = P.cam;
-            const DV target = vadd(vadd(ld3(CAM.topleft), vmul(ld3(CAM.right), u)), vmul(ld3(CAM.down), v));
-            o = ld3(CAM.position);
-            d = vnormalize(vsub(target, o));
+            if constexpr (LENS) {  // the lens draws come from a stream of their own: the path's counter stays at 2
+                double lo[3], ldir[3], la, lb;
+                const MfxLensRec L = *(const MfxLensRec*)(P.cam_dev + 1);  // wave-uniform: scalar loads
+                mfx_lens_ray(CAM.position, L, key, u, v, lo, ldir, la, lb);
+                o = dv(lo[0], lo[1], lo[2]);
+                d = dv(ldir[0], ldir[1], ldir[2]);
+            } else {
+                const DV target = vadd(vadd(ld3(CAM.topleft), vmul(ld3(CAM.right), u)), vmul(ld3(CAM.down), v));
+                o = ld3(CAM.position);
+                d = vnormalize(vsub(target, o));
+            }
             // throughput 1, radiance 0, rn 2 and depth max_depth stay implicit (WF_FRESH); the
             // key is derived again by k_shadow
         } else {
@@ -1778,6 +1790,10 @@ static constexpr bool camera_env_built(const WfKey& k) { return camera_built(k) 
 // (a sampled sky, SKY: k_shadow's twin of every several-light instance, textured or not; beside the key as ENV is.
 // k_extend and k_camera have none: their ENV twins run the camera rays, their plain instances the bounces.)
 static constexpr bool shadow_sky_built(const WfKey& k) { return shadow_built(k) && k.ml; }
+// (a thin lens, LENS: k_extend's twin of every path-starting instance without the traversal counters, and of its ENV
+// twin; beside the key as ENV is. Contexts created with MFX_F_COUNT_STATS refuse mfx_set_lens. k_camera has none: a
+// lens context's camera rays run k_extend; k_shadow and k_resolve never see where a camera ray came from.)
+static constexpr bool extend_lens_built(const WfKey& k) { return extend_env_built(k) && k.start; }
 static constexpr int built_count(bool (*built)(const WfKey&)) {
     int n = 0;
     for (int i = 0; i < WF_KEYS; ++i) n += built(key_at(i));
@@ -1795,8 +1811,12 @@ static_assert(built_count(extend_env_built) == (MFX_NODE_F16 ? 34 : 30) && built
 static_assert(built_count(shadow_sky_built) == (MFX_NODE_F16 ? 2 * 40 : 2 * 36),
               "the sampled sky's instances, SKY: the twin of every several-light k_shadow instance, untextured and "
               "textured, 2 * 40 / 2 * 36; k_resolve's six ML, ENV instances have a twin each");
+static_assert(built_count(extend_lens_built) == 18,
+              "the lens's instances, LENS: the twin of every START k_extend instance without counters (both spill states, "
+              "three scene kinds, three list kinds), 18, and of the ENV twin of each, 18 more");
 
-enum { WF_K_EXTEND, WF_K_SHADOW, WF_K_CAMERA, WF_K_CAMERA_CUTS, WF_K_EXTEND_ENV, WF_K_CAMERA_ENV, WF_K_CAMERA_CUTS_ENV, WF_K_SHADOW_SKY };
+enum { WF_K_EXTEND, WF_K_SHADOW, WF_K_CAMERA, WF_K_CAMERA_CUTS, WF_K_EXTEND_ENV, WF_K_CAMERA_ENV, WF_K_CAMERA_CUTS_ENV, WF_K_SHADOW_SKY, WF_K_EXTEND_LENS,
+       WF_K_EXTEND_LENS_ENV };
 template <int KERNEL, int I>
 static const void* instance_at() {
     constexpr WfKey k = key_at(I);
@@ -1816,6 +1836,10 @@ static const void* instance_at() {
         return (const void*)k_camera<k.stats, k.list, true, true>;
     else if constexpr (KERNEL == WF_K_SHADOW_SKY && shadow_sky_built(k))
         return (const void*)k_shadow<k.stats, k.spill, k.waves, k.sk, k.queue, k.list, k.nf, k.ml, k.tx, true>;
+    else if constexpr (KERNEL == WF_K_EXTEND_LENS && extend_lens_built(k))
+        return (const void*)k_extend<k.stats, k.spill, k.sk, k.queue, k.start, k.list, k.nf, false, true>;
+    else if constexpr (KERNEL == WF_K_EXTEND_LENS_ENV && extend_lens_built(k))
+        return (const void*)k_extend<k.stats, k.spill, k.sk, k.queue, k.start, k.list, k.nf, true, true>;
     else
         return nullptr;
 }
@@ -1824,8 +1848,11 @@ static const void* instance(const WfKey& k, std::index_sequence<I...>) {
     static const void* const table[WF_KEYS] = {instance_at<KERNEL, (int)I>()...};
     return table[key_index(k)];
 }
-// a key's kernel (null: not built); env: its ENV twin
-static const void* extend_kernel(const WfKey& k, bool env = false) {
+// a key's kernel (null: not built); env: its ENV twin; lens: the LENS twin of either (START keys only)
+static const void* extend_kernel(const WfKey& k, bool env = false, bool lens = false) {
+    if (lens)
+        return env ? instance<WF_K_EXTEND_LENS_ENV>(k, std::make_index_sequence<WF_KEYS>{})
+                   : instance<WF_K_EXTEND_LENS>(k, std::make_index_sequence<WF_KEYS>{});
     return env ? instance<WF_K_EXTEND_ENV>(k, std::make_index_sequence<WF_KEYS>{})
                : instance<WF_K_EXTEND>(k, std::make_index_sequence<WF_KEYS>{});
 }
@@ -1856,11 +1883,12 @@ static WfKey camera_key(bool stats, int list) { return {stats, false, WF_SK_FLAT
 // the scene kinds without per-format instances, k_extend's START instance instead of the bounce one (a
 // superset of the bounce instance's code).
 hipError_t mfx_wf_kernel_occupancy(const WfLdsShape& s, int* blocks_per_cu) {
-    WfKey k = shape_key(s, false, false, false, WF_LIST_NONE, 4);
-    if (!s.shadow && !wf_nf_fixed(k)) k.start = true;
+    // (a lens: the START instance whatever the scene kind, its LENS twin: the kernel that starts the context's paths)
+    const bool start = !s.shadow && (s.lens || !wf_nf_fixed(shape_key(s, false, false, false, WF_LIST_NONE, 4)));
+    const WfKey k = shape_key(s, false, false, start, WF_LIST_NONE, 4);
     const size_t lds = wf_lds_bytes(s);
-    const hipError_t e =
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, s.shadow ? shadow_kernel(k, s.sky) : extend_kernel(k, s.env), 256, lds);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        blocks_per_cu, s.shadow ? shadow_kernel(k, s.sky) : extend_kernel(k, s.env, s.lens), 256, lds);
     // (the API counts finer LDS granules than the hardware allocates: measured, k_shadow at 53,952 B per
     // block runs 2 blocks per CU where it says 3, a 10 % loss)
     *blocks_per_cu = std::min(*blocks_per_cu, mfx_lds_blocks(lds));
@@ -1891,20 +1919,22 @@ static WfLdsShape lds_shape(const WfParams& P, bool shadow) {
 }
 
 static hipError_t launch_iteration(const WfParams& P, int ext_grid, int shd_grid, bool stats, hipStream_t st,
-                                   hipEvent_t* ev) {
+                                   hipEvent_t* ev, bool lens) {
     const int list = list_kind(P.ntiles, P.tile_n);
     // a sky: the ENV twins of k_camera and k_extend; a sampled one: for the camera rays alone (the iteration that
     // starts the generation's paths holds nothing else), the plain instances for the bounces
     const bool env = P.env_rec != nullptr && (P.sky_tab == nullptr || P.start);
-    if (!P.inst && P.start && P.cam_grid > 0) {  // camera rays as packets
+    if (!P.inst && P.start && P.cam_grid > 0 && !lens) {  // camera rays as packets (a lens: one origin per ray, k_extend)
         const void* cam = camera_kernel(camera_key(stats, list), P.cuts != nullptr, env);
         if (!cam) return hipErrorInvalidValue;  // (a sky with counters: refused by mfx_set_environment)
         launch(cam, P.cam_grid, cam_lds_bytes(P.stack_size), st, P);
     } else {
         WfLdsShape s = lds_shape(P, false);
         s.env = env;
-        const bool queue = P.qcount != nullptr, start = !queue && P.start;        const void* ext = extend_kernel(shape_key(s, stats, queue, start, start ? list : WF_LIST_NONE, 4), env);
-        if (!ext) return hipErrorInvalidValue;
+        const bool queue = P.qcount != nullptr, start = !queue && P.start;
+        // a lens: the LENS twin starts the paths (the bounces run the plain instances)
+        const void* ext = extend_kernel(shape_key(s, stats, queue, start, start ? list : WF_LIST_NONE, 4), env, start && lens);
+        if (!ext) return hipErrorInvalidValue;  // (a lens with counters: refused by mfx_set_lens)
         launch(ext, ext_grid, wf_lds_bytes(s), st, P);
     }
     if (ev) {  // between the two kernels (per-stage timing); null: not recorded
@@ -1920,7 +1950,7 @@ static hipError_t launch_iteration(const WfParams& P, int ext_grid, int shd_grid
 }
 
 hipError_t mfx_wf_iteration(const WfParams& P, int ext_grid, int shd_grid, bool stats, hipStream_t st,
-                            hipEvent_t* ev) {
+                            hipEvent_t* ev, bool lens) {
     // several lights: the table, its count and the index plane go together (k_shadow<ML> writes vlt)
     // (a sampled sky is the light after them: one area light will do, 63 at most)
     if (P.lights && (!P.vlt || P.nlights < (P.sky_tab ? 1 : 2) || P.nlights > WF_MAX_LIGHTS - (P.sky_tab ? 1 : 0) || P.gray_light || stats))
@@ -1931,6 +1961,8 @@ hipError_t mfx_wf_iteration(const WfParams& P, int ext_grid, int shd_grid, bool 
     if (P.vtex && (!P.tx.uvrec || !P.tx.ptex || !P.tx.desc || !P.tx.texels || stats)) return hipErrorInvalidValue;
     // a sky: the record plane and the map go together (k_extend<ENV> / k_camera<ENV> write env_rec)
     if (P.env_rec && (!P.env_rgb || P.env_size < 1 || P.env_size > MFX_ENV_SIZE_MAX || stats)) return hipErrorInvalidValue;
+    // a lens: no counters, no cut table (its camera rays share no origin)
+    if (lens && (stats || P.cuts || !P.cam_dev)) return hipErrorInvalidValue;
     // the chunk heads and, beside them (WF_CTL_Q0 / WF_CTL_Q1), the next queue's shard counts
     unsigned long long* z = P.ctl;
     size_t nz = WF_NCTL;
@@ -1940,7 +1972,7 @@ hipError_t mfx_wf_iteration(const WfParams& P, int ext_grid, int shd_grid, bool 
     }
     hipError_t e = hipMemsetAsync(z, 0, nz * sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
-    e = launch_iteration(P, ext_grid, shd_grid, stats, st, ev);
+    e = launch_iteration(P, ext_grid, shd_grid, stats, st, ev, lens);
     if (e != hipSuccess) return e;
     return hipGetLastError();
 }

@@ -13,7 +13,7 @@ import numpy as np
 from .abi import (INSTANCING_KEYS, LAUNCH_INFO_KEYS, MFX_DN_SRC_ACCUM, MFX_DN_SRC_ADAPTIVE, MFX_DN_SRC_HOST,
                   MFX_DN_SRC_TEMPORAL, MFX_F_NONE, MFX_F_TWO_LEVEL, MfxAdaptive, MfxAdaptiveResume, MfxDenoiseCfg,
                   MfxDenoiseVarCfg, MfxInstance, MfxOptions, MfxPrimUv, MfxTemporalCfg, PRIM_UV_DTYPE, SceneArrays, check, dptr,
-                  iptr, load_library, pinhole_struct, quad_lights, texture_structs, environment_struct)
+                  iptr, load_library, pinhole_struct, quad_lights, texture_structs, environment_struct, lens_struct)
 from .denoise import DenoiseConfig, DenoiseVarConfig
 from .temporal import TemporalConfig
 
@@ -28,7 +28,7 @@ class NativeContext:
                  part_index: int = 0, part_count: int = 1, devices: list[int] | None = None,
                  instancing: bool = True, render_ahead: int = 0, lights: list | None = None,
                  textures: list | None = None, prim_uv: np.ndarray | None = None, environment=None,
-                 sample_sky: bool = False):
+                 sample_sky: bool = False, lens=None):
         """devices: drive this list of HIP devices from one context (mfx_options.devices; the
         library's own RCCL reduce sums them into devices[0]); None: the single `device`.
         instancing: a scene with instancing data is created through mfx_create_instanced (two-level
@@ -46,7 +46,9 @@ class NativeContext:
         an untextured context, whatever arrays holds.
         environment: an (S, S, 3) float32 octahedral map of linear RGB radiance (environment.py makes them), set
         with set_environment right after creation: rays that leave the scene return its texel. None: black.
-        sample_sky: set it with mfx_set_environment_sampled instead: the sky is a light, sampled at every vertex."""
+        sample_sky: set it with mfx_set_environment_sampled instead: the sky is a light, sampled at every vertex.
+        lens: (aperture, focus), set with set_lens right after creation: a thin lens with depth of field. None: the
+        pinhole."""
         self.lib = load_library()
         self.arrays = arrays
         self.w, self.h = arrays.width, arrays.height
@@ -88,12 +90,14 @@ class NativeContext:
         else:
             check(self.lib.mfx_create(C.byref(self._desc), C.byref(opt), C.byref(h)), "mfx_create")
         self._h = h
-        if environment is not None:
-            try:
+        try:
+            if environment is not None:
                 self.set_environment(environment, sampled=sample_sky)
-            except Exception:
-                self.close()
-                raise
+            if lens is not None:
+                self.set_lens(lens)
+        except Exception:
+            self.close()
+            raise
 
     def close(self):
         if getattr(self, "_h", None):
@@ -233,6 +237,27 @@ class NativeContext:
         temporal and sample_adaptive_resume."""
         p = pinhole_struct(camera)
         check(self.lib.mfx_set_camera(self._h, C.byref(p)), "mfx_set_camera")
+
+    def set_lens(self, lens):
+        """mfx_set_lens: make lens = (aperture, focus) the thin lens of every later call (aperture: the lens radius in
+        world units, focus: the distance of the sharp plane along the forward axis); None or an aperture of 0 removes
+        it. In place when the traversal images' box widening covers the lens disk, else the images are built again
+        (lens_info tells). The film, the accumulator and next_sample are left as they are; aov() and
+        sample_adaptive() must run again before denoise, denoise_var and sample_adaptive_resume, and temporal() is
+        refused under a lens."""
+        if lens is None:
+            check(self.lib.mfx_set_lens(self._h, None), "mfx_set_lens")
+            return
+        ln = lens_struct(lens)
+        check(self.lib.mfx_set_lens(self._h, C.byref(ln)), "mfx_set_lens")
+
+    def lens_info(self) -> np.ndarray:
+        """mfx_lens_info: [0] 1 with a lens, [1] aperture, [2] focus, [3:6] U, [6:9] V, [9] s, [10] the eps the lens
+        camera needs, [11] the image rebuilds set_lens caused, [12] / [13] resident blocks per CU of the k_extend
+        instance that starts the paths / of the k_aov instance in use; the rest 0. All 0 without a lens."""
+        out = np.zeros(16)
+        check(self.lib.mfx_lens_info(self._h, dptr(out)), "mfx_lens_info")
+        return out
 
     def set_environment(self, environment, sampled: bool = False):
         """mfx_set_environment: make the (S, S, 3) float32 octahedral map `environment` (linear RGB radiance; a

@@ -6,7 +6,7 @@ k_resolve<false / true> is k_resolve<0 / 1> (bool FRAMES became int MODE).
 
 With --strip-false every trailing `false` template argument is dropped on both sides, which matches instances
 across commits that added parameters defaulting to false (k_shadow ML and TX, k_resolve ML and TX, k_aov TX,
-k_extend / k_camera / k_resolve ENV, k_shadow / k_resolve SKY).
+k_extend / k_camera / k_resolve ENV, k_shadow / k_resolve SKY, k_extend / k_aov LENS).
 
 Usage: python scripts/resource_diff.py OLD.log NEW.log [--markdown] [--strip-false]"""
 import re
