@@ -187,6 +187,22 @@ type MfxPrimUv =
     val mutable u2 : float
     val mutable v2 : float
 
+/// mfx_prim_normals (80 B): smooth (0: the primitive keeps its face normal), reserved 0, and the normals of its
+/// corners p0, p1, p2 (they need not be unit length)
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type MfxPrimNormals =
+    val mutable smooth : int32
+    val mutable reserved : int32
+    val mutable n0x : float
+    val mutable n0y : float
+    val mutable n0z : float
+    val mutable n1x : float
+    val mutable n1y : float
+    val mutable n1z : float
+    val mutable n2x : float
+    val mutable n2y : float
+    val mutable n2z : float
+
 // ---- entry points --------------------------------------------------------------------------------
 
 module Api =
@@ -200,6 +216,11 @@ module Api =
     extern int mfx_create_textured(MfxSceneDesc& scene, MfxQuadLight[] lights, int nlights, nativeint instances, int ninstances, MfxTexture[] textures, int ntextures, MfxPrimUv[] primUv, MfxOptions& opt, nativeint& ctx)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
     extern int mfx_texture_info(nativeint ctx, float[] out8)
+    // smooth shading: the address of a pinned MfxPrimNormals[], one per entry of scene.prims (copied); 0n removes them
+    [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
+    extern int mfx_set_normals(nativeint ctx, nativeint primNormals, int64 nprims)
+    [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
+    extern int mfx_normal_info(nativeint ctx, float[] out8)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]
     extern void mfx_destroy(nativeint ctx)
     [<DllImport("mafrix_rt", CallingConvention = CallingConvention.Cdecl)>]

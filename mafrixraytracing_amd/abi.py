@@ -102,6 +102,11 @@ class MfxLens(C.Structure):
     _fields_ = [("aperture", C.c_double), ("focus", C.c_double)]
 
 
+class MfxPrimNormals(C.Structure):
+    """mfx_prim_normals: smooth (0: the face normal stays) and the normals of corners p[0], p[1], p[2]."""
+    _fields_ = [("smooth", C.c_int32), ("reserved", C.c_int32), ("n", (C.c_double * 3) * 3)]
+
+
 class MfxAdaptive(C.Structure):
     """mfx_adaptive: the schedule and threshold of mfx_sample_adaptive."""
     _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("step_spp", C.c_int32), ("reserved", C.c_int32),
@@ -139,6 +144,7 @@ assert C.sizeof(MfxInstance) == 48
 assert C.sizeof(MfxTexture) == 16
 assert C.sizeof(MfxPrimUv) == 56
 assert C.sizeof(MfxEnvironment) == 16
+assert C.sizeof(MfxPrimNormals) == 80
 assert C.sizeof(MfxAdaptive) == 32
 assert C.sizeof(MfxAdaptiveResume) == 32
 assert C.sizeof(MfxDenoiseCfg) == 56
@@ -155,6 +161,9 @@ assert INSTANCE_DTYPE.itemsize == 48
 # mfx_prim_uv: texture index (-1: untextured), (u, v) of p[0], p[1], p[2]
 PRIM_UV_DTYPE = np.dtype([("texture", "<i4"), ("reserved", "<i4"), ("uv", "<f8", (3, 2))], align=True)
 assert PRIM_UV_DTYPE.itemsize == 56
+# mfx_prim_normals: smooth (0: the face normal stays), the normals of p[0], p[1], p[2]
+PRIM_NORMALS_DTYPE = np.dtype([("smooth", "<i4"), ("reserved", "<i4"), ("n", "<f8", (3, 3))], align=True)
+assert PRIM_NORMALS_DTYPE.itemsize == 80
 
 
 class SceneArrays:
@@ -168,12 +177,14 @@ class SceneArrays:
 
     def __init__(self, prims: np.ndarray, albedo: np.ndarray, light: dict, camera: dict,
                  width: int, height: int, max_depth: int = 3, instancing=None, two_level: bool = False,
-                 lights=None, textures=None, prim_uv=None):
+                 lights=None, textures=None, prim_uv=None, prim_normals=None):
         self.prims = np.ascontiguousarray(prims, dtype=PRIM_DTYPE)
         # albedo textures ((H, W, 4) uint8 arrays, rows top to bottom) and the primitives' maps (PRIM_UV_DTYPE,
         # one per entry of `prims`; mfx_create_textured), or None: an untextured scene
         self.textures = [np.ascontiguousarray(t, dtype=np.uint8) for t in textures] if textures is not None else None
         self.prim_uv = np.ascontiguousarray(prim_uv, dtype=PRIM_UV_DTYPE) if prim_uv is not None else None
+        # corner normals (PRIM_NORMALS_DTYPE, one per entry of `prims`; mfx_set_normals), or None: face normals
+        self.prim_normals = np.ascontiguousarray(prim_normals, dtype=PRIM_NORMALS_DTYPE) if prim_normals is not None else None
         self.two_level = bool(two_level)
         # every area light of the scene, in order (light dicts; mfx_create_lights), or None: `light` alone
         self.lights = list(lights) if lights is not None else None
@@ -211,12 +222,13 @@ class SceneArrays:
 
     def with_film(self, width: int, height: int) -> "SceneArrays":
         return SceneArrays(self.prims, self.albedo, self.light, self.camera, width, height, self.max_depth,
-                           self.instancing, self.two_level, self.lights, self.textures, self.prim_uv)
+                           self.instancing, self.two_level, self.lights, self.textures, self.prim_uv, self.prim_normals)
 
     def flat(self) -> "SceneArrays":
         """The same scene without its instancing (the reference's flat primitive list)."""
         return SceneArrays(self.prims, self.albedo, self.light, self.camera, self.width, self.height,
-                           self.max_depth, lights=self.lights, textures=self.textures, prim_uv=self.prim_uv)
+                           self.max_depth, lights=self.lights, textures=self.textures, prim_uv=self.prim_uv,
+                           prim_normals=self.prim_normals)
 
 
 def quad_lights(lights):
@@ -266,6 +278,34 @@ def uv_table(prims, prim_uv) -> np.ndarray:
     check(lib.mfx_uv_table(pr.ctypes.data_as(C.POINTER(MfxPrim)), len(pr), uv.ctypes.data_as(C.POINTER(MfxPrimUv)),
                            dptr(out)), "mfx_uv_table")
     return out[:len(pr)]
+
+
+def normal_table(prims, prim_normals) -> np.ndarray:
+    """Host-only: (n, 12) normal records g_0[3], k_0, g_1[3], k_1, g_2[3], k_2 of `prims` as mfx_set_normals computes
+    them (mfx_normal_table; normals.normal_table is the Python statement of the same)."""
+    lib = load_library()
+    pr = np.ascontiguousarray(prims, dtype=PRIM_DTYPE)
+    pn = np.ascontiguousarray(prim_normals, dtype=PRIM_NORMALS_DTYPE)
+    if len(pr) != len(pn):
+        raise ValueError("one prim_normals entry per primitive")
+    out = np.zeros((max(1, len(pr)), 12))
+    check(lib.mfx_normal_table(pr.ctypes.data_as(C.POINTER(MfxPrim)), len(pr), pn.ctypes.data_as(C.POINTER(MfxPrimNormals)),
+                               dptr(out)), "mfx_normal_table")
+    return out[:len(pr)]
+
+
+def shading_normal(rec, ng, hp) -> np.ndarray:
+    """Host-only: (n, 3) shading normals at hit points hp (n, 3) under records rec (n, 12) of vertices whose normal is
+    ng (n, 3), by the code the kernels compile (mfx_shading_normal; normals.shading_normal is the Python statement)."""
+    lib = load_library()
+    rec = np.ascontiguousarray(rec, dtype=np.float64).reshape(-1, 12)
+    ng = np.ascontiguousarray(ng, dtype=np.float64).reshape(-1, 3)
+    hp = np.ascontiguousarray(hp, dtype=np.float64).reshape(-1, 3)
+    if not (len(rec) == len(ng) == len(hp)):
+        raise ValueError("shading_normal: one record, normal and hit point per vertex")
+    out = np.zeros((max(1, len(rec)), 3))
+    check(lib.mfx_shading_normal(len(rec), dptr(rec), dptr(ng), dptr(hp), dptr(out)), "mfx_shading_normal")
+    return out[:len(rec)]
 
 
 def texel_index(sizes, texture: int, uv) -> np.ndarray:
@@ -419,6 +459,10 @@ def _bind(lib, strict: bool = True):
         "mfx_lens_derive": (C.c_int, [_P(MfxPinhole), _P(MfxLens), _dp]),
         "mfx_lens_rays": (C.c_int, [_P(MfxPinhole), _P(MfxLens), C.c_uint64, C.c_int32, C.c_int32, C.c_int64, _ip, _ip,
                                     _P(C.c_int64), _dp, _ip]),
+        "mfx_set_normals": (C.c_int, [C.c_void_p, _P(MfxPrimNormals), C.c_int64]),
+        "mfx_normal_info": (C.c_int, [C.c_void_p, _dp]),
+        "mfx_normal_table": (C.c_int, [_P(MfxPrim), C.c_int64, _P(MfxPrimNormals), _dp]),
+        "mfx_shading_normal": (C.c_int, [C.c_int64, _dp, _dp, _dp, _dp]),
         "mfx_render_rgba8": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint8)]),
         "mfx_accumulate_render_rgba8": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint8)]),
         "mfx_stats": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -461,7 +505,7 @@ def _bind(lib, strict: bool = True):
 
 
 EXPORTED_SYMBOLS = [
-    "mfx_create", "mfx_create_instanced", "mfx_create_lights", "mfx_light_info", "mfx_light_table", "mfx_create_textured", "mfx_texture_info", "mfx_uv_table", "mfx_texel_index", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_sample_adaptive_resume", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_temporal", "mfx_pinhole_derive", "mfx_camera_info", "mfx_set_camera", "mfx_set_environment", "mfx_environment_info", "mfx_env_texel_index", "mfx_set_environment_sampled", "mfx_sky_sampling_info", "mfx_env_sample_table", "mfx_env_sample_direction", "mfx_set_lens", "mfx_lens_info", "mfx_lens_derive", "mfx_lens_rays", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
+    "mfx_create", "mfx_create_instanced", "mfx_create_lights", "mfx_light_info", "mfx_light_table", "mfx_create_textured", "mfx_texture_info", "mfx_uv_table", "mfx_texel_index", "mfx_expand_instances", "mfx_instancing_info", "mfx_build_instanced_info", "mfx_destroy", "mfx_sample", "mfx_sample_adaptive", "mfx_sample_adaptive_resume", "mfx_aov", "mfx_denoise", "mfx_denoise_var", "mfx_temporal", "mfx_pinhole_derive", "mfx_camera_info", "mfx_set_camera", "mfx_set_environment", "mfx_environment_info", "mfx_env_texel_index", "mfx_set_environment_sampled", "mfx_sky_sampling_info", "mfx_env_sample_table", "mfx_env_sample_direction", "mfx_set_lens", "mfx_lens_info", "mfx_lens_derive", "mfx_lens_rays", "mfx_set_normals", "mfx_normal_info", "mfx_normal_table", "mfx_shading_normal", "mfx_render_rgba8", "mfx_accumulate_render_rgba8", "mfx_reset",
     "mfx_film_mean", "mfx_stats",
     "mfx_trace_accumulate", "mfx_accum_clear", "mfx_accum_reduce", "mfx_accum_device_ptr", "mfx_accum_attach", "mfx_accum_read_mean",
     "mfx_sync", "mfx_stream", "mfx_ray_counts", "mfx_last_trace_ms", "mfx_trace_timing", "mfx_ray_counts_total", "mfx_closest_hit", "mfx_any_hit", "mfx_ref_leaves",

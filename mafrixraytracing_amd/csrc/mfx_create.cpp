@@ -112,7 +112,7 @@ static int texture_upload(mfx_ctx* c) {
 
 WfLdsShape mfxh::wf_lds_shape(const SceneImages& im, bool textured, bool shd, int nlds, int ntop, int nslot) {
     const WfLdsShape s{shd, nlds < im.stack_size, im.d_nodes_h != nullptr, nlds, ntop, (int)im.host.inst.size(), nslot,
-                       shd && im.multi_light(), shd && textured, false, shd && im.sky_light};
+                       shd && im.multi_light(), shd && textured, false, shd && im.sky_light, false, shd && im.normals};
     return s;
 }
 
@@ -185,7 +185,7 @@ static int scene_shapes(SceneImages& s, int device, const CreateEnv& env, bool t
         // waves per SIMD: more registers, no spills (C2 / C5 +2 %); with 4 it keeps the 4-wave one
         A.shadow_waves = sbpc <= 3 ? 3 : 4;
         if (env.shadow_waves) A.shadow_waves = *env.shadow_waves == 3 ? 3 : 4;
-        if (s.multi_light() || textured) A.shadow_waves = 4;  // the several-light and textured instances are the 4-wave build's only
+        if (s.multi_light() || textured || s.normals) A.shadow_waves = 4;  // the several-light, textured and SN instances are the 4-wave build's only
         if (A.shadow_waves == 3) sbpc = std::min(sbpc, 3);
         if (env.diag_iter)
             fprintf(stderr,
@@ -286,6 +286,8 @@ int mfxh::scene_relight(mfx_ctx* c) {
     else s.d_lights.reset();
     return scene_shapes(s, c->device, c->env, wf_textured(c), c->cuts.on);
 }
+
+int mfxh::scene_reshape(mfx_ctx* c) { return scene_shapes(c->scene, c->device, c->env, wf_textured(c), c->cuts.on); }
 #undef CK
 
 // Two-level or flat for an instanced scene. The flat image (one BVH over the expansion) is the faster
@@ -532,6 +534,7 @@ static int rebuild_for_camera(mfx_ctx* c, const char* who, const mfx_pinhole* ca
         const mfx_ctx* dv = ds[g];
         fresh[g].host = h;
         set_sky_light(fresh[g], dv->scene.sky_light);  // (a sampled sky stays a light of the new images)
+        fresh[g].normals = dv->scene.normals;          // (and the normals stay: their tables are the device's, not the images')
         rc = hipSetDevice(dv->device) == hipSuccess ? MFX_OK : fail(MFX_E_DEVICE, std::string(who) + ": hipSetDevice failed");
         if (rc == MFX_OK) rc = scene_upload(fresh[g], dv->env);
         if (rc == MFX_OK) rc = scene_shapes(fresh[g], dv->device, dv->env, wf_textured(dv), dv->cuts.on);

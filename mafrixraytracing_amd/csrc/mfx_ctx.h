@@ -1,6 +1,6 @@
 // mfx_ctx.h — the context behind the extern "C" boundary, shared by its translation units
 // (mfx_api.cpp, mfx_create.cpp, mfx_trace.cpp, mfx_readback.cpp, mfx_ahead.cpp, mfx_adaptive.cpp,
-// mfx_denoise_api.cpp, mfx_query.cpp, mfx_environment.cpp). Internal: never included from include/.
+// mfx_denoise_api.cpp, mfx_query.cpp, mfx_environment.cpp, mfx_normals.cpp). Internal: never included from include/.
 // Ownership: a GPU resource is a member (DevBuf, HostBuf, Event, Stream) of the struct of the
 // feature that uses it, and nothing is freed by hand. A feature that allocates at its first call is
 // a nested struct of mfx_ctx whose ready() says whether it has.
@@ -375,6 +375,16 @@ struct Lens {
     bool widened = false;
 };
 
+// Smooth shading (mfx_set_normals; mfx_normals.cpp), per device: the tables the SN instances read. Like the textures
+// they depend on the primitives alone and are no part of SceneImages: an mfx_set_camera rebuild leaves them where
+// they are. Whether they are on is SceneImages::normals (the launch shapes depend on it).
+struct Normals {
+    DevBuf<double> d_rec;      // [world primitives][12] the normal records
+    DevBuf<int32_t> d_flag;    // [world primitives] 1: smooth
+    int64_t nworld = 0, nsmooth = 0;
+    MfxSnTables tables() const { return d_rec ? MfxSnTables{d_rec, d_flag} : MfxSnTables{}; }
+};
+
 // What scene_shapes chooses for k_extend (ext) and k_shadow (shd): wf_trace copies it into a trace's WfParams
 struct LaunchShapes {
     int stack_lds_ext = 0, stack_lds_shd = 0;  // traversal stack entries per lane in LDS; the rest in d_spill
@@ -415,6 +425,10 @@ struct SceneImages {
     // pdf_n in `host` is (1 / area) / (N + 1) and one area light runs the several-light instances too. Set and
     // cleared by set_sky_light, which mfx_set_camera's rebuild applies to the images it builds.
     bool sky_light = false;
+    // the context has corner normals (mfx_set_normals): the SN twins of k_shadow, which are the 4-wave build's only
+    // and keep 16 B of LDS more. Set and cleared by mfx_set_normals, which asks for the launch shapes again;
+    // mfx_set_camera's rebuild copies it to the images it builds.
+    bool normals = false;
     // several lights (mfx_create_lights, N >= 2; a sampled sky beside N >= 1): the ML instances of k_shadow and
     // k_resolve, the wavefront pipeline for every trace, a light-index plane in the pool
     bool multi_light() const { return host.lights.size() >= 2 || sky_light; }
@@ -509,6 +523,7 @@ struct __attribute__((visibility("hidden"))) mfx_ctx {
     mfxh::Textures tex;
     mfxh::Environment sky;
     mfxh::Lens lens;
+    mfxh::Normals nrm;
 
     // the RCCL communicators, then the peers, then this device current; the members release themselves
     ~mfx_ctx();
@@ -546,6 +561,9 @@ inline bool wf_sky_sampled(const mfx_ctx* c) { return c->sky.on() && c->sky.samp
 // a thin lens (mfx_set_lens): the LENS twin of the k_extend instance that starts the paths (no k_camera, no camera
 // cuts) and of k_aov, the wavefront pipeline for every trace
 inline bool wf_lens(const mfx_ctx* c) { return c->lens.on; }
+
+// smooth shading (mfx_set_normals): the SN twins of k_shadow and k_aov, the wavefront pipeline for every trace
+inline bool wf_normals(const mfx_ctx* c) { return c->scene.normals; }
 
 // bytes of one path slot of the wavefront pool (ray queues included)
 inline size_t pool_slot_bytes(const mfx_ctx* c) {
@@ -589,6 +607,8 @@ int apply_camera_lens(mfx_ctx* c, const char* who, const mfx_pinhole* cam, const
 int lens_record(const char* who, const mfx_pinhole* cam, const mfx_lens* lens, MfxLensRec& rec);
 // after set_sky_light on c's images: the lights in HBM again and the launch shapes of the instances that run now
 int scene_relight(mfx_ctx* c);
+// after mfx_set_normals set or cleared SceneImages::normals: the launch shapes of the k_shadow instance that runs now
+int scene_reshape(mfx_ctx* c);
 // the LDS shape of k_extend or (shd) k_shadow over the scene images `s` of a context (textured: wf_textured) with
 // nlds stack entries per lane in LDS (the rest spilled), and ntop top nodes and nslot slots beside them
 WfLdsShape wf_lds_shape(const SceneImages& s, bool textured, bool shd, int nlds, int ntop = 0, int nslot = 0);

@@ -9,6 +9,7 @@
 
 #include "mfx_layout.h"
 #include "mfx_lens.h"
+#include "mfx_normals.h"
 #include "mfx_texture.h"
 
 #define MFX_AOV_PLANES 8  // normal xyz, hit t, albedo rgb, hit fraction
@@ -33,6 +34,7 @@ struct AovParams {
     MfxTexTables tx;          // albedo textures (all null without: the untextured instances run)
     MfxLensRec lens;          // a thin lens (mfx_set_lens; lens_on runs the LENS instances: the film's own lens rays)
     int32_t lens_on;
+    MfxSnTables sn;           // smooth shading (mfx_set_normals; both null without: the instances without run)
 };
 
 // k_atrous: one iteration of the edge-avoiding a-trous filter (the rule: include/mafrix_rt.h)
@@ -91,8 +93,8 @@ struct TemporalParams {
 };
 
 hipError_t mfx_launch_aov(const AovParams& P, hipStream_t st);
-// resident blocks per CU of k_aov's instance (two-level, textured, lens) with stack_size stack entries per lane in LDS
-hipError_t mfx_aov_occupancy(bool inst, bool tx, bool lens, int stack_size, int* blocks_per_cu);
+// resident blocks per CU of k_aov's instance (two-level, textured, lens, normals) with stack_size stack entries per lane in LDS
+hipError_t mfx_aov_occupancy(bool inst, bool tx, bool lens, int stack_size, int* blocks_per_cu, bool sn = false);
 hipError_t mfx_launch_temporal(const TemporalParams& P, hipStream_t st);
 hipError_t mfx_launch_atrous(const AtrousParams& P, hipStream_t st);
 hipError_t mfx_launch_atrous_var(const AtrousVarParams& P, hipStream_t st);

@@ -29,7 +29,9 @@
 // times the texel of the hit point, by the rule and the functions the path vertices use (mfx_texture.h).
 // LENS: the instances for a thin lens (mfx_set_lens): the ray is the film's own lens ray (mfx_lens.h), so plane [3]
 // is t along it.
-template <bool INST, bool TX = false, bool LENS = false>
+// SN: the twins for smooth shading (mfx_set_normals): on a smooth primitive the normal planes take the shading normal
+// of the hit point, by the rule and the function the path vertices use (mfx_normals.h).
+template <bool INST, bool TX = false, bool LENS = false, bool SN = false>
 __global__ void __launch_bounds__(256) k_aov(AovParams P) {
     extern __shared__ int lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -69,6 +71,18 @@ __global__ void __launch_bounds__(256) k_aov(AovParams P) {
             nm = vnormalize(vsub(vadd(o, vmul(d, B.t)), ld3(sh.n)));  // Sphere.fs:39-43
         else
             nm = ld3(sh.n);
+        if constexpr (SN) {
+            const int prim = sh.prim_kind >> 2;
+            if (P.sn.flag[prim]) {
+                const DV hp = vadd(o, vmul(d, B.t));  // Ray.PointAtParameter: the point k_extend stores
+                const double* r = P.sn.rec + (int64_t)MFX_SN_RECORD_DOUBLES * prim;
+                const double rec[12] = {r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], r[10], r[11]};
+                const double h3[3] = {hp.x, hp.y, hp.z}, g3[3] = {nm.x, nm.y, nm.z};
+                double s3[3];
+                mfx_sn_shade(rec, h3, g3, s3);
+                nm = dv(s3[0], s3[1], s3[2]);
+            }
+        }
         f[0] = f[0] + nm.x;
         f[1] = f[1] + nm.y;
         f[2] = f[2] + nm.z;
@@ -422,8 +436,18 @@ __global__ void k_dn_post(const double* __restrict__ src, int w, int h, double* 
 // ----------------------------------------------------------------------------------------------
 static inline unsigned dn_grid(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
-// k_aov's instance: two-level (inst), albedo textures (tx), a thin lens (lens)
-static const void* aov_kernel(bool inst, bool tx, bool lens) {
+// k_aov's instance: two-level (inst), albedo textures (tx), a thin lens (lens), smooth shading (sn: the twin of each)
+template <bool SN>
+static const void* aov_kernel_sn(bool inst, bool tx, bool lens) {
+    if (lens) {
+        if (tx) return inst ? (const void*)k_aov<true, true, true, SN> : (const void*)k_aov<false, true, true, SN>;
+        return inst ? (const void*)k_aov<true, false, true, SN> : (const void*)k_aov<false, false, true, SN>;
+    }
+    if (tx) return inst ? (const void*)k_aov<true, true, false, SN> : (const void*)k_aov<false, true, false, SN>;
+    return inst ? (const void*)k_aov<true, false, false, SN> : (const void*)k_aov<false, false, false, SN>;
+}
+static const void* aov_kernel(bool inst, bool tx, bool lens, bool sn = false) {
+    if (sn) return aov_kernel_sn<true>(inst, tx, lens);
     if (lens) {
         if (tx) return inst ? (const void*)k_aov<true, true, true> : (const void*)k_aov<false, true, true>;
         return inst ? (const void*)k_aov<true, false, true> : (const void*)k_aov<false, false, true>;
@@ -437,14 +461,16 @@ hipError_t mfx_launch_aov(const AovParams& P, hipStream_t st) {
     const dim3 g(dn_grid((int64_t)P.width * P.height, 256));
     // albedo textures: the TX instances
     if (P.tx.texels && (!P.tx.uvrec || !P.tx.ptex || !P.tx.desc)) return hipErrorInvalidValue;
+    // smooth shading: the SN twins
+    if ((P.sn.rec != nullptr) != (P.sn.flag != nullptr)) return hipErrorInvalidValue;
     void* args[] = {const_cast<AovParams*>(&P)};
-    const hipError_t e = hipLaunchKernel(aov_kernel(P.inst != nullptr, P.tx.texels != nullptr, P.lens_on != 0), g, dim3(256), args,
+    const hipError_t e = hipLaunchKernel(aov_kernel(P.inst != nullptr, P.tx.texels != nullptr, P.lens_on != 0, P.sn.rec != nullptr), g, dim3(256), args,
                                          aov_lds_bytes(P.stack_size), st);
     return e != hipSuccess ? e : hipGetLastError();
 }
 
-hipError_t mfx_aov_occupancy(bool inst, bool tx, bool lens, int stack_size, int* blocks_per_cu) {
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, aov_kernel(inst, tx, lens), 256, aov_lds_bytes(stack_size));
+hipError_t mfx_aov_occupancy(bool inst, bool tx, bool lens, int stack_size, int* blocks_per_cu, bool sn) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, aov_kernel(inst, tx, lens, sn), 256, aov_lds_bytes(stack_size));
 }
 
 hipError_t mfx_launch_temporal(const TemporalParams& P, hipStream_t st) {

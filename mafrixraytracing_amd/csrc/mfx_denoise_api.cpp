@@ -71,6 +71,7 @@ extern "C" int mfx_aov(mfx_ctx* c, int32_t spp, int64_t sample_base, double* out
     P.tx = c->tex.tables();  // albedo textures: k_aov's TX instances (all null without)
     P.lens = c->lens.rec;    // a thin lens: k_aov's LENS instances trace the film's own lens rays
     P.lens_on = wf_lens(c) ? 1 : 0;
+    P.sn = wf_normals(c) ? c->nrm.tables() : MfxSnTables{};  // smooth shading: k_aov's SN twins
     HIPCHECK(hipEventRecord(dn.ev0, c->stream));
     HIPCHECK(mfx_launch_aov(P, c->stream));
     HIPCHECK(hipEventRecord(dn.ev1, c->stream));

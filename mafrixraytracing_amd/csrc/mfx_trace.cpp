@@ -163,6 +163,8 @@ static void fill_scene_params(mfx_ctx* c, WfParams& P) {
     P.nlights = wf_multi_light(c) ? (int32_t)c->scene.host.lights.size() : 0;
     // albedo textures: the TX instances' tables (vtex set, by wf_ensure_pool: the launchers run them)
     P.tx = c->tex.tables();
+    // smooth shading: the SN instances' tables (set: mfx_wf_iteration launches them)
+    P.sn = wf_normals(c) ? c->nrm.tables() : MfxSnTables{};
     // a sky: the ENV instances' map (env_rec set, by wf_ensure_pool: the launchers run them)
     P.env_rgb = wf_env(c) ? c->sky.d_rgb.get() : nullptr;
     P.env_size = c->sky.size;
@@ -435,7 +437,7 @@ int mfxh::dev_trace_accumulate(mfx_ctx* c, int32_t spp, int64_t sample_base, Res
     // not pay the wavefront's per-bounce launches over a 2 M-path frame (r02e: 1.7 vs 7.9 ms at 1080p).
     // (several lights: always the wavefront, as under MFX_F_WAVEFRONT; creation refused MFX_F_MEGAKERNEL)
     // (albedo textures, a sky, a lens: likewise; mfx_set_environment and mfx_set_lens refuse an MFX_F_MEGAKERNEL context)
-    c->mega_last = !wf_multi_light(c) && !wf_textured(c) && !wf_env(c) && !wf_lens(c) && ((c->flags & MFX_F_MEGAKERNEL) != 0 || (ns == 1 && (c->flags & MFX_F_WAVEFRONT) == 0));
+    c->mega_last = !wf_multi_light(c) && !wf_textured(c) && !wf_env(c) && !wf_lens(c) && !wf_normals(c) && ((c->flags & MFX_F_MEGAKERNEL) != 0 || (ns == 1 && (c->flags & MFX_F_WAVEFRONT) == 0));
     if (ns == 0) {  // this partition has no sample in the call: zero rays in zero device time
         HIPCHECK(hipEventRecord(c->ev0, c->stream));
         HIPCHECK(hipEventRecord(c->ev1, c->stream));

@@ -32,6 +32,7 @@
 #include "mfx_environment.h"
 #include "mfx_layout.h"
 #include "mfx_lens.h"
+#include "mfx_normals.h"
 #include "mfx_texture.h"
 
 #define WF_FREE 0
@@ -232,8 +233,14 @@ struct WfParams {
     uint32_t* vsky;              // [vertex][stride] a sky vertex's texel id (beside vtex; allocated with a sampled sky only)
     // (A thin lens, mfx_set_lens, adds no field: its record lies behind the camera in device memory, cam_dev[1], where
     // k_extend's LENS instances read it (wf_lens_rec), and the launcher is told of it beside P. Kernel arguments of
-    // more than 1024 B cost every launch of every instance time, and these are 1000.)
+    // more than 1024 B cost every launch of every instance time, and these are 1016 with the tables below.)
+    // Smooth shading (mfx_set_normals; otherwise both null, and none of the instances without reads them). They run
+    // the SN twins of k_shadow: after the shade record the lane of a smooth primitive gathers its flag and its 96-B
+    // normal record and replaces the vertex's normal by the shading normal of the hit point (mfx_normals.h), before
+    // the sampler runs. k_extend, k_camera, k_resolve and the pool never see them.
+    MfxSnTables sn;
 };
+static_assert(sizeof(WfParams) <= 1024, "kernel arguments of more than 1024 B cost every launch time");
 static_assert(sizeof(MfxLensRec) <= sizeof(MfxCamera), "the lens record lies in the camera buffer's second element");
 #define WF_MAX_LIGHTS 64  // MFX_MAX_LIGHTS: a light index is 6 bits of k_shadow's pending flag word
 
@@ -308,6 +315,7 @@ struct WfLdsShape {
     bool env;       // k_extend's ENV instance (WfParams::env_rec set; the same LDS footprint)
     bool sky;       // k_shadow's SKY twin of the ml instance (WfParams::sky_tab set; the same LDS footprint)
     bool lens;      // k_extend's LENS twin of the instance that starts the paths (mfx_set_lens; the same LDS footprint)
+    bool sn;        // k_shadow's SN twin (WfParams::sn set; its table pointers take 16 B of LDS more)
 };
 // resident blocks per CU of the kernel instance that holds shape s
 hipError_t mfx_wf_kernel_occupancy(const WfLdsShape& s, int* blocks_per_cu);

@@ -977,6 +977,8 @@ struct TxShd {
     const MfxTexDesc* desc;
     uint32_t* vtex;
 };
+// k_shadow's SN twins keep the normal tables in LDS after TxShd's place (after the scene references without TX)
+static_assert(sizeof(MfxSnTables) == 16, "SnShd: 16 B of k_shadow's LDS");
 // k_shadow's array pointers in its LDS (after the light)
 struct ShdPtrs {
     double *ox, *oy, *oz, *dx, *dy, *dz, *vei, *vls;
@@ -1018,8 +1020,13 @@ struct ShdPtrs {
 // sends its shadow ray to the extension ray's far bound, and records cs and pdf_v where cs and solid go and N
 // as the light index. The table, the plane and the map's size lie in the light's LDS block after MlPtrs
 // (SkyPtrs), so the LDS footprint is the ML instance's.
+// SN: the twins for smooth shading (mfx_set_normals) of every 4-wave instance without counters, in each (ML, TX) state
+// and of the SKY twins: after the shade record (and TX's block) the lane of a smooth primitive loads its flag and its
+// 96-B normal record and replaces nm by the shading normal of the hit point (mfx_normals.h), before the sampler runs,
+// so the record is dead by then. The table pointers lie in 16 B of LDS after TxShd's place. A template parameter for
+// ML's reason.
 template <bool STATS, bool SPILL, int WAVES, int SK, bool Q, int LIST = WF_LIST_NONE, int NF = MFX_NF_ANY, bool ML = false,
-          bool TX = false, bool SKY = false>
+          bool TX = false, bool SKY = false, bool SN = false>
 __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
     constexpr bool INST = SK == WF_SK_INST, SLDS = SK == WF_SK_SLDS;
     extern __shared__ int lds_all[];
@@ -1057,6 +1064,11 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
     [[maybe_unused]] const TxShd& X = *(const TxShd*)(refs_lds + 1);  // TX: after the scene references
     if constexpr (TX) {
         if (threadIdx.x == 4) *(TxShd*)(refs_lds + 1) = TxShd{P.tx.uvrec, P.tx.ptex, P.tx.desc, P.vtex};
+    }
+    // SN: after TxShd (TX), or in its place
+    [[maybe_unused]] const MfxSnTables& NT = *(const MfxSnTables*)((const char*)(refs_lds + 1) + (TX ? sizeof(TxShd) : 0));
+    if constexpr (SN) {
+        if (threadIdx.x == 5) *(MfxSnTables*)((char*)(refs_lds + 1) + (TX ? sizeof(TxShd) : 0)) = P.sn;
     }
     if (threadIdx.x == 1) {
         PixParams px;
@@ -1189,6 +1201,17 @@ __global__ void __launch_bounds__(256, WAVES) k_shadow(WfParams P) {
                             id = mfx_tx_texel(X.desc[tex], tu, tv);
                         }
                         X.vtex[(int64_t)(P.max_depth - (dw & 0xff)) * P.vstride + jr] = id;
+                    }
+                    if constexpr (SN) {  // the shading normal of a smooth primitive (a sphere's flag is 0)
+                        const int prim = sh.prim_kind >> 2;
+                        if (NT.flag[prim]) {
+                            const double* r = NT.rec + (int64_t)MFX_SN_RECORD_DOUBLES * prim;
+                            const double rec[12] = {r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], r[10], r[11]};
+                            const double h3[3] = {hp.x, hp.y, hp.z}, g3[3] = {nm.x, nm.y, nm.z};
+                            double s3[3];
+                            mfx_sn_shade(rec, h3, g3, s3);
+                            nm = dv(s3[0], s3[1], s3[2]);
+                        }
                     }
                     // the key k_extend derived for the path's camera ray (same expressions), derived
                     // again at every vertex from the path's slot instead of stored (8 B written at the
@@ -1703,7 +1726,7 @@ static size_t wf_lds_bytes(const WfLdsShape& s) {
     const size_t stacks = (size_t)s.ntop * sizeof(MfxNode) + (size_t)std::min(s.ninst, WF_INST_LDS) * sizeof(MfxInstance) +
                           (size_t)s.nslot * 80 + (size_t)4 * s.stack_lds * 64 * sizeof(int);
     return s.shadow ? stacks + 4 * PendShd::BYTES + 64 + 4 * 2 * WF_SHD_LIST * sizeof(int) + sizeof(MfxLight) + sizeof(ShdPtrs) +
-                          sizeof(PixParams) + sizeof(SceneRefs) + (s.tx ? sizeof(TxShd) : 0)
+                          sizeof(PixParams) + sizeof(SceneRefs) + (s.tx ? sizeof(TxShd) : 0) + (s.sn ? sizeof(MfxSnTables) : 0)
                     : stacks + 4 * WF_EXT_PEND * sizeof(int) + 64;
 }
 
@@ -1790,6 +1813,11 @@ static constexpr bool camera_env_built(const WfKey& k) { return camera_built(k) 
 // (a sampled sky, SKY: k_shadow's twin of every several-light instance, textured or not; beside the key as ENV is.
 // k_extend and k_camera have none: their ENV twins run the camera rays, their plain instances the bounces.)
 static constexpr bool shadow_sky_built(const WfKey& k) { return shadow_built(k) && k.ml; }
+// (smooth shading, SN: k_shadow's twin of every 4-wave instance without the traversal counters, in each ml and tx
+// state, and of every SKY twin; beside the key as SKY is. Contexts created with MFX_F_COUNT_STATS refuse
+// mfx_set_normals, and a context with normals takes the 4-wave build. No other kernel of this file reads a normal.)
+static constexpr bool shadow_sn_built(const WfKey& k) { return shadow_built(k) && !k.stats && k.waves == 4; }
+static constexpr bool shadow_sky_sn_built(const WfKey& k) { return shadow_sky_built(k) && shadow_sn_built(k); }
 // (a thin lens, LENS: k_extend's twin of every path-starting instance without the traversal counters, and of its ENV
 // twin; beside the key as ENV is. Contexts created with MFX_F_COUNT_STATS refuse mfx_set_lens. k_camera has none: a
 // lens context's camera rays run k_extend; k_shadow and k_resolve never see where a camera ray came from.)
@@ -1811,12 +1839,16 @@ static_assert(built_count(extend_env_built) == (MFX_NODE_F16 ? 34 : 30) && built
 static_assert(built_count(shadow_sky_built) == (MFX_NODE_F16 ? 2 * 40 : 2 * 36),
               "the sampled sky's instances, SKY: the twin of every several-light k_shadow instance, untextured and "
               "textured, 2 * 40 / 2 * 36; k_resolve's six ML, ENV instances have a twin each");
+static_assert(built_count(shadow_sn_built) == (MFX_NODE_F16 ? 4 * 40 : 4 * 36) &&
+                  built_count(shadow_sky_sn_built) == (MFX_NODE_F16 ? 2 * 40 : 2 * 36),
+              "smooth shading's instances, SN: the twin of every 4-wave k_shadow instance without counters, 40 / 36 in each "
+              "of the four (ML, TX) states, and of every SKY twin, 2 * 40 / 2 * 36");
 static_assert(built_count(extend_lens_built) == 18,
               "the lens's instances, LENS: the twin of every START k_extend instance without counters (both spill states, "
               "three scene kinds, three list kinds), 18, and of the ENV twin of each, 18 more");
 
 enum { WF_K_EXTEND, WF_K_SHADOW, WF_K_CAMERA, WF_K_CAMERA_CUTS, WF_K_EXTEND_ENV, WF_K_CAMERA_ENV, WF_K_CAMERA_CUTS_ENV, WF_K_SHADOW_SKY, WF_K_EXTEND_LENS,
-       WF_K_EXTEND_LENS_ENV };
+       WF_K_EXTEND_LENS_ENV, WF_K_SHADOW_SN, WF_K_SHADOW_SKY_SN };
 template <int KERNEL, int I>
 static const void* instance_at() {
     constexpr WfKey k = key_at(I);
@@ -1840,6 +1872,10 @@ static const void* instance_at() {
         return (const void*)k_extend<k.stats, k.spill, k.sk, k.queue, k.start, k.list, k.nf, false, true>;
     else if constexpr (KERNEL == WF_K_EXTEND_LENS_ENV && extend_lens_built(k))
         return (const void*)k_extend<k.stats, k.spill, k.sk, k.queue, k.start, k.list, k.nf, true, true>;
+    else if constexpr (KERNEL == WF_K_SHADOW_SN && shadow_sn_built(k))
+        return (const void*)k_shadow<k.stats, k.spill, k.waves, k.sk, k.queue, k.list, k.nf, k.ml, k.tx, false, true>;
+    else if constexpr (KERNEL == WF_K_SHADOW_SKY_SN && shadow_sky_sn_built(k))
+        return (const void*)k_shadow<k.stats, k.spill, k.waves, k.sk, k.queue, k.list, k.nf, k.ml, k.tx, true, true>;
     else
         return nullptr;
 }
@@ -1856,8 +1892,11 @@ static const void* extend_kernel(const WfKey& k, bool env = false, bool lens = f
     return env ? instance<WF_K_EXTEND_ENV>(k, std::make_index_sequence<WF_KEYS>{})
                : instance<WF_K_EXTEND>(k, std::make_index_sequence<WF_KEYS>{});
 }
-// (sky: the SKY twin of a several-light key)
-static const void* shadow_kernel(const WfKey& k, bool sky = false) {
+// (sky: the SKY twin of a several-light key; sn: the SN twin of either)
+static const void* shadow_kernel(const WfKey& k, bool sky = false, bool sn = false) {
+    if (sn)
+        return sky ? instance<WF_K_SHADOW_SKY_SN>(k, std::make_index_sequence<WF_KEYS>{})
+                   : instance<WF_K_SHADOW_SN>(k, std::make_index_sequence<WF_KEYS>{});
     return sky ? instance<WF_K_SHADOW_SKY>(k, std::make_index_sequence<WF_KEYS>{})
                : instance<WF_K_SHADOW>(k, std::make_index_sequence<WF_KEYS>{});
 }
@@ -1888,7 +1927,7 @@ hipError_t mfx_wf_kernel_occupancy(const WfLdsShape& s, int* blocks_per_cu) {
     const WfKey k = shape_key(s, false, false, start, WF_LIST_NONE, 4);
     const size_t lds = wf_lds_bytes(s);
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        blocks_per_cu, s.shadow ? shadow_kernel(k, s.sky) : extend_kernel(k, s.env, s.lens), 256, lds);
+        blocks_per_cu, s.shadow ? shadow_kernel(k, s.sky, s.sn) : extend_kernel(k, s.env, s.lens), 256, lds);
     // (the API counts finer LDS granules than the hardware allocates: measured, k_shadow at 53,952 B per
     // block runs 2 blocks per CU where it says 3, a 10 % loss)
     *blocks_per_cu = std::min(*blocks_per_cu, mfx_lds_blocks(lds));
@@ -1915,7 +1954,8 @@ static WfLdsShape lds_shape(const WfParams& P, bool shadow) {
     const int stack_lds = shadow ? P.stack_lds_shd : P.stack_lds_ext;
     return {shadow, stack_lds < P.stack_size, wf_fp16(P), stack_lds, shadow ? P.ntop_shd : P.ntop_ext,
             P.inst ? P.ninst_lds : 0, shadow ? P.nslot_shd : P.nslot_ext, shadow && P.lights != nullptr,
-            shadow && P.vtex != nullptr, !shadow && P.env_rec != nullptr, shadow && P.sky_tab != nullptr};
+            shadow && P.vtex != nullptr, !shadow && P.env_rec != nullptr, shadow && P.sky_tab != nullptr, false,
+            shadow && P.sn.rec != nullptr};
 }
 
 static hipError_t launch_iteration(const WfParams& P, int ext_grid, int shd_grid, bool stats, hipStream_t st,
@@ -1943,8 +1983,8 @@ static hipError_t launch_iteration(const WfParams& P, int ext_grid, int shd_grid
     }
     const WfLdsShape s = lds_shape(P, true);
     const bool queue = P.qslot || P.ncount;
-    const void* shd = shadow_kernel(shape_key(s, stats, queue, false, list, shadow_build(P.shadow_waves)), s.sky);
-    if (!shd) return hipErrorInvalidValue;  // (several lights or textures with counters or the 3-wave build: refused at creation)
+    const void* shd = shadow_kernel(shape_key(s, stats, queue, false, list, shadow_build(P.shadow_waves)), s.sky, s.sn);
+    if (!shd) return hipErrorInvalidValue;  // (several lights, textures or normals with counters or the 3-wave build: refused by their entry points)
     launch(shd, shd_grid, wf_lds_bytes(s), st, P);
     return hipSuccess;
 }
@@ -1959,6 +1999,8 @@ hipError_t mfx_wf_iteration(const WfParams& P, int ext_grid, int shd_grid, bool 
     if ((P.sky_tab != nullptr) != (P.vsky != nullptr) || (P.sky_tab && (!P.env_rec || !P.lights))) return hipErrorInvalidValue;
     // albedo textures: the id plane and the tables go together (k_shadow<TX> reads the tables and writes vtex)
     if (P.vtex && (!P.tx.uvrec || !P.tx.ptex || !P.tx.desc || !P.tx.texels || stats)) return hipErrorInvalidValue;
+    // smooth shading: the records and the flags go together (k_shadow<SN> reads both)
+    if ((P.sn.rec != nullptr) != (P.sn.flag != nullptr) || (P.sn.rec && stats)) return hipErrorInvalidValue;
     // a sky: the record plane and the map go together (k_extend<ENV> / k_camera<ENV> write env_rec)
     if (P.env_rec && (!P.env_rgb || P.env_size < 1 || P.env_size > MFX_ENV_SIZE_MAX || stats)) return hipErrorInvalidValue;
     // a lens: no counters, no cut table (its camera rays share no origin)

@@ -12,7 +12,8 @@ import numpy as np
 
 from .abi import (INSTANCING_KEYS, LAUNCH_INFO_KEYS, MFX_DN_SRC_ACCUM, MFX_DN_SRC_ADAPTIVE, MFX_DN_SRC_HOST,
                   MFX_DN_SRC_TEMPORAL, MFX_F_NONE, MFX_F_TWO_LEVEL, MfxAdaptive, MfxAdaptiveResume, MfxDenoiseCfg,
-                  MfxDenoiseVarCfg, MfxInstance, MfxOptions, MfxPrimUv, MfxTemporalCfg, PRIM_UV_DTYPE, SceneArrays, check, dptr,
+                  MfxDenoiseVarCfg, MfxInstance, MfxOptions, MfxPrimNormals, MfxPrimUv, MfxTemporalCfg, PRIM_NORMALS_DTYPE,
+                  PRIM_UV_DTYPE, SceneArrays, check, dptr,
                   iptr, load_library, pinhole_struct, quad_lights, texture_structs, environment_struct, lens_struct)
 from .denoise import DenoiseConfig, DenoiseVarConfig
 from .temporal import TemporalConfig
@@ -28,7 +29,7 @@ class NativeContext:
                  part_index: int = 0, part_count: int = 1, devices: list[int] | None = None,
                  instancing: bool = True, render_ahead: int = 0, lights: list | None = None,
                  textures: list | None = None, prim_uv: np.ndarray | None = None, environment=None,
-                 sample_sky: bool = False, lens=None):
+                 sample_sky: bool = False, lens=None, normals: np.ndarray | None = None):
         """devices: drive this list of HIP devices from one context (mfx_options.devices; the
         library's own RCCL reduce sums them into devices[0]); None: the single `device`.
         instancing: a scene with instancing data is created through mfx_create_instanced (two-level
@@ -48,7 +49,10 @@ class NativeContext:
         with set_environment right after creation: rays that leave the scene return its texel. None: black.
         sample_sky: set it with mfx_set_environment_sampled instead: the sky is a light, sampled at every vertex.
         lens: (aperture, focus), set with set_lens right after creation: a thin lens with depth of field. None: the
-        pinhole."""
+        pinhole.
+        normals: corner normals (abi.PRIM_NORMALS_DTYPE, one per primitive the context is created from, as prim_uv),
+        set with set_normals right after creation: smooth shading. Pass arrays.prim_normals for a scene loaded with
+        normals=True, or normals.smooth_normals(prims). None: face normals."""
         self.lib = load_library()
         self.arrays = arrays
         self.w, self.h = arrays.width, arrays.height
@@ -95,6 +99,8 @@ class NativeContext:
                 self.set_environment(environment, sampled=sample_sky)
             if lens is not None:
                 self.set_lens(lens)
+            if normals is not None:
+                self.set_normals(normals)
         except Exception:
             self.close()
             raise
@@ -250,6 +256,26 @@ class NativeContext:
             return
         ln = lens_struct(lens)
         check(self.lib.mfx_set_lens(self._h, C.byref(ln)), "mfx_set_lens")
+
+    def set_normals(self, normals):
+        """mfx_set_normals: make `normals` (abi.PRIM_NORMALS_DTYPE, one per primitive the context was created from:
+        the templates of an instanced scene, the world list otherwise) the corner normals of every later call: a
+        smooth primitive is shaded with the interpolated normal of the hit point (the rule: include/mafrix_rt.h,
+        normals.py); None removes them. The film, the accumulator and next_sample are left as they are; aov() and
+        sample_adaptive() must run again before denoise, denoise_var and sample_adaptive_resume."""
+        if normals is None:
+            check(self.lib.mfx_set_normals(self._h, None, 0), "mfx_set_normals")
+            return
+        pn = np.ascontiguousarray(normals, dtype=PRIM_NORMALS_DTYPE)
+        check(self.lib.mfx_set_normals(self._h, pn.ctypes.data_as(C.POINTER(MfxPrimNormals)), len(pn)), "mfx_set_normals")
+
+    def normal_info(self) -> np.ndarray:
+        """mfx_normal_info: [0] smooth world primitives, [1] 1 if the SN kernel instances run, [2] device bytes of the
+        tables, [3] 0 (no pool bytes), [4] / [5] resident blocks per CU of the k_shadow / k_aov instance in use; the
+        rest 0. All 0 without normals."""
+        out = np.zeros(8)
+        check(self.lib.mfx_normal_info(self._h, dptr(out)), "mfx_normal_info")
+        return out
 
     def lens_info(self) -> np.ndarray:
         """mfx_lens_info: [0] 1 with a lens, [1] aperture, [2] focus, [3:6] U, [6:9] V, [9] s, [10] the eps the lens

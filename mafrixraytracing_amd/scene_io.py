@@ -22,7 +22,13 @@ and whose corners all have a `vt` carries them into SceneArrays.textures / prim_
 A shapelist or instances element replaces the material, as ever, and keeps the face's map. Without
 textures=True nothing of this is read and every result is what it was.
 
-Documented extensions: `vt`/`vn`/`o`/`s` lines are accepted and ignored
+Smooth shading (an extension; normals=True on load_obj, InitSceneState and load_scene_file): `vn`
+lines and the faces' `v//vn` and `v/vt/vn` indices are kept, and a face whose corners all have a `vn` carries them
+into SceneArrays.prim_normals (mfx_set_normals). A quad face that carries `vn` is emitted as the two triangles
+(v0,v1,v2), (v0,v2,v3), so that all four normals count: the primitive list then differs from the default load's (a
+quad without `vn` stays a Rect). Without normals=True nothing of this is read and every result is what it was.
+
+Documented extensions: `vt`/`vn`/`o`/`s` lines are accepted and ignored (unless asked for, above)
 (an `o` name may contain dots, which FindModel's `model.group` split rejects), trailing whitespace/CR is trimmed from group names (the
 FParsec grammar as shipped rejects the bundled meshes — SURVEY.md §0.4); a `.npz` mesh
 (converted OBJ, scripts/make_scenes.py) may stand in for an `.obj`; and
@@ -43,7 +49,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .abi import (INSTANCE_DTYPE, MFX_INSTANCE_VERBATIM, MFX_PRIM_RECT, MFX_PRIM_SPHERE, MFX_PRIM_TRIANGLE,
-                  PRIM_DTYPE, PRIM_UV_DTYPE, SceneArrays)
+                  PRIM_DTYPE, PRIM_NORMALS_DTYPE, PRIM_UV_DTYPE, SceneArrays)
 
 
 class SceneError(ValueError):
@@ -110,6 +116,7 @@ class Prim:
     material: int
     uv: tuple | None = None  # textures=True: the (u, v) of the first three corners of a face with a map
     texture: int = -1        # and its texture (MaterialManager.textures)
+    nrm: tuple | None = None  # normals=True: the `vn` of the three corners of a triangle whose corners all have one
 
 
 def load_texture(path: str) -> np.ndarray:
@@ -178,14 +185,17 @@ def _vi(i: int, n: int) -> int:
     return i - 1 if i > 0 else n + i  # VertexReferencing.VI, ObjModelLoader.fs:63-64
 
 
-def load_obj(path: str, manager: MaterialManager, textures: bool = False) -> ObjState:
+def load_obj(path: str, manager: MaterialManager, textures: bool = False, normals: bool = False) -> ObjState:
     """LoadObjModel (ObjModelLoader.fs:306-340) plus the documented grammar extensions.
     textures: keep `vt` and the faces' `v/vt` indices, and read the MTL's map_Kd (a `.npz` mesh carries no
-    UVs: its primitives stay untextured)."""
+    UVs: its primitives stay untextured).
+    normals: keep `vn` and the faces' `v//vn` and `v/vt/vn` indices; a quad face whose corners all have a `vn` becomes
+    the two triangles (v0,v1,v2), (v0,v2,v3) (a `.npz` mesh carries no normals: normals.smooth_normals makes them)."""
     if path.endswith(".npz"):
         return load_npz_mesh(path, manager)
     st = ObjState()
     vts: list = []
+    vns: list = []
     with open(path, "r", encoding="utf-8", errors="replace") as f:
         lines = f.read().split("\n")
     # the reference loads the first mtllib before replaying statements (:317-330)
@@ -212,6 +222,10 @@ def load_obj(path: str, manager: MaterialManager, textures: bool = False) -> Obj
             if len(tok) < 3:
                 raise SceneError(f"{path}: vt needs 2 coordinates: {line!r}")
             vts.append((float(tok[1]), float(tok[2])))
+        elif key == "vn" and normals:
+            if len(tok) < 4:
+                raise SceneError(f"{path}: vn needs 3 coordinates: {line!r}")
+            vns.append((float(tok[1]), float(tok[2]), float(tok[3])))
         elif key in ("vt", "vn", "s", "o", "mtllib", "maplib", "usemap"):
             continue
         elif key == "g":
@@ -230,8 +244,20 @@ def load_obj(path: str, manager: MaterialManager, textures: bool = False) -> Obj
                 if all(len(q) >= 2 and q[1] for q in parts):  # every corner has a vt: the first three map the face
                     uv = tuple(vts[_vi(int(q[1]), len(vts))] for q in parts[:3])
                     tex = manager.material_texture[mat]
-            if len(pts) == 3:
-                st.groups[cur].append(Prim(MFX_PRIM_TRIANGLE, pts, mat, uv, tex))
+            nrm = None
+            if normals:
+                parts = [t.split("/") for t in tok[1:]]
+                if all(len(q) >= 3 and q[2] for q in parts):  # every corner has a vn
+                    nrm = tuple(vns[_vi(int(q[2]), len(vns))] for q in parts)
+            if nrm is not None and len(pts) == 4:  # two triangles, so that all four normals count
+                uv2 = None
+                if uv is not None:
+                    uv2 = tuple(vts[_vi(int(parts[k][1]), len(vts))] for k in (0, 2, 3))
+                st.groups[cur].append(Prim(MFX_PRIM_TRIANGLE, pts[:3], mat, uv, tex, nrm[:3]))
+                st.groups[cur].append(Prim(MFX_PRIM_TRIANGLE, (pts[0], pts[2], pts[3]), mat, uv2, tex if uv2 is not None else -1,
+                                           (nrm[0], nrm[2], nrm[3])))
+            elif len(pts) == 3:
+                st.groups[cur].append(Prim(MFX_PRIM_TRIANGLE, pts, mat, uv, tex, nrm))
             elif len(pts) == 4:
                 st.groups[cur].append(Prim(MFX_PRIM_RECT, pts, mat, uv, tex))
             else:
@@ -317,6 +343,8 @@ class SceneState:
     lights: list | None = None
     # InitSceneState(textures=True): SceneArrays gets the manager's textures and the primitives' maps
     textures: bool = False
+    # InitSceneState(normals=True): SceneArrays gets the primitives' corner normals
+    normals: bool = False
 
     def arrays(self, max_depth: int = 3, width: int | None = None, height: int | None = None) -> SceneArrays:
         inst = None
@@ -337,7 +365,8 @@ class SceneState:
         return SceneArrays(_prim_array(self.prims), self.manager.albedo_table(), self.light, self.camera,
                            width or self.width, height or self.height, max_depth, instancing=inst, lights=self.lights,
                            textures=list(self.manager.textures) if self.textures else None,
-                           prim_uv=prim_uv_array(self.prims) if self.textures else None)
+                           prim_uv=prim_uv_array(self.prims) if self.textures else None,
+                           prim_normals=prim_normals_array(self.prims) if self.normals else None)
 
 
 def prim_uv_array(plist) -> np.ndarray:
@@ -348,6 +377,16 @@ def prim_uv_array(plist) -> np.ndarray:
         if p.texture >= 0 and p.uv is not None:
             out[k]["texture"] = p.texture
             out[k]["uv"] = p.uv
+    return out
+
+
+def prim_normals_array(plist) -> np.ndarray:
+    """abi.PRIM_NORMALS_DTYPE corner normals of a list of Prim (smooth 0 and zeros for a primitive without them)."""
+    out = np.zeros(len(plist), dtype=PRIM_NORMALS_DTYPE)
+    for k, p in enumerate(plist):
+        if p.nrm is not None:
+            out[k]["smooth"] = 1
+            out[k]["n"] = p.nrm
     return out
 
 
@@ -370,7 +409,7 @@ def translate(p: Prim, off) -> Prim:
     if p.kind == MFX_PRIM_SPHERE:
         c = p.pts[0]
         return Prim(p.kind, ((c[0] + off[0], c[1] + off[1], c[2] + off[2]), p.pts[1]), p.material)
-    return Prim(p.kind, tuple((q[0] + off[0], q[1] + off[1], q[2] + off[2]) for q in p.pts), p.material, p.uv, p.texture)
+    return Prim(p.kind, tuple((q[0] + off[0], q[1] + off[1], q[2] + off[2]) for q in p.pts), p.material, p.uv, p.texture, p.nrm)
 
 
 def _find_model(ref: str, models: dict):
@@ -395,7 +434,8 @@ RELEASE_FALLBACK_LIGHT = {
 
 
 def InitSceneState(xml_text: str, base_dir: str = ".", manager: MaterialManager | None = None,
-                   light_fallback: str = "debug", all_lights: bool = False, textures: bool = False) -> SceneState:
+                   light_fallback: str = "debug", all_lights: bool = False, textures: bool = False,
+                   normals: bool = False) -> SceneState:
     """InitSceneState (Scene.fs:265-271): parse XML *text*, version must be 0.1.
 
     all_lights: with True, every <Light type="area"> element becomes a light, in document order
@@ -404,6 +444,10 @@ def InitSceneState(xml_text: str, base_dir: str = ".", manager: MaterialManager 
 
     textures: with True, the models' `vt` coordinates and map_Kd textures are read and SceneState.arrays()
     carries them (SceneArrays.textures, prim_uv; mfx_create_textured). The default reads neither.
+
+    normals: with True, the models' `vn` normals are read and SceneState.arrays() carries them
+    (SceneArrays.prim_normals, one per world primitive; mfx_set_normals). A quad face with `vn` becomes two
+    triangles (load_obj), so the primitive list differs from the default load's. The default reads none.
 
     light_fallback: what a light group whose first primitive is not a Rect does. "debug" (the
     default) raises SceneError, as the reference's Debug build does at `assert(false)`
@@ -450,7 +494,7 @@ def InitSceneState(xml_text: str, base_dir: str = ".", manager: MaterialManager 
                 fname = a.get("value")
             else:
                 raise SceneError(f"unknown model argument {a.get('name')!r}")
-        models[n.get("name")] = load_obj(os.path.join(base_dir, fname), mgr, textures)
+        models[n.get("name")] = load_obj(os.path.join(base_dir, fname), mgr, textures, normals)
     # Light (Scene.fs:179-199)
     def parse_light(ln):
         if ln is None or ln.get("type") != "area":
@@ -525,7 +569,7 @@ def InitSceneState(xml_text: str, base_dir: str = ".", manager: MaterialManager 
                     raise SceneError(f"unknown instances argument {nm!r}")
             key = (ref, mat)
             if key not in templates:
-                templates[key] = [Prim(p.kind, p.pts, mat, p.uv, p.texture) for p in _find_model(ref, models)]
+                templates[key] = [Prim(p.kind, p.pts, mat, p.uv, p.texture, p.nrm) for p in _find_model(ref, models)]
             for off in offs:
                 segments.append(("instance", key, off, len(prims), len(templates[key])))
                 prims.extend(translate(p, off) for p in templates[key])
@@ -540,7 +584,7 @@ def InitSceneState(xml_text: str, base_dir: str = ".", manager: MaterialManager 
                 else:
                     raise SceneError(f"unknown shape argument {a.get('name')!r}")
             for p in _find_model(ref, models):
-                prims.append(Prim(p.kind, p.pts, mat, p.uv, p.texture))
+                prims.append(Prim(p.kind, p.pts, mat, p.uv, p.texture, p.nrm))
         elif t == "sphere":  # extension
             c, r, mat = (0.0, 0.0, 0.0), 1.0, 0
             for a in s:
@@ -563,16 +607,16 @@ def InitSceneState(xml_text: str, base_dir: str = ".", manager: MaterialManager 
     for p in prims:
         if not (0 <= p.material < len(mgr.materials)):
             raise SceneError(f"material index {p.material} out of range (manager has {len(mgr.materials)})")
-    return SceneState(cam, light, w, h, prims, mgr, segments, templates, lights, textures)
+    return SceneState(cam, light, w, h, prims, mgr, segments, templates, lights, textures, normals)
 
 
 def load_scene_file(path: str, fresh_manager: bool = True, light_fallback: str = "debug", all_lights: bool = False,
-                    textures: bool = False, **kw) -> SceneArrays:
+                    textures: bool = False, normals: bool = False, **kw) -> SceneArrays:
     """Convenience: XML file -> SceneArrays, with a fresh MaterialManager (the reference's
     manager is process-global; a fresh one gives the index space of a first load)."""
     with open(path, "r", encoding="utf-8") as f:
         text = f.read()
     mgr = MaterialManager() if fresh_manager else None
     st = InitSceneState(text, base_dir=os.path.dirname(os.path.abspath(path)), manager=mgr,
-                        light_fallback=light_fallback, all_lights=all_lights, textures=textures)
+                        light_fallback=light_fallback, all_lights=all_lights, textures=textures, normals=normals)
     return st.arrays(**kw)
